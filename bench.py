@@ -13,8 +13,17 @@ step (÷G: the gradient of the global B-row minibatch), advantage statistics are
 runs rank 0's shard of a G-way split on one GPU (E/G envs, B/G rows), for tuning the shard shapes.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c4|c3|c2|c5|c5f32] [--batch B] [--weak]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
     (torch.distributed.run is only the launcher: this process never imports torch)
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the legs that take
+runs of their own: the device rollout measurement, the serialised kernel pass behind `roofline` and
+the per-kernel breakdown, and the CPU baseline (each still has its `--no-...` switch).
+`--dump-outputs DIR` writes DIR/<name>.npy (float32), every file the same in every run: the advantages
+and value targets of the last timed step's GAE pass.  The parameters that step leaves carry the
+run-to-run noise of its float atomics and are not written.  With the option the last
+timed step starts from the seeded initial parameters and Adam state (restored with the clock stopped).
 
 Prints ONE JSON line (rank 0).  `value` = learner env-steps/s over all ranks = world·N / t_update.
 """
@@ -128,6 +137,82 @@ def cpu_info():
     return model, os.cpu_count() or 1, usable
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def packed_params(lib, nn_ptr):
+    """[W0, b0, W1, b1, ...] of a NeuralNetwork, read from HBM."""
+    nn = nn_ptr.contents
+    out = []
+    for i in range(nn.num_layers - 1):
+        ly = nn.layers[i]
+        out.append(ppo_ffi.d2h(lib, ly.d_weights, np.float32, ly.input_size * ly.output_size))
+        out.append(ppo_ffi.d2h(lib, ly.d_biases, np.float32, ly.output_size))
+    return np.concatenate(out)
+
+
+def set_packed_params(lib, nn_ptr, params):
+    nn = nn_ptr.contents
+    off = 0
+    for i in range(nn.num_layers - 1):
+        ly = nn.layers[i]
+        for ptr, n in ((ly.d_weights, ly.input_size * ly.output_size), (ly.d_biases, ly.output_size)):
+            ppo_ffi.h2d(lib, ptr, np.ascontiguousarray(params[off:off + n]))
+            off += n
+
+
+def learner_state(lib, ppo, A):
+    """Everything an update reads and writes besides the rollout: parameters, log σ and the Adam states."""
+    p = ppo.contents
+    adams = [a.contents for a in (p.adam_V, p.adam_policy, p.adam_entropy)]
+    return {"V": packed_params(lib, p.V), "mu": packed_params(lib, p.policy.contents.mu),
+            "log_std": ppo_ffi.d2h(lib, p.policy.contents.d_log_std, np.float32, A),
+            "adam": [(ppo_ffi.d2h(lib, a.m, np.float32, a.span), ppo_ffi.d2h(lib, a.v, np.float32, a.span), a.time_step)
+                     for a in adams]}
+
+
+def restore_learner_state(lib, ppo, st, dtype_code):
+    p = ppo.contents
+    set_packed_params(lib, p.V, st["V"])
+    set_packed_params(lib, p.policy.contents.mu, st["mu"])
+    ppo_ffi.h2d(lib, p.policy.contents.d_log_std, st["log_std"])
+    for a, (m, v, t) in zip((p.adam_V, p.adam_policy, p.adam_entropy), st["adam"]):
+        ppo_ffi.h2d(lib, a.contents.m, m)
+        ppo_ffi.h2d(lib, a.contents.v, v)
+        a.contents.time_step = t
+    if dtype_code == 1:                                                  # bf16 mode: refresh the bf16 weight shadow
+        lib.ppo_set_compute_dtype(ppo, 1)
+
+
+DUMP_FILES = 2                                                          # each may take DUMP_LIMIT_BYTES / 2
+
+
+def save_arrays(out_dir, arrays):
+    """out_dir/<name>.npy, float32.  An array over its share of DUMP_LIMIT_BYTES is cut to a fixed seeded
+    sample of its elements (in index order)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // DUMP_FILES
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def dump_outputs(lib, ppo, N, out_dir):
+    """Of what the last timed ppo_update left with its caller, the part every run repeats bit for bit:
+    the normalised advantages and the value targets its GAE pass wrote into the buffer (two value
+    forwards over the whole rollout, the scan, the global normalisation).  The parameters that update
+    leaves cannot be compared array by array: the gradient sums of its minibatch steps use float
+    atomics, whose order changes from run to run, and Adam over the 448 steps turns that rounding
+    into differences of 3 % of the largest parameter (C4, one update from identical state: 4e-3 of
+    0.13); the same update with the atomic-free gradient GEMMs (ppo_gemm_tune(., 1)) differs as much,
+    its heads and bias sums use float atomics too.  So nothing of the minibatch steps is written."""
+    b = ppo.contents.buffer.contents
+    save_arrays(out_dir, {"advantage": ppo_ffi.d2h(lib, b.d_advantage_p, np.float32, N),
+                          "adv_target": ppo_ffi.d2h(lib, b.d_adv_target_p, np.float32, N)})
+
+
 def cpu_baseline(lib, ppo, S, H, A, N, B, sample_envs=16, steps=2):
     """The oracle (plain-C restatement of the reference CPU path, OpenBLAS sgemm, 1 thread) on a bounded
     sample of the same workload; extrapolated to one full update with the update formula."""
@@ -151,20 +236,10 @@ def cpu_baseline(lib, ppo, S, H, A, N, B, sample_envs=16, steps=2):
         "truncated": ppo_ffi.d2h(lib, b.d_truncated_p, np.uint8, Ns),
     }
     sizes = [S] + H + [A]
-
-    def packed(nn_ptr):
-        nn = nn_ptr.contents
-        out = []
-        for i in range(nn.num_layers - 1):
-            ly = nn.layers[i]
-            out.append(ppo_ffi.d2h(lib, ly.d_weights, np.float32, ly.input_size * ly.output_size))
-            out.append(ppo_ffi.d2h(lib, ly.d_biases, np.float32, ly.output_size))
-        return np.concatenate(out)
-
     pol = ppo.contents.policy.contents
-    mu0 = packed(pol.mu)
+    mu0 = packed_params(lib, pol.mu)
     ls0 = ppo_ffi.d2h(lib, pol.d_log_std, np.float32, A)
-    v0 = packed(ppo.contents.V)
+    v0 = packed_params(lib, ppo.contents.V)
     nb = N // B
 
     def timed(threads):
@@ -211,6 +286,12 @@ def main():
                     help="one GPU runs rank 0's shard of a G-way split (E/G envs, B/G rows per step); the line is "
                          "then a per-rank shard measurement, not the metric")
     ap.add_argument("--shuffle", type=int, default=1, help="1 = device Feistel shuffle, 0 = reference host rand()")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the rollout measurement, the serialised "
+                         "kernel pass (roofline, per-kernel breakdown) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write, as DIR/<name>.npy, the last one's advantages and value targets "
+                         "(they repeat bit for bit from run to run; its parameters do not and are not written)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--gemm-flags", type=int, default=0, help="ppo_gemm_flags experiment bits (A/B runs)")
@@ -222,6 +303,8 @@ def main():
                          "costs a few µs of stream time, so the throughput run samples)")
     ap.add_argument("--seed", type=int, default=1234)
     args = ap.parse_args()
+    if not args.full:                                                    # a plain run: the timed steps only
+        args.no_cpu_baseline = args.no_kernel_events = args.no_rollout = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -289,6 +372,13 @@ def main():
         LIB.ppo_synchronize()
         LIB.ppo_comm_barrier()
 
+    # --dump-outputs: the update's float atomics reorder its gradient sums from run to run, and the
+    # minibatch steps turn that rounding into visibly different parameters within one update.  So that
+    # the last timed step's GAE pass sees the same value network in every run, that step starts from
+    # the seeded initial learner state, put back while the clock is stopped (below).
+    dumping = bool(args.dump_outputs) and args.steps > 0
+    state0 = learner_state(LIB, ppo, A) if dumping else None
+
     for _ in range(args.warmup):
         LIB.ppo_update(ppo, 0.99, B, 4, 10, args.shuffle, args.seed)
     barrier()
@@ -298,13 +388,36 @@ def main():
     # one event pair per class); kernel timing is the serialised pass below
     LIB.ppo_prof_enable(1 << 30)
     barrier()
+    stopped = 0.0
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
+        if dumping and i == args.steps - 1:
+            barrier()
+            s0 = time.perf_counter()
+            restore_learner_state(LIB, ppo, state0, 1 if dtype == "bf16" else 0)
+            barrier()
+            stopped = time.perf_counter() - s0
         LIB.ppo_update(ppo, 0.99, B, 4, 10, args.shuffle, args.seed)
     barrier()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - stopped
     LIB.ppo_prof_enable(0)
     elapsed = LIB.ppo_comm_max_f64(elapsed)                              # max over ranks
+
+    def prof_snapshot():
+        ms, work, launches = (C.c_double * 7)(), (C.c_double * 7)(), (C.c_long * 7)()
+        LIB.ppo_prof_read(ms, work, launches)
+        issued, issued_work = (C.c_long * 7)(), (C.c_double * 7)()
+        LIB.ppo_prof_counts(issued)
+        LIB.ppo_prof_issued_work(issued_work)
+        return list(ms), list(work), list(launches), list(issued), list(issued_work)
+
+    def loss_stats():
+        st = (C.c_double * 7)()
+        LIB.ppo_read_stats(ppo, st, 7)
+        return st
+
+    if dumping and rank == 0:                                            # before any other leg touches the state
+        dump_outputs(LIB, ppo, N, args.dump_outputs)
 
     # batched device rollout of the same E x T (SURVEY §8d "rollout env-steps/s", reported beside
     # the learner throughput; not part of `value`): one warm call, then one timed call
@@ -319,17 +432,7 @@ def main():
         t_rollout = time.perf_counter() - r0
         t_rollout = LIB.ppo_comm_max_f64(t_rollout)
 
-    def prof_snapshot():
-        ms, work, launches = (C.c_double * 7)(), (C.c_double * 7)(), (C.c_long * 7)()
-        LIB.ppo_prof_read(ms, work, launches)
-        issued, issued_work = (C.c_long * 7)(), (C.c_double * 7)()
-        LIB.ppo_prof_counts(issued)
-        LIB.ppo_prof_issued_work(issued_work)
-        return list(ms), list(work), list(launches), list(issued), list(issued_work)
-
-    ms, work, launches, issued, issued_work = prof_snapshot()
-    stats = (C.c_double * 7)()
-    LIB.ppo_read_stats(ppo, stats, 7)
+    (ms, work, launches, issued, issued_work), stats = prof_snapshot(), loss_stats()
 
     # Kernel pass for the roofline (not part of `value`): in the timed region the value and policy
     # minibatch loops overlap on two streams, so a launch's event time there includes the share of
@@ -396,6 +499,7 @@ def main():
         "warmup": args.warmup,
         "ms_per_step": 1000.0 * t_update,
         "higher_is_better": True,
+        "full": args.full,
         "scaling": "weak" if args.weak else "strong",
         "vs_baseline": None,
         "dtype": dtype,

@@ -54,9 +54,11 @@ def test_struct_layouts_match_ctypes(lib_built):
 
 def test_reference_main_compiles_unchanged_against_headers(tmp_path):
     """The reference's main.c (as shipped) compiles against include/ with no warnings (gcc and clang)."""
-    main_c = "/root/reference/src/main.c"
-    if not os.path.exists(main_c):      # the GPU box has no reference tree; the built bin/ppo_main travels
-        assert os.path.exists(os.path.join(ROOT, "ppo.c_amd", "bin", "ppo_main"))
+    ref = subprocess.run(["make", "-s", "--no-print-directory", "-C", os.path.join(ROOT, "oracle"), "ref-dir"],
+                         capture_output=True, text=True, check=True).stdout.strip()   # the Makefile's REF
+    main_c = os.path.join(ref, "src", "main.c")
+    if not os.path.exists(main_c):      # no reference tree here: the built oracle/_ref/ppo_main travels
+        assert os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ppo_main"))
         return
     for cc in ("gcc", "/opt/rocm/llvm/bin/clang"):
         r = subprocess.run([cc, "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", main_c, "-o",

@@ -12,7 +12,7 @@ Covers the host-pointer half of the reference interface:
   * save_ppo byte for byte against the oracle's restatement of the reference writer
     (ppo.cu:585-611, policy.cu:207-211, neural_network.cu:283-300, adam.cu:172-189), load_ppo round
     trips, and a loaded checkpoint trains exactly like the original;
-  * the reference's unchanged main.c (bin/ppo_main, linked against libppo) runs to completion.
+  * the reference's unchanged main.c (oracle/_ref/ppo_main, linked against libppo) runs to completion.
 """
 import ctypes as C
 import os
@@ -277,11 +277,12 @@ def test_checkpoint_bytes_and_round_trip(lib, oracle, tmp_path, sizes, N, B):
 
 
 def test_reference_main_binary_runs(lib, tmp_path):
-    """/root/reference/src/main.c, compiled unchanged against include/ and linked to libppo
-    (bin/ppo_main, built by `make -C ppo.c_amd main` in the build container): 10 epochs of
-    30000 steps on Pendulum-v1 with eval and the checkpoint at the end."""
-    exe = os.path.join(ROOT, "ppo.c_amd", "bin", "ppo_main")
-    assert os.path.exists(exe), "bin/ppo_main not built (make -C ppo.c_amd main)"
+    """The reference's main.c, compiled unchanged against include/ and linked to libppo
+    (oracle/_ref/ppo_main, built by `make -C oracle ref` where the reference tree is present; the
+    binary travels with the tree to the GPU machine): 10 epochs of 30000 steps on Pendulum-v1 with
+    eval and the checkpoint at the end."""
+    exe = os.path.join(ROOT, "oracle", "_ref", "ppo_main")
+    assert os.path.exists(exe), "oracle/_ref/ppo_main not built (make -C oracle ref, where the reference tree is)"
     r = subprocess.run([exe, "64"], cwd=tmp_path, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     evals = parse_eval(r.stdout)

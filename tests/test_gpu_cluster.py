@@ -118,7 +118,7 @@ def test_cluster_first_steps_vs_oracle(lib, oracle, sizes):
     np.testing.assert_allclose(a["stats"][2], ref["sum_policy_loss"], rtol=1e-3, atol=1e-5)
 
 
-def oracle_motion(oracle, a, sizes, lim, n_pol, n_val, mode, ent=0.0):
+def oracle_motion(oracle, a, sizes, lim, n_pol, n_val, mode, ent=0.0, with_sums=False):
     """The oracle's update of run()'s buffer from run()'s initial state (Feistel order, seed 9), its
     products re-associated per `mode` (oracle_ffi.blas_mode: 0 proper, 1 split-K halves, 2 double
     products rounded once) — returns (value motion, policy motion).  16 OpenBLAS threads: measured
@@ -133,6 +133,8 @@ def oracle_motion(oracle, a, sizes, lim, n_pol, n_val, mode, ent=0.0):
     finally:
         oracle.blas_mode(0)
         lib.ref_blas_threads(1)
+    if with_sums:      # + (value-loss sum, policy-loss sum) over the update's steps
+        return ref["v"] - a["v0"], ref["mu"] - a["mu0"], (ref["sum_v_loss"], ref["sum_policy_loss"])
     return ref["v"] - a["v0"], ref["mu"] - a["mu0"]
 
 
@@ -184,8 +186,25 @@ def test_cluster_full_update_matches_multilaunch(lib, oracle, shuffle, sizes):
     assert not a["multi"] and b["multi"]
     assert a["t"] == b["t"] == (2560, 1024, 1024)
     assert a["next_rand"] == b["next_rand"]
-    assert abs(a["stats"][0] - b["stats"][0]) <= 0.02 * abs(b["stats"][0])
-    assert abs(a["stats"][2] - b["stats"][2]) <= 0.05 * abs(b["stats"][2]) + 1e-3
+    # Loss sums need a reference that repeats run to run.  In the host rand() order the multi-launch
+    # loop does (C4 policy-loss sum 80.3393 - 80.3411 over four runs).  In the device order its float
+    # atomics reorder the policy gradients on every run, and over C4's 1024 policy steps that grows to a
+    # 13 % spread of its own policy-loss sum (71.7 - 81.2 over four runs; the cluster phase repeats
+    # exactly, 68.81; the oracle and its two re-associations give 70.75 / 72.44 / 70.51).  There the
+    # reference is the multi-launch loop with atomic-free gradient sums (ppo_gemm_tune(·, 1)), which
+    # repeats (71.7296 three times).  The bounds are the same in both orders.
+    d = b
+    if shuffle == 1:
+        lib.ppo_gemm_tune(-1, 1)
+        try:
+            d = run(lib, sizes, N, B, 4, 10, shuffle, cluster=False)
+        finally:
+            lib.ppo_gemm_tune(-1, 0)
+        assert d["multi"] and d["t"] == b["t"] and d["next_rand"] == b["next_rand"]
+    print(f"loss sums {sizes} shuffle {shuffle}: cluster {a['stats'][0]:.4f} / {a['stats'][2]:.4f}, multi-launch "
+          f"{b['stats'][0]:.4f} / {b['stats'][2]:.4f}, reference {d['stats'][0]:.4f} / {d['stats'][2]:.4f}")
+    assert abs(a["stats"][0] - d["stats"][0]) <= 0.02 * abs(d["stats"][0])
+    assert abs(a["stats"][2] - d["stats"][2]) <= 0.05 * abs(d["stats"][2]) + 1e-3
     if sizes == C3:           # C3 stays near-deterministic (oracle self-drift cos ≥ 0.9995 at 512 steps)
         for k, k0 in (("v", "v0"), ("mu", "mu0")):
             cos, ratio = cos_ratio(a[k] - a[k0], b[k] - b[k0])
@@ -194,7 +213,14 @@ def test_cluster_full_update_matches_multilaunch(lib, oracle, shuffle, sizes):
         return
     if shuffle != 1:          # the oracle floor is measured in the device (Feistel) minibatch order
         return
-    ref = [oracle_motion(oracle, a, sizes, (-1, -1), 4, 10, mode, ent=0.01) for mode in (0, 1, 2)]
+    ref = [oracle_motion(oracle, a, sizes, (-1, -1), 4, 10, mode, ent=0.01, with_sums=True) for mode in (0, 1, 2)]
+    # the cluster phase's loss sums also against the independent reference, the oracle's update of the
+    # same buffer (both repeat run to run), at the same bounds
+    o_v, o_p = ref[0][2]
+    print(f"C4 full update loss sums: cluster {a['stats'][0]:.4f} / {a['stats'][2]:.4f}, oracle {o_v:.4f} / {o_p:.4f} "
+          f"(re-associated: {ref[1][2][1]:.4f}, {ref[2][2][1]:.4f})")
+    assert abs(a["stats"][0] - o_v) <= 0.02 * abs(o_v)
+    assert abs(a["stats"][2] - o_p) <= 0.05 * abs(o_p) + 1e-3
     for idx, k, k0 in ((0, "v", "v0"), (1, "mu", "mu0")):
         floor = [cos_ratio(ref[1][idx], ref[0][idx]), cos_ratio(ref[2][idx], ref[0][idx])]
         spread = max(abs(r - 1) for _, r in floor)

@@ -13,9 +13,9 @@ for rep in 1 2; do
     for L in A B; do
       if [ $L = A ]; then export PPO_LIB=$VAR; else unset PPO_LIB; fi
       if [ $cfg = shard8 ]; then
-        PPO_COMM_SELF=1 timeout -k 10 300 python bench.py --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/${cfg}_${L}$rep.json
+        PPO_COMM_SELF=1 timeout -k 10 300 python bench.py --full --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/${cfg}_${L}$rep.json
       else
-        timeout -k 10 300 python bench.py --config $cfg --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/${cfg}_${L}$rep.json
+        timeout -k 10 300 python bench.py --full --config $cfg --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/${cfg}_${L}$rep.json
       fi
     done
   done

@@ -8,9 +8,9 @@ cd $R
 for rep in 1 2; do
     for L in A B; do
         if [ $L = A ]; then V=0; else V=1; fi
-        env $2=$V timeout -k 10 200 python bench.py --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c4_${L}$rep.json || exit 1
-        env $2=$V PPO_COMM_SELF=1 timeout -k 10 200 python bench.py --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/shard8_${L}$rep.json || exit 1
-        env $2=$V timeout -k 10 200 python bench.py --config c3 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c3_${L}$rep.json || exit 1
+        env $2=$V timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c4_${L}$rep.json || exit 1
+        env $2=$V PPO_COMM_SELF=1 timeout -k 10 200 python bench.py --full --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/shard8_${L}$rep.json || exit 1
+        env $2=$V timeout -k 10 200 python bench.py --full --config c3 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c3_${L}$rep.json || exit 1
     done
 done
 python - "$O" <<'PY'

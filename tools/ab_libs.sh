@@ -21,9 +21,9 @@ gemms >> $O/gemm.txt
 for rep in 1 2; do
     for L in A B; do
         if [ $L = A ]; then export PPO_LIB=$VAR; else unset PPO_LIB; fi
-        PPO_COMM_SELF=1 timeout -k 10 200 python bench.py --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/shard8_${L}$rep.json
-        timeout -k 10 200 python bench.py --config c3 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c3_${L}$rep.json
-        timeout -k 10 200 python bench.py --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c4_${L}$rep.json
+        PPO_COMM_SELF=1 timeout -k 10 200 python bench.py --full --emulate-world 8 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/shard8_${L}$rep.json
+        timeout -k 10 200 python bench.py --full --config c3 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c3_${L}$rep.json
+        timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c4_${L}$rep.json
     done
 done
 unset PPO_LIB

@@ -12,7 +12,7 @@ for rep in 1 2; do
     if [ $L = A ]; then export PPO_LIB=$VAR; else unset PPO_LIB; fi
     echo "== $L$rep"
     NO_GRADW=1 timeout -k 5 120 python tools/gemm16_sweep.py --cfgs 9
-    timeout -k 10 300 python bench.py --config c5 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c5_${L}$rep.json
+    timeout -k 10 300 python bench.py --full --config c5 --no-cpu-baseline --no-rollout 2>/dev/null | tail -1 > $O/c5_${L}$rep.json
     python -c "import json; print('c5 ms', round(json.load(open('$O/c5_${L}$rep.json'))['ms_per_step'], 2))"
   done
 done
