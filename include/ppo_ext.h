@@ -104,9 +104,30 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[0]=Σ value loss, out[1]=#value steps, out[2]=Σ policy loss,
  * out[3]=#policy steps, out[4]=entropy, out[5]=advantage mean, out[6]=advantage std,
  * out[7]=rows of the last GAE's own V(next_state) forward (those not reused from V(state[t+1])),
- * out[8]=minibatch steps replayed from captured graphs (PPO_GRAPH=1) */
+ * out[8]=minibatch steps replayed from captured graphs (PPO_GRAPH=1),
+ * out[9] / out[10]=pre-clip gradient norm of the last value / policy step, out[11] / out[12]=value /
+ * policy steps whose clip coefficient was < 1 since the last reset (all four 0 while gradient
+ * clipping is off; callers passing n <= 9 see no change) */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
+
+/* Global gradient-norm clipping (off by default; not in the reference).  With max_norm > 0 and finite,
+ * every minibatch step computes on the device, after the gradient all-reduce and before its Adam,
+ *     norm = grad_scale · sqrt(Σ g²)              (grad_scale = 1/world: the norm of the mean gradient)
+ *     coef = min(1, max_norm / (norm + 1e-6))     (torch.nn.utils.clip_grad_norm_)
+ * and Adam scales the gradient by fl32(grad_scale · coef).  A value step sums over V's gradients; a
+ * policy step over μ's gradients and the log σ gradient jointly (one optimiser group: the same coef
+ * feeds the policy Adam and the entropy Adam).  The norm is deterministic (no floating-point atomics),
+ * so replicas stay bit-identical under data parallelism.  While clipping is on, ppo_update runs the
+ * multi-launch loop: the single-workgroup / cluster phases (small networks, B = 64) and graph replay do
+ * not clip and are not taken.  The setting is not part of a checkpoint (save_ppo keeps the reference's
+ * byte layout): set it again after load_ppo.
+ * max_norm <= 0 or +inf: off.  Returns 0, or −1 for NaN (setting unchanged). */
+int    ppo_set_max_grad_norm(void* ppo, float max_norm);
+float  ppo_get_max_grad_norm(void* ppo);                  /* 0 when off */
+/* L2 norm of a device span plus an optional second span (d_b may be NULL with nb = 0), by the update's
+ * own norm kernel; synchronises */
+double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

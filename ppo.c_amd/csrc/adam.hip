@@ -24,6 +24,12 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
     p -= step * m / denom;
 }
 
+// the step's gradient scale: grad_scale, times the device clip coefficient when clipping is on
+// (clip.hip wrote it in the launch before this one); coef == nullptr leaves g · scale as it was
+__device__ __forceinline__ float clip_scale(float scale, const float* __restrict__ coef) {
+    return coef ? scale * *coef : scale;
+}
+
 // n elements: float4 body plus a scalar tail (a network's span ends with its unpadded output bias).
 // w16 (bf16 mode): the parameters' bf16 shadow for the first n16 elements, written in the same pass.
 // zero_g: the gradient is cleared once read (ppo_update: the next backward's split-K atomics then
@@ -67,8 +73,9 @@ __device__ __forceinline__ void adam_vec_body(float* __restrict__ p, float* __re
 
 __global__ void adam_flat_vec_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                      float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
-                                     float scale, __bf16* __restrict__ w16, long n16, int zero_g) {
-    adam_vec_body(p, g, m, v, n, step, b1, b2, bc2, scale, w16, n16, zero_g);
+                                     float scale, __bf16* __restrict__ w16, long n16, int zero_g,
+                                     const float* __restrict__ coef) {
+    adam_vec_body(p, g, m, v, n, step, b1, b2, bc2, clip_scale(scale, coef), w16, n16, zero_g);
 }
 
 // a second, small flat span in the same launch (the policy step's entropy Adam beside the network's,
@@ -78,7 +85,13 @@ struct SideSpan {
 };
 __global__ void adam_flat_vec_pair_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
-                                          float scale, __bf16* __restrict__ w16, long n16, int zero_g, SideSpan s) {
+                                          float scale, __bf16* __restrict__ w16, long n16, int zero_g, SideSpan s,
+                                          const float* __restrict__ coef) {
+    if (coef) {                                    // one clip coefficient for both spans (one optimiser group)
+        const float c = *coef;
+        scale = scale * c;
+        s.scale = s.scale * c;
+    }
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x < s.n) {
         const int j = threadIdx.x;
         float pp = s.p[j], mm = s.m[j], vv = s.v[j];
@@ -141,7 +154,8 @@ __global__ void adam_flat_tab_kernel(float* __restrict__ p, float* __restrict__ 
 
 __global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
-                                 float scale) {
+                                 float scale, const float* __restrict__ coef) {
+    scale = clip_scale(scale, coef);
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
         float pp = p[i], mm = m[i], vv = v[i];
         adam_elem(pp, g[i], mm, vv, step, b1, b2, bc2, scale);
@@ -183,7 +197,7 @@ extern "C" {
 
 void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                         float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g) {
+                        long n16, int zero_g, const float* coef) {
     if (n <= 0) return;
     const float step = lr / bias_correction1;
     ppo::ProfScope ps(PPO_K_ADAM, 28.0 * n + (w16 ? 2.0 * n16 : 0.0) + (zero_g ? 4.0 * n : 0.0));
@@ -192,11 +206,11 @@ void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr
     if (vec) {
         hipLaunchKernelGGL(adam_flat_vec_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
                            v, n, step, beta1, beta2, bias_correction2, grad_scale,
-                           reinterpret_cast<__bf16*>(w16), n16, zero_g);
+                           reinterpret_cast<__bf16*>(w16), n16, zero_g, coef);
     } else {
         PPO_REQUIRE(!w16 && !zero_g, "phip_adam_flat_w16: unaligned span with a bf16 shadow or gradient clear");
         hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n)), dim3(TPB), 0, ppo::stream(), p, g, m, v, n, step,
-                           beta1, beta2, bias_correction2, grad_scale);
+                           beta1, beta2, bias_correction2, grad_scale, coef);
     }
     PPO_LAUNCH_CHECK();
 }
@@ -204,7 +218,8 @@ void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr
 void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                          float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
                          long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
-                         float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2) {
+                         float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
+                         const float* coef) {
     PPO_REQUIRE(n > 0 && n2 >= 0 && n2 <= TPB, "phip_adam_flat_pair: spans");
     PPO_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0 && ((uintptr_t)w16 & 7u) == 0,
                 "phip_adam_flat_pair: the network span must be 16-B aligned");
@@ -212,7 +227,7 @@ void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float l
     SideSpan s{p2, g2, m2, v2, n2, lr2 / bias_correction1_2, bias_correction2_2, grad_scale2, zero_g2};
     hipLaunchKernelGGL(adam_flat_vec_pair_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
                        v, n, lr / bias_correction1, beta1, beta2, bias_correction2, grad_scale,
-                       reinterpret_cast<__bf16*>(w16), n16, zero_g, s);
+                       reinterpret_cast<__bf16*>(w16), n16, zero_g, s, coef);
     PPO_LAUNCH_CHECK();
 }
 
@@ -230,7 +245,7 @@ void phip_adam_flat_tab(float* p, float* g, float* m, float* v, long n, const Ph
 void phip_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float bias_correction1, float bias_correction2, float grad_scale) {
     phip_adam_flat_w16(p, const_cast<float*>(g), m, v, n, lr, beta1, beta2, bias_correction1, bias_correction2,
-                       grad_scale, nullptr, 0, 0);
+                       grad_scale, nullptr, 0, 0, nullptr);
 }
 
 void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,

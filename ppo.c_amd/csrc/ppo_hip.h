@@ -268,19 +268,40 @@ void phip_graph_destroy(void* exec);
 const char* phip_graph_error(void);         /* why the last capture failed (warning text) */
 int  phip_capturing(void);                   /* 1 while a capture is open (profiling scopes stay out) */
 
+/* coef (both kernels below; NULL: off, the arithmetic is g · grad_scale as before): the device clip
+ * coefficient of this step (clip.hip, PhipClipRec.coef) — the gradient is scaled by fl32(grad_scale · *coef) */
 void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                         float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g);
+                        long n16, int zero_g, const float* coef);
 /* the same for a network span (16-B aligned) plus a small second span (≤ 256 floats, any alignment:
  * the policy step's entropy Adam) with its own step size, in one launch */
 void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                          float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
                          long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
-                         float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2);
+                         float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
+                         const float* coef);
 /* multi-tensor: ptrs/lengths are HOST arrays describing device tensors; m/v are flat */
 void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors,
                      float* m, float* v, float lr, float beta1, float beta2,
                      float bias_correction1, float bias_correction2, float grad_scale);
+
+/* ---------------- global gradient-norm clipping (clip.hip) ---------------- */
+#define PHIP_CLIP_PARTS 256
+/* one per loop (the value and policy loops run concurrently): the result, the ticket and the
+ * per-workgroup partials of the norm kernel.  Zero-initialised (phip_malloc); the kernel leaves the
+ * ticket at zero again. */
+typedef struct {
+    double norm;                    /* grad_scale · sqrt(Σ g²) of the last launch (before clipping) */
+    float coef;                     /* min(1, max_norm / (norm + 1e-6)) */
+    unsigned clipped;               /* launches with coef < 1 since the record was cleared */
+    unsigned ticket;
+    unsigned pad;
+    double partial[PHIP_CLIP_PARTS];
+} PhipClipRec;
+/* norm and coef of g[0, n) plus side[0, n_side) (n_side may be 0) into rec; one launch, deterministic
+ * (no floating-point atomics, grid a function of n), no host read */
+void phip_grad_norm(const float* g, long n, const float* side, long n_side, float grad_scale, float max_norm,
+                    PhipClipRec* rec);
 
 /* ---------------- sampling / synthetic data (sample.hip) ---------------- */
 void phip_sample(const float* mu, const float* log_std, float* action, float* logprob, int m, int A,

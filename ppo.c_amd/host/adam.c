@@ -163,12 +163,14 @@ void free_adam_cuda(Adam* adam) {
     free(adam);
 }
 
-void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NULL, 0, 0); }
+void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NULL, 0, 0, NULL); }
 
 /* w16 != NULL: also refresh the bf16 shadow of the first n16 parameters (flat spans only).
  * zero_g: clear the gradient span once read (flat spans only).  Returns bit 0: shadow refreshed,
- * bit 1: gradients cleared. */
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g) {
+ * bit 1: gradients cleared.  coef != NULL (flat spans only): the step's device clip coefficient
+ * (PhipClipRec.coef), multiplied into the gradient scale by the kernel. */
+int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef) {
+    if (coef && !adam->flat) die("adam_update_cuda_w16: gradient clipping needs a flat Adam span");
     float bc1, bc2;
     bias_corrections(adam, &bc1, &bc2);
     nn_note_device_update(adam->weights[0]);          /* the network's host mirrors are now stale */
@@ -178,7 +180,7 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
                              (uintptr_t)adam->v;
         if (al & 15u) zero_g = 0;
         phip_adam_flat_w16(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                           adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g);
+                           adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef);
         return (w16 != NULL) | (zero_g ? 2 : 0);
     } else {
         phip_adam_multi(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v, lr,
@@ -190,9 +192,10 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
 /* a network's flat Adam (16-B aligned span) and a small flat side Adam (the entropy Adam's log σ) in
  * one launch; the side's step runs first in the step counters (ppo.cu:440-442 order; the spans are
  * independent).  Returns bit 0: shadow refreshed, bit 1: network gradients cleared, bit 2: side
- * gradients cleared; −1 (nothing done) when the pair does not qualify. */
+ * gradients cleared; −1 (nothing done) when the pair does not qualify.  coef as in adam_update_cuda_w16:
+ * one coefficient for both spans. */
 int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side) {
+                         int zero_side, const float* coef) {
     const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
                          (uintptr_t)adam->v;
     if (!adam->flat || !side->flat || (al & 15u) || side->span > 256 || side->span < 1 || adam->span < 1 ||
@@ -206,7 +209,7 @@ int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
     phip_adam_flat_pair(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
                         adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, side->weights[0],
                         side->grad_weights[0], side->m, side->v, (int)side->span, lr_side, bc1s, bc2s,
-                        side->grad_scale, zero_side);
+                        side->grad_scale, zero_side, coef);
     return (w16 != NULL) | (zero_g ? 2 : 0) | (zero_side ? 4 : 0);
 }
 

@@ -53,6 +53,11 @@ typedef struct {
     int* ph_rows[2];
     float *ph_tgt, *ph_act, *ph_olp, *ph_adv;
     long ph_cap[2];
+    /* global gradient-norm clipping (ppo_set_max_grad_norm; 0 = off): each loop's own device record
+     * (norm, coefficient, clipped-step counter, the norm kernel's ticket and partials) — the value and
+     * policy loops run concurrently, so they share nothing here */
+    float max_grad_norm;
+    PhipClipRec* clip[2];
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -102,6 +107,8 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d = (PPODev*)xcalloc(1, sizeof(PPODev));
         d->stats = (float*)phip_malloc(4 * sizeof(float));
         d->max_v = d->max_p = -1;
+        d->clip[0] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
+        d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         ppo->dev = d;
     }
     if (B > d->cap_B) {
@@ -136,6 +143,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->tab[0]); phip_free(d->tab[1]); phip_free(d->ctr);
     phip_free(d->ph_rows[0]); phip_free(d->ph_rows[1]); phip_free(d->ph_tgt); phip_free(d->ph_act);
     phip_free(d->ph_olp); phip_free(d->ph_adv);
+    phip_free(d->clip[0]); phip_free(d->clip[1]);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -359,11 +367,12 @@ static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
 
 /* Adam step of a network's flat span; in bf16 mode the same pass refreshes the bf16 parameter
  * shadow when the span starts at the network's parameters, else a separate conversion does.
- * zero_grads: the same pass clears the gradients it read (the next backward skips its memset) */
-static int adam_update_net(Adam* adam, float lr, NeuralNetwork* nn, int zero_grads) {
+ * zero_grads: the same pass clears the gradients it read (the next backward skips its memset);
+ * coef: NULL, or the step's device clip coefficient */
+static int adam_update_net(Adam* adam, float lr, NeuralNetwork* nn, int zero_grads, const float* coef) {
     const int own = adam->flat && adam->weights[0] == nn->d_params && adam->grad_weights[0] == nn->d_grads;
     const int fused = nn->dtype == 1 && own;
-    const int r = adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own);
+    const int r = adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own, coef);
     if (!(r & 1) && nn->dtype == 1) nn_sync_w16(nn);
     return (r & 2) != 0;                 /* the network's gradients are zero again */
 }
@@ -429,6 +438,9 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int 
     const int limit = buf->full ? buf->capacity : buf->idx;
     const int num_batches = buf->capacity / B;
     if (getenv("PPO_NO_TINY") || phip_comm_world() > 1 || n_epochs_value > 16 || n_epochs_policy > 16) return -1;
+    /* the single-workgroup and cluster kernels run their Adam steps inside the launch and do not clip:
+     * with gradient clipping on, the update takes the multi-launch loop */
+    if (d->max_grad_norm > 0.f) return -1;
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -523,6 +535,18 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int 
 /* ------------------------------------------------------------------ */
 /* one value / policy minibatch step (ppo.cu:395-443 bodies)           */
 /* ------------------------------------------------------------------ */
+/* gradient clipping (off: NULL, nothing launched): the global L2 norm of the loop's summed gradient
+ * — the Adam's flat span plus `side` (the policy's log σ gradient) — and the clip coefficient, on the
+ * device (clip.hip), after the all-reduce has joined and before the step's Adam, which reads the
+ * coefficient through the returned pointer.  Under data parallelism the buffer holds the sum over ranks
+ * and every rank computes the same bits from it, so the replicas stay identical. */
+static const float* clip_coef(PPODev* d, int ph, Adam* adam, const float* side, int n_side) {
+    if (!(d->max_grad_norm > 0.f)) return NULL;
+    if (!adam->flat) die("ppo_update: gradient clipping needs flat Adam spans");
+    phip_grad_norm(adam->grad_weights[0], adam->span, side, n_side, adam->grad_scale, d->max_grad_norm, d->clip[ph]);
+    return &d->clip[ph]->coef;
+}
+
 typedef struct {
     PPO* ppo;
     PPODev* d;
@@ -579,7 +603,8 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
         adam_net_tab(ppo->adam_V, V, d, 0, 0);
         return 1;
     }
-    return adam_update_net(ppo->adam_V, ppo->lr_V, V, iv + 1 < c->nv);
+    return adam_update_net(ppo->adam_V, ppo->lr_V, V, iv + 1 < c->nv,
+                           clip_coef(d, 0, ppo->adam_V, NULL, 0));
 }
 
 static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab) {
@@ -634,20 +659,23 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     }
     /* both Adams in one launch where they qualify (flat spans, the network's 16-B aligned) */
     Adam* ap = ppo->adam_policy;
+    /* μ's gradient span and the log σ gradient clip as one group: one coefficient for both Adams */
+    const float* coef = clip_coef(d, 1, ap, pol->d_log_std_grad, A);
     const int own = ap->flat && ap->weights[0] == mu->d_params && ap->grad_weights[0] == mu->d_grads;
     const int fused = mu->dtype == 1 && own;
     const int ls_own = ppo->adam_entropy->flat && ppo->adam_entropy->grad_weights[0] == pol->d_log_std_grad;
     const int r = adam_update_pair_w16(ap, ppo->lr_policy, fused ? mu->d_w16 : NULL, mu->num_params,
                                          ip + 1 < c->np && own, ppo->adam_entropy, ppo->lr_policy,
-                                         ip + 1 < c->np && ls_own);
+                                         ip + 1 < c->np && ls_own, coef);
     if (r >= 0) {
         if (!(r & 1) && mu->dtype == 1) nn_sync_w16(mu);
         *ls_zero = ls_own && (r & 4);
         *p_zero = (r & 2) != 0;
         return;
     }
-    *ls_zero = ls_own && (adam_update_cuda_w16(ppo->adam_entropy, ppo->lr_policy, NULL, 0, ip + 1 < c->np) & 2);
-    *p_zero = adam_update_net(ppo->adam_policy, ppo->lr_policy, mu, ip + 1 < c->np);
+    *ls_zero = ls_own &&
+               (adam_update_cuda_w16(ppo->adam_entropy, ppo->lr_policy, NULL, 0, ip + 1 < c->np, coef) & 2);
+    *p_zero = adam_update_net(ppo->adam_policy, ppo->lr_policy, mu, ip + 1 < c->np, coef);
 }
 
 /* graph replay (opt-in, PPO_GRAPH=1; PPO_GRAPH_STEPS = steps per captured graph, default 16) for
@@ -659,6 +687,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
 static int step_graphs_ok(const StepCtx* c) {
     const char* e = getenv("PPO_GRAPH");
     if (!(e && *e && *e != '0') || c->comm || phip_comm_world() > 1 || c->B > 2048 || c->A > 32) return 0;
+    if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
     for (int i = 0; i < 3; i++) {
@@ -966,6 +995,8 @@ void ppo_reset_stats(void* vppo) {
     PPO* ppo = (PPO*)vppo;
     PPODev* d = dev_ws(ppo, 1);
     phip_memset(d->stats, 0, 4 * sizeof(float));
+    /* norm, coef and the clipped-step counter (the 16 bytes ahead of the ticket) */
+    for (int i = 0; i < 2; i++) phip_memset(d->clip[i], 0, offsetof(PhipClipRec, ticket));
     d->n_v = d->n_p = d->n_graph = 0;
 }
 
@@ -975,9 +1006,42 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[9] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                   (double)g_gae_own_rows, (double)d->n_graph};
-    for (int i = 0; i < n && i < 9; i++) out[i] = v[i];
+    double v[13] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0};
+    if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
+        for (int i = 0; i < 2; i++) {
+            PhipClipRec r;
+            phip_d2h(&r, d->clip[i], offsetof(PhipClipRec, partial));
+            v[9 + i] = r.norm;
+            v[11 + i] = (double)r.clipped;
+        }
+    }
+    for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
+}
+
+/* ppo_ext.h: global gradient-norm clipping */
+int ppo_set_max_grad_norm(void* vppo, float max_norm) {
+    if (isnan(max_norm)) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    d->max_grad_norm = (max_norm > 0.f && !isinf(max_norm)) ? max_norm : 0.f;
+    return 0;
+}
+
+float ppo_get_max_grad_norm(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo->dev ? ((PPODev*)ppo->dev)->max_grad_norm : 0.f;
+}
+
+double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb) {
+    static PhipClipRec* rec = NULL;
+    if (!rec) rec = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
+    if (na < 0) na = 0;
+    if (nb < 0) nb = 0;
+    phip_memset(rec, 0, offsetof(PhipClipRec, partial));
+    phip_grad_norm(d_a, na, d_b, nb, 1.0f, INFINITY, rec);
+    double norm = 0.0;
+    phip_d2h(&norm, &rec->norm, sizeof(double));
+    return norm;
 }
 
 /* ppo.cu:451-558 */

@@ -150,6 +150,9 @@ _SIGS = {
     "ppo_read_stats": (None, [_P, C.POINTER(C.c_double), C.c_int]),
     "ppo_reset_stats": (None, [_P]),
     "ppo_set_step_limit": (None, [_P, C.c_long, C.c_long]),
+    "ppo_set_max_grad_norm": (C.c_int, [_P, C.c_float]),
+    "ppo_get_max_grad_norm": (C.c_float, [_P]),
+    "ppo_grad_norm_device": (C.c_double, [_P, C.c_long, _P, C.c_long]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
