@@ -96,7 +96,9 @@ enum { PPO_SHUFFLE_HOST_RAND = 0,   /* reference shuffle_buffer: swap(i, rand()%
  * all-reduced (mean over the global minibatch) and advantage statistics are
  * global.  Asynchronous: nothing is read back to the host — except after the multi-workgroup
  * B = 64 phases (cluster.hip), which synchronise once at the end to check their grid barriers
- * (a timeout ends the process with status 1: the phase's state is incomplete). */
+ * (a timeout ends the process with status 1: the phase's state is incomplete), and, only while
+ * target-KL early stopping is on (ppo_set_target_kl), after the last step of each policy epoch, where the
+ * host waits for the policy loop's stream and reads 40 bytes to stop issuing steps the device skips. */
 void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int n_epochs_value,
                 int shuffle_mode, unsigned long long seed);
 
@@ -107,7 +109,10 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[8]=minibatch steps replayed from captured graphs (PPO_GRAPH=1),
  * out[9] / out[10]=pre-clip gradient norm of the last value / policy step, out[11] / out[12]=value /
  * policy steps whose clip coefficient was < 1 since the last reset (all four 0 while gradient
- * clipping is off; callers passing n <= 9 see no change) */
+ * clipping is off; callers passing n <= 9 see no change),
+ * out[13]=approximate KL of the last decided policy step, out[14]=its clip fraction, out[15]=policy steps
+ * whose Adam ran since the last reset, out[16]=stop step of the last update (−1: none) (all four 0 while
+ * target-KL early stopping is off; callers passing n <= 13 see no change) */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
 
@@ -128,6 +133,35 @@ float  ppo_get_max_grad_norm(void* ppo);                  /* 0 when off */
 /* L2 norm of a device span plus an optional second span (d_b may be NULL with nb = 0), by the update's
  * own norm kernel; synchronises */
 double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb);
+
+/* Target-KL early stopping (off by default; not in the reference).  While it is on, every policy minibatch
+ * step measures on the device, after its forward and before its Adam, with x = log-prob − old log-prob of
+ * the minibatch's rows (the log-prob by the loss's own expression),
+ *     kl        = mean(expm1(x) − x)               (in double; Schulman's k3 estimator of KL(old ‖ new))
+ *     clip_frac = mean(|exp(x) − 1| > epsilon)
+ * and stops the policy loop of this update once kl > 1.5 · target_kl (Stable-Baselines3, CleanRL,
+ * Spinning Up): the step that tripped it and every later policy step of the update take no Adam step (μ,
+ * log σ and both Adams' moments stay; the gradients are still cleared).  A NaN kl never stops.  The value
+ * loop is untouched.  The decision is taken on the device, per step; ppo_update synchronises the policy
+ * loop's stream after the last step of each policy epoch — only while this feature is on — to stop
+ * issuing steps that would be no-ops, and sets the policy and entropy Adams' time_step back by the skipped
+ * steps, so they count the steps that were applied.  The sums are deterministic (no floating-point
+ * atomics).  Under data parallelism the two sums are all-reduced (one extra 16-byte collective per policy
+ * step behind the gradient's, same stream and communicator) and kl is the mean over the global minibatch:
+ * EVERY RANK MUST HOLD THE SAME target_kl SETTING, or the ranks issue different sequences of collectives.
+ * While it is on, ppo_update runs the multi-launch loop (no single-workgroup / cluster phases, no graph
+ * replay), as with gradient clipping, and works together with it.  Not part of a checkpoint: set it again
+ * after load_ppo.
+ * target_kl > 0: on; +inf: measure only, never stop; <= 0: off.  Returns 0, or −1 for NaN (unchanged). */
+int    ppo_set_target_kl(void* ppo, float target_kl);
+float  ppo_get_target_kl(void* ppo);                      /* 0 when off */
+/* KL of every decided policy step of the last ppo_update, in step order, into out[0, min(n, steps, 4096));
+ * returns the number of decided steps (0 while the feature is off); synchronises */
+int    ppo_kl_history(void* ppo, double* out, int n);
+/* the update's KL kernel on caller-supplied device arrays: μ [m, A], log σ [A], action [m, A], old log-prob
+ * [m] → out2 = {approximate KL, clip fraction}; returns 0, −1 for bad arguments; synchronises */
+int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
+                            int m, int A, float eps, double* out2);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

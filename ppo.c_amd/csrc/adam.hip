@@ -71,10 +71,26 @@ __device__ __forceinline__ void adam_vec_body(float* __restrict__ p, float* __re
     }
 }
 
+// target-KL early stopping (kl.hip wrote the stop word in a launch before this one): the step is not taken —
+// p, m, v and the bf16 shadow stay as they are — but the gradient is still cleared where the step would have
+// cleared it, since the next backward accumulates into it.  skip == nullptr: off.
+__device__ __forceinline__ bool step_skipped(const unsigned* __restrict__ skip) { return skip && *skip != 0u; }
+
+__device__ __forceinline__ void clear_vec_body(float* __restrict__ g, long n) {
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n4; i += (long)gridDim.x * TPB)
+        reinterpret_cast<float4*>(g)[i] = float4{0.f, 0.f, 0.f, 0.f};
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) g[4 * n4 + threadIdx.x] = 0.f;
+}
+
 __global__ void adam_flat_vec_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                      float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
                                      float scale, __bf16* __restrict__ w16, long n16, int zero_g,
-                                     const float* __restrict__ coef) {
+                                     const float* __restrict__ coef, const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) {
+        if (zero_g) clear_vec_body(g, n);
+        return;
+    }
     adam_vec_body(p, g, m, v, n, step, b1, b2, bc2, clip_scale(scale, coef), w16, n16, zero_g);
 }
 
@@ -86,7 +102,12 @@ struct SideSpan {
 __global__ void adam_flat_vec_pair_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
                                           float scale, __bf16* __restrict__ w16, long n16, int zero_g, SideSpan s,
-                                          const float* __restrict__ coef) {
+                                          const float* __restrict__ coef, const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) {                      // neither span steps; both gradients cleared as asked
+        if (s.zero_g && blockIdx.x == gridDim.x - 1 && threadIdx.x < s.n) s.g[threadIdx.x] = 0.f;
+        if (zero_g) clear_vec_body(g, n);
+        return;
+    }
     if (coef) {                                    // one clip coefficient for both spans (one optimiser group)
         const float c = *coef;
         scale = scale * c;
@@ -154,7 +175,8 @@ __global__ void adam_flat_tab_kernel(float* __restrict__ p, float* __restrict__ 
 
 __global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
-                                 float scale, const float* __restrict__ coef) {
+                                 float scale, const float* __restrict__ coef, const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) return;
     scale = clip_scale(scale, coef);
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
         float pp = p[i], mm = m[i], vv = v[i];
@@ -197,7 +219,7 @@ extern "C" {
 
 void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                         float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g, const float* coef) {
+                        long n16, int zero_g, const float* coef, const unsigned* skip) {
     if (n <= 0) return;
     const float step = lr / bias_correction1;
     ppo::ProfScope ps(PPO_K_ADAM, 28.0 * n + (w16 ? 2.0 * n16 : 0.0) + (zero_g ? 4.0 * n : 0.0));
@@ -206,11 +228,11 @@ void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr
     if (vec) {
         hipLaunchKernelGGL(adam_flat_vec_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
                            v, n, step, beta1, beta2, bias_correction2, grad_scale,
-                           reinterpret_cast<__bf16*>(w16), n16, zero_g, coef);
+                           reinterpret_cast<__bf16*>(w16), n16, zero_g, coef, skip);
     } else {
         PPO_REQUIRE(!w16 && !zero_g, "phip_adam_flat_w16: unaligned span with a bf16 shadow or gradient clear");
         hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n)), dim3(TPB), 0, ppo::stream(), p, g, m, v, n, step,
-                           beta1, beta2, bias_correction2, grad_scale, coef);
+                           beta1, beta2, bias_correction2, grad_scale, coef, skip);
     }
     PPO_LAUNCH_CHECK();
 }
@@ -219,7 +241,7 @@ void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float l
                          float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
                          long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
                          float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
-                         const float* coef) {
+                         const float* coef, const unsigned* skip) {
     PPO_REQUIRE(n > 0 && n2 >= 0 && n2 <= TPB, "phip_adam_flat_pair: spans");
     PPO_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0 && ((uintptr_t)w16 & 7u) == 0,
                 "phip_adam_flat_pair: the network span must be 16-B aligned");
@@ -227,7 +249,7 @@ void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float l
     SideSpan s{p2, g2, m2, v2, n2, lr2 / bias_correction1_2, bias_correction2_2, grad_scale2, zero_g2};
     hipLaunchKernelGGL(adam_flat_vec_pair_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
                        v, n, lr / bias_correction1, beta1, beta2, bias_correction2, grad_scale,
-                       reinterpret_cast<__bf16*>(w16), n16, zero_g, s, coef);
+                       reinterpret_cast<__bf16*>(w16), n16, zero_g, s, coef, skip);
     PPO_LAUNCH_CHECK();
 }
 
@@ -245,7 +267,7 @@ void phip_adam_flat_tab(float* p, float* g, float* m, float* v, long n, const Ph
 void phip_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float bias_correction1, float bias_correction2, float grad_scale) {
     phip_adam_flat_w16(p, const_cast<float*>(g), m, v, n, lr, beta1, beta2, bias_correction1, bias_correction2,
-                       grad_scale, nullptr, 0, 0, nullptr);
+                       grad_scale, nullptr, 0, 0, nullptr, nullptr);
 }
 
 void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,

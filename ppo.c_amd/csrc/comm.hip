@@ -21,7 +21,9 @@
 //  * each communicator's collectives are issued from ONE stream in program order, and the host
 //    interleaves the two loops by a fixed rule (iv·np ≤ ip·nv, host/ppo.c) that does not depend on
 //    timing, so every rank submits the same total order of collectives — also the order a shared
-//    hardware queue would serialise them in;
+//    hardware queue would serialise them in (target-KL early stopping adds one 16-byte all-reduce per
+//    policy step behind the gradient's: a function of the setting, which every rank must share, and of
+//    all-reduced sums, never of timing);
 //  * every communicator is created with ncclConfig_t.maxCTAs = kMaxCTAs (32; PPO_COMM_MAX_CTAS), so
 //    the two collectives that can be in flight at once need ≤ 64 workgroups of 256 CUs: once the
 //    finite kernels beside them drain, both are resident, whatever else is queued.

@@ -1,0 +1,155 @@
+// kl.hip — approximate KL and clip fraction of a policy minibatch step, and the target-KL stop decision,
+// on the device (no counterpart in the reference).
+//
+// One launch per policy minibatch step, after the step's forward has left μ in HBM and before its Adam:
+//   lp_i  = Gaussian log-prob of action_i under (μ_i, log σ)           (kernels.hip log_prob_row's expression)
+//   x_i   = (double)lp_i − (double)old_lp_i
+//   kl    = Σ (expm1(x_i) − x_i) / rows          (Schulman's k3 estimator; double: (r − 1) − log r cancels in fp32)
+//   frac  = Σ 1[|(float)exp(x_i) − 1| > ε] / rows
+//   if (!stopped && kl > 1.5f · target_kl) { stopped = 1; stop_step = step; }      (Stable-Baselines3's rule)
+// left in a device record; the step's Adam reads `stopped` through a pointer (adam.hip) and takes no step once
+// it is set.  The host never reads the record inside an epoch.
+//
+// Deterministic by construction, as clip.hip: the grid is a function of m only, every thread sums its
+// grid-stride rows in index order in double, a workgroup folds its 256 sums by a fixed LDS tree, and the last
+// workgroup to arrive folds the ≤ 256 workgroup partials by the same tree — no floating-point atomic.  The
+// hand-off is clip.hip's ticket form: each workgroup's two 8-byte partials are stored write-through at agent
+// scope and drained before its ticket add; the last arriver acquires once and reads the partials with
+// agent-scope loads.
+//
+// Without a communicator the last arriver takes the decision itself (one launch per step).  With one, it only
+// writes the local sums; the caller all-reduces those four floats and kl_decide_kernel decides from the global
+// sums, so every rank takes the same decision from the same bits.
+#include "dev.h"
+
+namespace {
+
+constexpr int TPB = 256;
+
+__device__ __forceinline__ double block_sum(double v, double* s) {
+    s[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = TPB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = s[0];
+    __syncthreads();
+    return r;
+}
+
+// policy.cu:67-74 with the reference's double temporaries — kernels.hip log_prob_row, so the ratio is the one
+// the loss saw
+__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
+    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
+    float lp = c;
+    for (int j = 0; j < A; ++j) {
+        const float z = (a[j] - mu[j]) / expf(log_std[j]);
+        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
+    }
+    return lp;
+}
+
+// one thread, from rec->sums (local, or all-reduced over the ranks): the step's statistics and the decision
+__device__ __forceinline__ void decide(PhipKlRec* rec, float target_kl, double rows_global) {
+    const float kl = (float)((double)rec->sums[0] / rows_global);
+    rec->kl = kl;
+    rec->clip_frac = (float)((double)rec->sums[1] / rows_global);
+    unsigned stopped = rec->stopped;
+    const unsigned step = rec->step;
+    if (!stopped && kl > 1.5f * target_kl) {          // NaN compares false: never stops
+        stopped = 1u;
+        rec->stopped = 1u;
+        rec->stop_step = (int)step;
+    }
+    if (step < (unsigned)PHIP_KL_HIST) rec->hist[step] = kl;
+    rec->step = step + 1u;
+    rec->applied += stopped ? 0u : 1u;
+}
+
+__global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
+                                                     const float* __restrict__ action,
+                                                     const float* __restrict__ old_lp, int m, int A, float eps,
+                                                     float target_kl, double rows_global, int decide_here,
+                                                     PhipKlRec* rec) {
+    __shared__ double s[TPB + 1];             // s[TPB]: "this workgroup drew the last ticket"
+    double kl = 0.0, cnt = 0.0;
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < m; i += (long)gridDim.x * TPB) {
+        const float lp = log_prob_row(mu + i * A, log_std, action + i * A, A);
+        const double x = (double)lp - (double)old_lp[i];
+        kl += expm1(x) - x;
+        cnt += fabsf((float)exp(x) - 1.0f) > eps ? 1.0 : 0.0;
+    }
+    const double part_kl = block_sum(kl, s);
+    const double part_cnt = block_sum(cnt, s);
+
+    if (threadIdx.x == 0) {
+        unsigned long long* slot = reinterpret_cast<unsigned long long*>(&rec->partial[2 * blockIdx.x]);
+        __hip_atomic_store(slot, (unsigned long long)__double_as_longlong(part_kl), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(slot + 1, (unsigned long long)__double_as_longlong(part_cnt), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the write-through stores have left this CU
+        const unsigned t = __hip_atomic_fetch_add(&rec->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = t == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        s[TPB] = last ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    if (s[TPB] == 0.0) return;                // uniform over the workgroup
+
+    // the last workgroup: every partial of this launch is visible; fold them in index order
+    double pk = 0.0, pc = 0.0;
+    if (threadIdx.x < gridDim.x) {
+        const unsigned long long* slot = reinterpret_cast<const unsigned long long*>(&rec->partial[2 * threadIdx.x]);
+        pk = __longlong_as_double((long long)__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        pc = __longlong_as_double((long long)__hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    }
+    const double tk = block_sum(pk, s);
+    const double tc = block_sum(pc, s);
+    if (threadIdx.x == 0) {
+        rec->sums[0] = (float)tk;
+        rec->sums[1] = (float)tc;
+        rec->sums[2] = 0.f;
+        rec->sums[3] = 0.f;
+        if (decide_here) decide(rec, target_kl, rows_global);
+        __hip_atomic_store(&rec->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the next launch's
+    }
+}
+
+__global__ void kl_decide_kernel(PhipKlRec* rec, float target_kl, double rows_global) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) decide(rec, target_kl, rows_global);
+}
+
+int grid_for(int m) {
+    long g = ((long)m + TPB - 1) / TPB;
+    if (g < 1) g = 1;
+    if (g > PHIP_KL_PARTS) g = PHIP_KL_PARTS;
+    return (int)g;
+}
+
+}  // namespace
+
+extern "C" {
+
+void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
+                    float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec) {
+    static_assert(PHIP_KL_PARTS <= TPB, "the last workgroup folds one pair of partials per thread");
+    PPO_REQUIRE(m > 0 && A > 0 && rows_global > 0 && rec, "phip_policy_kl: shape");
+    ppo::ProfScope ps(PPO_K_ADAM, 8.0 * (double)m * A + 4.0 * m);
+    hipLaunchKernelGGL(kl_sum_kernel, dim3(grid_for(m)), dim3(TPB), 0, ppo::stream(), mu, log_std, action, old_lp, m,
+                       A, eps, target_kl, (double)rows_global, decide_here, rec);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global) {
+    PPO_REQUIRE(rows_global > 0 && rec, "phip_kl_decide: shape");
+    ppo::ProfScope ps(PPO_K_ADAM, 64.0);
+    hipLaunchKernelGGL(kl_decide_kernel, dim3(1), dim3(64), 0, ppo::stream(), rec, target_kl, (double)rows_global);
+    PPO_LAUNCH_CHECK();
+}
+
+}  // extern "C"

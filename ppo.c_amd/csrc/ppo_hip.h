@@ -269,17 +269,20 @@ const char* phip_graph_error(void);         /* why the last capture failed (warn
 int  phip_capturing(void);                   /* 1 while a capture is open (profiling scopes stay out) */
 
 /* coef (both kernels below; NULL: off, the arithmetic is g · grad_scale as before): the device clip
- * coefficient of this step (clip.hip, PhipClipRec.coef) — the gradient is scaled by fl32(grad_scale · *coef) */
+ * coefficient of this step (clip.hip, PhipClipRec.coef) — the gradient is scaled by fl32(grad_scale · *coef).
+ * skip (both kernels; NULL: off, arithmetic and launch shape as before): the device stop word of target-KL
+ * early stopping (kl.hip, PhipKlRec.stopped) — while *skip != 0 the step is not taken: p, m, v and w16 stay
+ * untouched (both spans of the pair kernel), the gradients are still cleared where zero_g / zero_g2 ask */
 void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                         float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g, const float* coef);
+                        long n16, int zero_g, const float* coef, const unsigned* skip);
 /* the same for a network span (16-B aligned) plus a small second span (≤ 256 floats, any alignment:
  * the policy step's entropy Adam) with its own step size, in one launch */
 void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                          float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
                          long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
                          float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
-                         const float* coef);
+                         const float* coef, const unsigned* skip);
 /* multi-tensor: ptrs/lengths are HOST arrays describing device tensors; m/v are flat */
 void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors,
                      float* m, float* v, float lr, float beta1, float beta2,
@@ -302,6 +305,37 @@ typedef struct {
  * (no floating-point atomics, grid a function of n), no host read */
 void phip_grad_norm(const float* g, long n, const float* side, long n_side, float grad_scale, float max_norm,
                     PhipClipRec* rec);
+
+/* ---------------- target-KL early stopping (kl.hip) ---------------- */
+#define PHIP_KL_PARTS 256
+#define PHIP_KL_HIST 4096
+/* the policy loop's record: zero-initialised (phip_malloc); the sum kernel leaves the ticket at zero again.
+ * Everything ahead of `ticket` is the head the host reads at policy-epoch boundaries. */
+typedef struct {
+    float sums[4];                  /* [0] Σ KL terms, [1] clipped rows of this rank's minibatch (16-B aligned:
+                                     * all-reduced under data parallelism), [2..3] zero */
+    float kl, clip_frac;            /* of the last decided step, over the global minibatch */
+    unsigned stopped;               /* sticky within one update: the Adam kernels take no step while set */
+    unsigned step;                  /* policy steps decided in this update */
+    int stop_step;                  /* index of the step that tripped it, −1 if none */
+    unsigned applied;               /* steps whose Adam ran, since the record was cleared */
+    unsigned ticket;
+    unsigned pad;
+    double partial[2 * PHIP_KL_PARTS];
+    float hist[PHIP_KL_HIST];       /* KL per decided step of the current update (later steps are not recorded) */
+} PhipKlRec;
+/* Σ (expm1(x) − x) and the clipped-row count of one policy minibatch (x = log-prob − old log-prob, rows of
+ * μ [m, A]) into rec->sums; one launch, deterministic (no floating-point atomics, grid a function of m), no
+ * host read.  decide_here != 0: the same launch also decides (below) from the local sums */
+void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
+                    float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec);
+/* kl = sums[0] / rows_global, clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
+ * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the
+ * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so
+ * that all ranks issue the same order of collectives */
+void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global);
+/* the host waits for the launches issued so far on the current stream only (an event recorded there) */
+void phip_stream_wait(void);
 
 /* ---------------- sampling / synthetic data (sample.hip) ---------------- */
 void phip_sample(const float* mu, const float* log_std, float* action, float* logprob, int m, int A,

@@ -284,6 +284,15 @@ void phip_sync(void) {
     PPO_CHECK(hipStreamSynchronize(g_stream));
 }
 
+// the host waits for the current stream's queued work only (target-KL early stopping's epoch-boundary check:
+// the policy loop's stream, while the value loop's keeps running)
+void phip_stream_wait(void) {
+    static hipEvent_t ev = nullptr;
+    if (!ev) PPO_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    PPO_CHECK(hipEventRecord(ev, stream()));
+    PPO_CHECK(hipEventSynchronize(ev));
+}
+
 void phip_side_fork(void) {
     ensure_device();
     PPO_CHECK(hipEventRecord(g_fork_ev, g_stream));
@@ -332,7 +341,7 @@ void ppo_synchronize(void) { phip_sync(); }
 const char* ppo_build_info(void) {
     return "libppo: hand-written HIP for gfx950 (MI355X); fp32 MFMA v_mfma_f32_32x32x2_f32 GEMMs; "
            "kernels: gemm{NT,NN,TN}, relu, mse, policy_head, log_prob, gae_scan, welford, normalize, "
-           "gather, adam_flat/multi, sample, synthetic fill; comm: RCCL";
+           "gather, adam_flat/multi, grad_norm, policy_kl, sample, synthetic fill; comm: RCCL";
 }
 
 void* ppo_dev_alloc(size_t bytes) { return phip_malloc(bytes); }

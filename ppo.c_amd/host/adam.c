@@ -163,14 +163,19 @@ void free_adam_cuda(Adam* adam) {
     free(adam);
 }
 
-void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NULL, 0, 0, NULL); }
+void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NULL, 0, 0, NULL, NULL); }
 
 /* w16 != NULL: also refresh the bf16 shadow of the first n16 parameters (flat spans only).
  * zero_g: clear the gradient span once read (flat spans only).  Returns bit 0: shadow refreshed,
  * bit 1: gradients cleared.  coef != NULL (flat spans only): the step's device clip coefficient
- * (PhipClipRec.coef), multiplied into the gradient scale by the kernel. */
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef) {
+ * (PhipClipRec.coef), multiplied into the gradient scale by the kernel.  skip != NULL (flat spans only): the
+ * device stop word of target-KL early stopping (PhipKlRec.stopped): while it is set the kernel takes no step
+ * and only clears the gradient where zero_g asks.  The host step counter advances either way; ppo_update
+ * sets it back by the steps the device skipped. */
+int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
+                         const unsigned* skip) {
     if (coef && !adam->flat) die("adam_update_cuda_w16: gradient clipping needs a flat Adam span");
+    if (skip && !adam->flat) die("adam_update_cuda_w16: target-KL early stopping needs a flat Adam span");
     float bc1, bc2;
     bias_corrections(adam, &bc1, &bc2);
     nn_note_device_update(adam->weights[0]);          /* the network's host mirrors are now stale */
@@ -180,7 +185,7 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
                              (uintptr_t)adam->v;
         if (al & 15u) zero_g = 0;
         phip_adam_flat_w16(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                           adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef);
+                           adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef, skip);
         return (w16 != NULL) | (zero_g ? 2 : 0);
     } else {
         phip_adam_multi(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v, lr,
@@ -193,9 +198,9 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
  * one launch; the side's step runs first in the step counters (ppo.cu:440-442 order; the spans are
  * independent).  Returns bit 0: shadow refreshed, bit 1: network gradients cleared, bit 2: side
  * gradients cleared; −1 (nothing done) when the pair does not qualify.  coef as in adam_update_cuda_w16:
- * one coefficient for both spans. */
+ * one coefficient for both spans; skip likewise: one stop word for both. */
 int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side, const float* coef) {
+                         int zero_side, const float* coef, const unsigned* skip) {
     const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
                          (uintptr_t)adam->v;
     if (!adam->flat || !side->flat || (al & 15u) || side->span > 256 || side->span < 1 || adam->span < 1 ||
@@ -209,7 +214,7 @@ int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
     phip_adam_flat_pair(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
                         adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, side->weights[0],
                         side->grad_weights[0], side->m, side->v, (int)side->span, lr_side, bc1s, bc2s,
-                        side->grad_scale, zero_side, coef);
+                        side->grad_scale, zero_side, coef, skip);
     return (w16 != NULL) | (zero_g ? 2 : 0) | (zero_side ? 4 : 0);
 }
 

@@ -81,10 +81,12 @@ void nn_sync_w16(NeuralNetwork* nn);       /* bf16 mode: refresh the bf16 weight
 /* adam.c */
 void adam_next_step(Adam* a, float lr, float* step, float* bc2);
 /* device Adam that also writes the bf16 shadow w16[0, n16) in the same pass; returns 1 when it did;
- * coef: NULL, or the step's device clip coefficient (gradient clipping, csrc/clip.hip) */
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef);
+ * coef: NULL, or the step's device clip coefficient (gradient clipping, csrc/clip.hip);
+ * skip: NULL, or the device stop word of target-KL early stopping (csrc/kl.hip) */
+int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
+                         const unsigned* skip);
 int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side, const float* coef);
+                         int zero_side, const float* coef, const unsigned* skip);
 
 /* checkpoint Adam with a known tensor count (n_expected < 0: unknown); rejects mismatches */
 Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda);

@@ -58,6 +58,11 @@ typedef struct {
      * policy loops run concurrently, so they share nothing here */
     float max_grad_norm;
     PhipClipRec* clip[2];
+    /* target-KL early stopping (ppo_set_target_kl; 0 = off, +inf = measure only): the policy loop's device
+     * record (csrc/kl.hip) — the step's KL and clip fraction, the sticky stop word the policy Adams read,
+     * the per-step KL history of the last update */
+    float target_kl;
+    PhipKlRec* kl;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -109,6 +114,7 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d->max_v = d->max_p = -1;
         d->clip[0] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
+        d->kl = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
         ppo->dev = d;
     }
     if (B > d->cap_B) {
@@ -144,6 +150,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ph_rows[0]); phip_free(d->ph_rows[1]); phip_free(d->ph_tgt); phip_free(d->ph_act);
     phip_free(d->ph_olp); phip_free(d->ph_adv);
     phip_free(d->clip[0]); phip_free(d->clip[1]);
+    phip_free(d->kl);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -368,11 +375,15 @@ static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
 /* Adam step of a network's flat span; in bf16 mode the same pass refreshes the bf16 parameter
  * shadow when the span starts at the network's parameters, else a separate conversion does.
  * zero_grads: the same pass clears the gradients it read (the next backward skips its memset);
- * coef: NULL, or the step's device clip coefficient */
-static int adam_update_net(Adam* adam, float lr, NeuralNetwork* nn, int zero_grads, const float* coef) {
+ * coef: NULL, or the step's device clip coefficient; skip: NULL, or the device stop word of target-KL
+ * early stopping */
+static int adam_update_net(Adam* adam, float lr, NeuralNetwork* nn, int zero_grads, const float* coef,
+                           const unsigned* skip) {
     const int own = adam->flat && adam->weights[0] == nn->d_params && adam->grad_weights[0] == nn->d_grads;
     const int fused = nn->dtype == 1 && own;
-    const int r = adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own, coef);
+    const int r = adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own, coef,
+                                       skip);
+    /* a skipped step left the parameters, hence their shadow, as they were: the refresh rewrites the same bits */
     if (!(r & 1) && nn->dtype == 1) nn_sync_w16(nn);
     return (r & 2) != 0;                 /* the network's gradients are zero again */
 }
@@ -441,6 +452,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int 
     /* the single-workgroup and cluster kernels run their Adam steps inside the launch and do not clip:
      * with gradient clipping on, the update takes the multi-launch loop */
     if (d->max_grad_norm > 0.f) return -1;
+    /* … and they neither measure the KL nor read a stop word: target-KL early stopping takes that loop too */
+    if (d->target_kl > 0.f) return -1;
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -604,7 +617,7 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
         return 1;
     }
     return adam_update_net(ppo->adam_V, ppo->lr_V, V, iv + 1 < c->nv,
-                           clip_coef(d, 0, ppo->adam_V, NULL, 0));
+                           clip_coef(d, 0, ppo->adam_V, NULL, 0), NULL);
 }
 
 static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab) {
@@ -648,6 +661,19 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
                          ppo->ent_coeff, d->gmu, pol->d_log_std_grad, d->stats + 1, *ls_zero);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
     }
+    /* target-KL early stopping (off: nothing launched): the step's KL and clip fraction from the μ the
+     * forward just left, on the device (kl.hip), before the step's Adam, which reads the stop word through
+     * `skip`.  Without a communicator one launch sums and decides.  With one, the sum launch writes this
+     * rank's two sums, one all-reduce of those four floats follows the step's gradient all-reduce on the
+     * same stream and communicator, and a one-workgroup launch decides from the global sums after the join:
+     * every rank decides from the same bits.  The extra collective is a function of the setting only, so
+     * the fixed order of collectives (comm.hip) holds as long as every rank holds the same target_kl. */
+    const int kl_on = !tab && d->target_kl > 0.f;
+    const long kl_rows = (long)B * phip_comm_world();
+    if (kl_on && c->comm) {
+        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, ppo->epsilon, d->target_kl, kl_rows, 0, d->kl);
+        phip_allreduce_sum_f32_async(d->kl->sums, 4);
+    }
     phip_allreduce_join();
     /* ppo.cu:440-442 order; the entropy Adam clears the log σ gradient it read (the next policy head
      * accumulates into zeros) */
@@ -661,12 +687,23 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     Adam* ap = ppo->adam_policy;
     /* μ's gradient span and the log σ gradient clip as one group: one coefficient for both Adams */
     const float* coef = clip_coef(d, 1, ap, pol->d_log_std_grad, A);
+    const unsigned* skip = NULL;
+    if (kl_on) {
+        if (!ap->flat || !ppo->adam_entropy->flat) die("ppo_update: target-KL early stopping needs flat Adam spans");
+        if (c->comm) phip_kl_decide(d->kl, d->target_kl, kl_rows);
+        else phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, ppo->epsilon, d->target_kl, kl_rows, 1, d->kl);
+        skip = &d->kl->stopped;
+    }
+    /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
+     * record behind it and may end the loop there, and a caller may read the last issued step's gradients
+     * (the next step, if one follows, clears them itself) */
+    const int clear = ip + 1 < c->np && !(kl_on && (ip + 1) % c->num_batches == 0);
     const int own = ap->flat && ap->weights[0] == mu->d_params && ap->grad_weights[0] == mu->d_grads;
     const int fused = mu->dtype == 1 && own;
     const int ls_own = ppo->adam_entropy->flat && ppo->adam_entropy->grad_weights[0] == pol->d_log_std_grad;
     const int r = adam_update_pair_w16(ap, ppo->lr_policy, fused ? mu->d_w16 : NULL, mu->num_params,
-                                         ip + 1 < c->np && own, ppo->adam_entropy, ppo->lr_policy,
-                                         ip + 1 < c->np && ls_own, coef);
+                                         clear && own, ppo->adam_entropy, ppo->lr_policy,
+                                         clear && ls_own, coef, skip);
     if (r >= 0) {
         if (!(r & 1) && mu->dtype == 1) nn_sync_w16(mu);
         *ls_zero = ls_own && (r & 4);
@@ -674,8 +711,17 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         return;
     }
     *ls_zero = ls_own &&
-               (adam_update_cuda_w16(ppo->adam_entropy, ppo->lr_policy, NULL, 0, ip + 1 < c->np, coef) & 2);
-    *p_zero = adam_update_net(ppo->adam_policy, ppo->lr_policy, mu, ip + 1 < c->np, coef);
+               (adam_update_cuda_w16(ppo->adam_entropy, ppo->lr_policy, NULL, 0, clear, coef, skip) & 2);
+    *p_zero = adam_update_net(ppo->adam_policy, ppo->lr_policy, mu, clear, coef, skip);
+}
+
+/* target-KL early stopping, at a policy-epoch boundary: the host waits for the policy loop's stream only
+ * (the bounded wait over every stream while a communicator is up) and reads the record's head */
+static int kl_stopped(PPODev* d, int comm, PhipKlRec* head) {
+    if (comm) phip_comm_wait("target-KL epoch check");
+    else phip_stream_wait();
+    phip_d2h(head, d->kl, offsetof(PhipKlRec, ticket));
+    return head->stopped != 0;
 }
 
 /* graph replay (opt-in, PPO_GRAPH=1; PPO_GRAPH_STEPS = steps per captured graph, default 16) for
@@ -688,6 +734,7 @@ static int step_graphs_ok(const StepCtx* c) {
     const char* e = getenv("PPO_GRAPH");
     if (!(e && *e && *e != '0') || c->comm || phip_comm_world() > 1 || c->B > 2048 || c->A > 32) return 0;
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
+    if (c->d->target_kl > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
     for (int i = 0; i < 3; i++) {
@@ -941,6 +988,14 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     /* eager steps: every step's gathered inputs up front (one launch per epoch instead of one per
      * step; on libppo's stream before the fork, so both loops see them) */
     if (!graphs) phase_gather(&c);
+    /* target-KL early stopping: the stop word, the stop step and the step counter start afresh with every
+     * update (stream-ordered, ahead of the fork: the policy loop's stream sees them) */
+    const int kl_on = d->target_kl > 0.f && np > 0;
+    if (kl_on) {
+        phip_memset(&d->kl->stopped, 0, 2 * sizeof(unsigned));          /* stopped, step */
+        phip_memset(&d->kl->stop_step, 0xFF, sizeof(int));              /* −1 */
+    }
+    long kl_issued = 0, kl_applied = 0;
     if (concurrent) phip_side_fork();
     long iv = 0, ip = 0;
     /* gradients cleared by the previous Adam step (not after a loop's last step: a caller may read
@@ -971,6 +1026,20 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
             } else {
                 policy_step(&c, ip, &p_zero, &ls_zero, 0);
                 if (ip == 0 && graphs && np >= 3) capture_steps(&c, 1);
+                /* target-KL early stopping: behind the last step of each policy epoch (and of the loop) the
+                 * host waits for the policy stream and reads the record; once the device has stopped, every
+                 * further policy step would be a no-op there, so none is issued — purely a saving: ending
+                 * the issue at any later boundary leaves identical parameters.  The decision is the same
+                 * bits on every rank, so all ranks end their policy loops at the same step. */
+                if (kl_on && ((ip + 1) % num_batches == 0 || ip + 1 == np)) {
+                    PhipKlRec head;
+                    const int stop = kl_stopped(d, comm, &head);
+                    if (stop || ip + 1 == np) {
+                        kl_issued = ip + 1;
+                        kl_applied = stop ? head.stop_step : ip + 1;
+                        np = ip + 1;
+                    }
+                }
             }
             if (concurrent) phip_side_use(0);
             d->n_p += done;
@@ -982,6 +1051,12 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     phip_graph_destroy(c.gv1);
     phip_graph_destroy(c.gp1);
     if (concurrent) phip_side_join();
+    /* the host step counters advanced per issued policy step; the steps the device skipped took no Adam
+     * step, so bias corrections and checkpoints continue as in a run that broke out of the loop */
+    if (kl_on && kl_issued > kl_applied) {
+        ppo->adam_policy->time_step -= (int)(kl_issued - kl_applied);
+        ppo->adam_entropy->time_step -= (int)(kl_issued - kl_applied);
+    }
     free(keys);
 }
 
@@ -997,6 +1072,7 @@ void ppo_reset_stats(void* vppo) {
     phip_memset(d->stats, 0, 4 * sizeof(float));
     /* norm, coef and the clipped-step counter (the 16 bytes ahead of the ticket) */
     for (int i = 0; i < 2; i++) phip_memset(d->clip[i], 0, offsetof(PhipClipRec, ticket));
+    phip_memset(d->kl, 0, offsetof(PhipKlRec, ticket));      /* the head: KL, clip fraction, stop state, applied */
     d->n_v = d->n_p = d->n_graph = 0;
 }
 
@@ -1006,8 +1082,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[13] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0};
+    double v[17] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1016,7 +1092,60 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[11 + i] = (double)r.clipped;
         }
     }
-    for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
+    if (n > 13 && d->target_kl > 0.f) {         /* target-KL early stopping: zeros while it is off */
+        PhipKlRec r;
+        phip_d2h(&r, d->kl, offsetof(PhipKlRec, ticket));
+        v[13] = r.kl;
+        v[14] = r.clip_frac;
+        v[15] = (double)r.applied;
+        v[16] = r.stopped ? (double)r.stop_step : -1.0;
+    }
+    for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
+}
+
+/* ppo_ext.h: target-KL early stopping */
+int ppo_set_target_kl(void* vppo, float target_kl) {
+    if (isnan(target_kl)) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    d->target_kl = target_kl > 0.f ? target_kl : 0.f;        /* +inf stays: measure, never stop */
+    return 0;
+}
+
+float ppo_get_target_kl(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo->dev ? ((PPODev*)ppo->dev)->target_kl : 0.f;
+}
+
+int ppo_kl_history(void* vppo, double* out, int n) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    phip_sync();
+    if (!(d->target_kl > 0.f)) return 0;
+    unsigned steps = 0;
+    phip_d2h(&steps, &d->kl->step, sizeof(unsigned));
+    long have = steps < (unsigned)PHIP_KL_HIST ? (long)steps : PHIP_KL_HIST;
+    if (have > n) have = n;
+    if (out && have > 0) {
+        float* h = (float*)xmalloc(sizeof(float) * (size_t)have);
+        phip_d2h(h, d->kl->hist, sizeof(float) * (size_t)have);
+        for (long i = 0; i < have; i++) out[i] = (double)h[i];
+        free(h);
+    }
+    return (int)steps;
+}
+
+int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
+                         int m, int A, float eps, double* out2) {
+    static PhipKlRec* rec = NULL;
+    if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
+    if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+    phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, eps, INFINITY, m, 1, rec);
+    float sums[4];
+    phip_d2h(sums, rec->sums, sizeof(sums));
+    out2[0] = (double)sums[0] / m;
+    out2[1] = (double)sums[1] / m;
+    return 0;
 }
 
 /* ppo_ext.h: global gradient-norm clipping */

@@ -153,6 +153,10 @@ _SIGS = {
     "ppo_set_max_grad_norm": (C.c_int, [_P, C.c_float]),
     "ppo_get_max_grad_norm": (C.c_float, [_P]),
     "ppo_grad_norm_device": (C.c_double, [_P, C.c_long, _P, C.c_long]),
+    "ppo_set_target_kl": (C.c_int, [_P, C.c_float]),
+    "ppo_get_target_kl": (C.c_float, [_P]),
+    "ppo_kl_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
+    "ppo_policy_kl_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double)]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
