@@ -10,6 +10,19 @@
  * over the flat range; otherwise a multi-tensor kernel walks a small table.
  * m and v are always flat device buffers of `size` floats (`size` counts the
  * span including alignment padding for flat networks; padding gradients are 0).
+ *
+ * Which lists are flat: a list given to create_adam_cuda / load_adam is flat only
+ * when its tensors abut (no float between one tensor's end and the next one's
+ * start) and every tensor has the same parameter→gradient offset.  Floats between
+ * tensors belong to the caller and are neither read nor written: a list with any
+ * gap is updated tensor by tensor.  create_adam_from_nn_cuda / load_adam_from_nn
+ * own their network's buffers (≤ 3 padding floats after each tensor, gradients 0)
+ * and keep the padded span: flat = 1, span = the padded extent.
+ *
+ * Contract: given identical fp32 gradients, parameters, m and v match the update
+ * rule above evaluated in C without FMA contraction (float operations, the ε added
+ * in double) bit for bit — for every g in the fp32 range, subnormals, ±inf and NaN
+ * included (NaN payloads aside) — whichever kernel runs (tests/test_gpu_adam.py).
  */
 #ifndef ADAM_H
 #define ADAM_H

@@ -73,6 +73,8 @@ def load(use_openblas=False):
         lib.ref_blas_name.restype = C.c_char_p
         lib.ref_adam_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
                                         C.POINTER(C.c_int), C.c_float, C.c_float, C.c_float]
+        lib.ref_adam_apply.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_float,
+                                       C.c_float]
         lib.ref_gae.argtypes = [C.c_void_p] * 5 + [C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                                    C.POINTER(C.c_float), C.POINTER(C.c_float)]
         lib.ref_policy_loss_and_grad.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_void_p, C.c_void_p,
@@ -265,6 +267,12 @@ def adam_update(params, grads, m, v, t, lr, beta1=0.9, beta2=0.999):
     load().ref_adam_update(_p(params), _p(np.ascontiguousarray(grads, _f32)), _p(m), _p(v), params.size,
                            C.byref(ts), beta1, beta2, lr)
     return ts.value
+
+
+def adam_apply(params, m, v, t, lr, beta1=0.9, beta2=0.999):
+    """The parameter line of adam_update alone, in place on params: m, v and the time step t as given."""
+    load().ref_adam_apply(_p(params), _p(np.ascontiguousarray(m, _f32)), _p(np.ascontiguousarray(v, _f32)),
+                          params.size, t, beta1, beta2, lr)
 
 
 def ppo_update(sizes, relu_flags, mu_params, log_std, v_params, buf, *, batch_size, n_epochs_policy=4,

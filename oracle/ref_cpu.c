@@ -432,6 +432,18 @@ void ref_adam_update(float* params, const float* grads, float* m, float* v, long
     }
 }
 
+/* the parameter line of ref_adam_update alone: m, v and the time step are taken as given */
+void ref_adam_apply(float* params, const float* m, const float* v, long size, int time_step, float beta1,
+                    float beta2, float lr) {
+    float bias_correction1 = 1 - powf(beta1, time_step);
+    float bias_correction2 = 1 - powf(beta2, time_step);
+    float step_size = lr / bias_correction1;
+    for (long i = 0; i < size; i++) {
+        float denom = sqrtf(v[i] / bias_correction2) + 1e-8;
+        params[i] -= step_size * m[i] / denom;
+    }
+}
+
 /* ------------------------------------------------------------------ */
 /* one PPO update (ppo.cu:395-443, CPU branch, without collect_trajectories) */
 /* ------------------------------------------------------------------ */

@@ -80,6 +80,9 @@ void ref_get_batch(const int* perm, int n, int batch_idx, int batch_size, int S,
 /* ---- Adam (adam.cu:53-74) ---- */
 void ref_adam_update(float* params, const float* grads, float* m, float* v, long size,
                      int* time_step, float beta1, float beta2, float lr);
+/* the parameter line of ref_adam_update alone (same expressions): m, v and time_step as given */
+void ref_adam_apply(float* params, const float* m, const float* v, long size, int time_step, float beta1,
+                    float beta2, float lr);
 
 /* ---- one PPO update = ppo.cu:395-443 (CPU branch) without the rollout ---- */
 typedef struct {

@@ -8,7 +8,8 @@
 // Arithmetic is the reference's, operation for operation (compiled without FMA contraction):
 //   m = β1·m + (1−β1)·g;  v = β2·v + (1−β2)·g²;
 //   denom = (float)(sqrtf(v/bc2) + 1e-8)   (double add, as in C);   p −= step·m/denom
-// so that, given identical gradients, parameters match the oracle bit for bit.
+// so that, given identical gradients, parameters, m and v match the oracle bit for bit — over the whole
+// fp32 range of g (subnormals, ±inf, NaN up to its payload): tests/test_gpu_adam.py.
 #include "dev.h"
 
 namespace {

@@ -1,14 +1,19 @@
 /*
  * adam.c — Adam objects (reference /root/reference/src/adam.cu).
  *
- * Device Adams detect when their tensors form one contiguous span (the flat
- * per-network buffers, with ≤3 floats of zero-gradient alignment padding
- * between tensors) and then update the whole span with a single vectorised
- * kernel; m and v are flat HBM buffers covering that span.
+ * Device Adams detect when their tensors form one contiguous span and then
+ * update the whole span with a single vectorised kernel; m and v are flat HBM
+ * buffers covering that span.  A caller's tensor list (create_adam_cuda,
+ * load_adam) is flat only when its tensors abut: floats between two tensors are
+ * the caller's, and the span kernel would read them as gradients and write them
+ * as parameters.  The network constructors own their buffers' ≤3 floats of
+ * zero-gradient alignment padding between tensors and keep the padded span.
  */
 #include "internal.h"
 
 #include <math.h>
+
+#define NN_PAD_GAP 3          /* neural_network.c aligns every tensor of a network's buffer to 4 floats */
 
 static Adam* adam_alloc(float** weights, float** grads, int* length, int num_layers, int size, float beta1,
                         float beta2) {
@@ -28,15 +33,17 @@ static Adam* adam_alloc(float** weights, float** grads, int* length, int num_lay
     return a;
 }
 
-/* contiguous with small (<4 float) padding gaps, identical param→grad offset for every tensor */
-static long flat_span(float** w, float** g, const int* len, int n) {
+/* contiguous with gaps of at most max_gap floats, identical param→grad offset for every tensor.
+ * max_gap: 0 for a caller's list, 3 for a network's own buffers (the caller vouches that the
+ * gap floats are padding it owns, with zero gradients) */
+static long flat_span(float** w, float** g, const int* len, int n, int max_gap) {
     if (n <= 0) return -1;
     const ptrdiff_t dg = g[0] - w[0];
     for (int i = 0; i < n; i++) {
         if (g[i] - w[i] != dg) return -1;
         if (i + 1 < n) {
             const ptrdiff_t gap = w[i + 1] - (w[i] + len[i]);
-            if (gap < 0 || gap > 3) return -1;
+            if (gap < 0 || gap > max_gap) return -1;
         }
     }
     return (long)((w[n - 1] + len[n - 1]) - w[0]);
@@ -124,16 +131,21 @@ void adam_update(Adam* adam, float lr) {
 }
 
 /* ---------------- device Adam (adam.cu:76-169) ---------------- */
-Adam* create_adam_cuda(float** weights, float** grad_weights, int* length, int num_layers, int size, float beta1,
-                       float beta2) {
+static Adam* adam_create_device(float** weights, float** grad_weights, int* length, int num_layers, int size,
+                                float beta1, float beta2, int max_gap) {
     Adam* a = adam_alloc(weights, grad_weights, length, num_layers, size, beta1, beta2);
     a->on_device = 1;
-    const long span = flat_span(weights, grad_weights, length, num_layers);
+    const long span = flat_span(weights, grad_weights, length, num_layers, max_gap);
     a->flat = span >= 0;
     a->span = a->flat ? span : size;
     a->m = (float*)phip_malloc(sizeof(float) * (size_t)align4(a->span));
     a->v = (float*)phip_malloc(sizeof(float) * (size_t)align4(a->span));
     return a;
+}
+
+Adam* create_adam_cuda(float** weights, float** grad_weights, int* length, int num_layers, int size, float beta1,
+                       float beta2) {
+    return adam_create_device(weights, grad_weights, length, num_layers, size, beta1, beta2, 0);
 }
 
 Adam* create_adam_from_nn_cuda(NeuralNetwork* nn, float beta1, float beta2) {
@@ -148,7 +160,7 @@ Adam* create_adam_from_nn_cuda(NeuralNetwork* nn, float beta1, float beta2) {
         w[2 * i + 1] = ly->d_biases; g[2 * i + 1] = ly->d_grad_biases; len[2 * i + 1] = ly->output_size;
         size += len[2 * i] + len[2 * i + 1];
     }
-    Adam* a = create_adam_cuda(w, g, len, 2 * L, size, beta1, beta2);
+    Adam* a = adam_create_device(w, g, len, 2 * L, size, beta1, beta2, NN_PAD_GAP);
     free(w); free(g); free(len);
     return a;
 }
@@ -253,8 +265,10 @@ void save_adam(Adam* adam, FILE* file, bool cuda) {
 }
 
 /* n_expected: tensors the caller's arrays hold (−1: unknown, the reference signature) — a checkpoint
- * whose tensor count or size disagrees is rejected before anything is allocated or copied */
-Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda) {
+ * whose tensor count or size disagrees is rejected before anything is allocated or copied.
+ * max_gap: as in flat_span (0 for a caller's list, NN_PAD_GAP for a network's own buffers) */
+static Adam* load_adam_gap(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda,
+                           int max_gap) {
     int size, t, n;
     float b1, b2;
     if (fread(&size, sizeof(int), 1, file) != 1 || fread(&t, sizeof(int), 1, file) != 1 ||
@@ -276,7 +290,7 @@ Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* lengt
         die("checkpoint: unexpected end of file");
     Adam* a;
     if (cuda) {
-        a = create_adam_cuda(weights, grad_weights, length, n, size, b1, b2);
+        a = adam_create_device(weights, grad_weights, length, n, size, b1, b2, max_gap);
         long src = 0, dst = 0;
         for (int i = 0; i < n; i++) {
             if (a->flat) dst = (long)(a->weights[i] - a->weights[0]);
@@ -297,6 +311,10 @@ Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* lengt
     return a;
 }
 
+Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda) {
+    return load_adam_gap(file, weights, grad_weights, length, n_expected, cuda, 0);
+}
+
 Adam* load_adam(FILE* file, float** weights, float** grad_weights, int* length, bool cuda) {
     return load_adam_ex(file, weights, grad_weights, length, -1, cuda);
 }
@@ -315,7 +333,7 @@ Adam* load_adam_from_nn(FILE* file, NeuralNetwork* nn, bool cuda) {
         len[2 * i] = ly->input_size * ly->output_size;
         len[2 * i + 1] = ly->output_size;
     }
-    Adam* a = load_adam_ex(file, w, g, len, 2 * L, cuda);
+    Adam* a = load_adam_gap(file, w, g, len, 2 * L, cuda, NN_PAD_GAP);
     free(w); free(g); free(len);
     return a;
 }

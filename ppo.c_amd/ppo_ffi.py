@@ -208,6 +208,14 @@ _SIGS = {
     "create_adam_from_nn_cuda": (C.POINTER(Adam), [C.POINTER(NeuralNetwork), C.c_float, C.c_float]),
     "adam_update_cuda": (None, [C.POINTER(Adam), C.c_float]),
     "free_adam_cuda": (None, [C.POINTER(Adam)]),
+    "create_adam": (C.POINTER(Adam), [C.POINTER(_P), C.POINTER(_P), c_int_p, C.c_int, C.c_int, C.c_float,
+                                     C.c_float]),
+    "adam_update": (None, [C.POINTER(Adam), C.c_float]),
+    "free_adam": (None, [C.POINTER(Adam)]),
+    # FILE* arguments: an opaque pointer from the C library's fopen
+    "save_adam": (None, [C.POINTER(Adam), _P, C.c_bool]),
+    "load_adam": (C.POINTER(Adam), [_P, C.POINTER(_P), C.POINTER(_P), c_int_p, C.c_bool]),
+    "load_adam_from_nn": (C.POINTER(Adam), [_P, C.POINTER(NeuralNetwork), C.c_bool]),
     # buffer
     "create_trajectory_buffer": (C.POINTER(TrajectoryBuffer), [C.c_int, C.c_int, C.c_int]),
     "free_trajectory_buffer": (None, [C.POINTER(TrajectoryBuffer), C.c_bool]),

@@ -80,6 +80,25 @@ def test_adam_vs_torch(oracle):
     assert t == g["grads"].shape[0]
 
 
+def test_adam_apply_is_the_parameter_line_of_adam_update(oracle):
+    """numpy fp32 moment updates (one rounding per operation, as C evaluates them) followed by
+    ref_adam_apply reproduce ref_adam_update bit for bit, step after step."""
+    g = gold("adam")
+    lr, b1, b2 = float(g["lr"]), F32(0.9), F32(0.999)
+    p = g["p0"].astype(F32)
+    m, v = np.zeros_like(p), np.zeros_like(p)
+    p2, m2, v2 = p.copy(), m.copy(), v.copy()
+    for k in range(g["grads"].shape[0]):
+        gk = g["grads"][k].astype(F32)
+        assert oracle.adam_update(p, gk, m, v, k, lr) == k + 1
+        m2 = b1 * m2 + (F32(1) - b1) * gk
+        v2 = b2 * v2 + (F32(1) - b2) * (gk * gk)
+        assert m2.dtype == F32 and v2.dtype == F32
+        oracle.adam_apply(p2, m2, v2, k + 1, lr)
+        for got, want, what in ((m2, m, "m"), (v2, v, "v"), (p2, p, "p")):
+            np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32), f"{what} after step {k + 1}")
+
+
 def test_glibc_rand_and_reference_shuffle(oracle):
     """The libc rand() stream the reference consumes (srand → rand) and its swap shuffle."""
     import ctypes as C
