@@ -112,7 +112,11 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * clipping is off; callers passing n <= 9 see no change),
  * out[13]=approximate KL of the last decided policy step, out[14]=its clip fraction, out[15]=policy steps
  * whose Adam ran since the last reset, out[16]=stop step of the last update (−1: none) (all four 0 while
- * target-KL early stopping is off; callers passing n <= 13 see no change) */
+ * target-KL early stopping is off; callers passing n <= 13 see no change),
+ * out[17]=Σ clipped rows over the value steps since the last reset, out[18]=Σ rows of those steps (value-loss
+ * clipping, ppo_set_value_clip: exact integer counts, under data parallelism THIS RANK's rows; both 0 while it
+ * is off; callers passing n <= 17 see no change).  While value-loss clipping is on, out[0] accumulates the
+ * clipped loss. */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
 
@@ -162,6 +166,40 @@ int    ppo_kl_history(void* ppo, double* out, int n);
  * [m] → out2 = {approximate KL, clip fraction}; returns 0, −1 for bad arguments; synchronises */
 int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
                             int m, int A, float eps, double* out2);
+/* PPO2 value-loss clipping (off by default; not in the reference; baselines PPO2, CleanRL clip_vloss,
+ * Stable-Baselines3 clip_range_vf).  For a value minibatch of m rows, with y the network's value of a row, t its
+ * target (adv_target), v_old its old value and eps_v > 0 the clip range, every form of the value head (the plain
+ * MSE kernel, the fused output layer in fp32 and bf16 storage, the folded head and the head carried by the x3
+ * grad_W launch — one device function, csrc/vclip.h) computes in fp32, in this order:
+ *     d      = y − v_old
+ *     inside = !(|d| > eps_v)                      (NaN counts as inside: it propagates exactly as with clipping off)
+ *     lu     = (t − y)²
+ *     if inside:      l = lu, g = 2·(y − t)/m      (bit for bit the head with clipping off)
+ *     else:  yc = v_old + copysignf(eps_v, d)
+ *            lc = (t − yc)²
+ *            if lu >= lc:  l = lu, g = 2·(y − t)/m (max() picks the unclipped term; ties go here)
+ *            else:         l = lc, g = 0, the row counts as "clipped"
+ *     loss = Σ l / m                               (the reference's MSE convention, no ½)
+ * — mean(max((y − t)², (v_old + clamp(y − v_old, ±eps_v) − t)²)) with the sub-gradient fixed; an inside row
+ * never depends on whether v_old + (y − v_old) rounds back to y.  The gradient stays one scalar per row, and no
+ * launch is added to a value step.  While it is on, ppo_update runs the multi-launch loop (no single-workgroup /
+ * cluster phases, no graph replay), as with gradient clipping and target-KL early stopping, and works together
+ * with both and with data parallelism: the head is element-wise, so no collective is added and the order of
+ * collectives does not depend on the setting.  Not part of a checkpoint: set it again after load_ppo.
+ * eps_v > 0 and finite: on; <= 0 or +inf: off.  Returns 0, or −1 for NaN (setting unchanged). */
+int    ppo_set_value_clip(void* ppo, float eps_v);
+float  ppo_get_value_clip(void* ppo);                     /* 0 when off */
+/* The old values.  By default they are the V(state) of every buffer row that the update's own GAE has just
+ * computed (with them the first value step of an update has y ≈ v_old, so nothing clips yet).  Callers who
+ * stored values at rollout time pass them here: a caller-owned device array indexed by BUFFER ROW, which must
+ * stay valid while it is set.  Returns −1 (unchanged) when n is smaller than the buffer capacity; NULL restores
+ * the default. */
+int    ppo_value_clip_old_values(void* ppo, const float* d_v_old, long n);
+/* the update's own head arithmetic (the plain head's kernel) on caller-supplied device arrays: y [m], old values
+ * read at d_v_old[d_rows[i]] (d_rows NULL: the identity), targets [m] → d_g [m] = ∂loss/∂y and out3 = {loss,
+ * clipped rows, rows}; returns 0, −1 for bad arguments (a NULL array, m <= 0, eps_v not > 0); synchronises */
+int    ppo_value_clip_head_device(const float* d_y, const float* d_v_old, const int* d_rows, const float* d_tgt, int m,
+                                  float eps_v, float* d_g, double* out3);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

@@ -30,6 +30,7 @@
 //     the atomics per output element;
 //   * XCD-aware block remap: tiles that share an operand panel run on one XCD's L2.
 #include "dev.h"
+#include "vclip.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -81,6 +82,10 @@ struct X3Args {
     const float* vh_ypart; const float* vh_b; const float* vh_t;
     float* vh_y; float* vh_gb; float* vh_loss;
     int vh_slots;
+    // … with PPO2 value-loss clipping (vclip.h; vh_vc.v_old null: off): every workgroup gathers its split's
+    // old values through vh_vc.rows and takes g from the shared row function; only tile (0, 0) of each
+    // split counts the clipped rows and the rows
+    PhipVClip vh_vc;
     // grad_x carrying the previous grad_W's split-K reduction (phip_x3_defer_reduce): workgroups
     // gemm_wgs … gemm_wgs + red_wgs − 1 sum red_splits slabs of red_n floats (stride red_stride) into red_out
     const float* red_slab; float* red_out;
@@ -548,20 +553,21 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
             const bool head = tm == 0 && tn == 0;
             const float bias = a.vh_b[0];
             float ls = 0.f, sgs = 0.f;
+            int nclip = 0, nrow = 0;
             for (int rr = tid; rr < kend - kbeg; rr += NTH) {
                 const int row = kbeg + rr;
                 float yv = 0.f;
                 for (int q = 0; q < a.vh_slots; ++q) yv += a.vh_ypart[(long)q * a.K + row];
                 yv += bias;
-                const float tv = a.vh_t[row];
-                const float d = tv - yv;
-                const float gv = 2 * (yv - tv) / (float)a.K;
+                float gv;
+                const float lv = ppo::value_head_row(yv, a.vh_t[row], (float)a.K, a.vh_vc, row, gv, nclip);   // vclip.h
                 gl[rr] = gv;
                 if (head) {
                     a.vh_y[row] = yv;
                     const_cast<float*>(a.fold_g)[row] = gv;
-                    ls += d * d;
+                    ls += lv;
                     sgs += gv;
+                    ++nrow;
                 }
             }
             if (head) {
@@ -570,6 +576,10 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 if (lane == 0) {
                     atomicAdd(a.vh_gb, sgs);
                     if (a.vh_loss) atomicAdd(a.vh_loss, ls * (1.0f / (float)a.K));
+                }
+                if (a.vh_vc.v_old) {     // a split's rows fit LDS (< 2^16): the fp32 wave sums are exact
+                    const float fc = ppo::wave_sum64((float)nclip), fr = ppo::wave_sum64((float)nrow);
+                    if (lane == 0) ppo::value_clip_count(a.vh_vc, (unsigned long long)fc, (unsigned long long)fr);
                 }
             }
             __syncthreads();
@@ -1020,7 +1030,7 @@ void launch_x3(X3Args a) {
             lds += 4 * (size_t)a.kchunk;
         } else {                                       // no room: the head kernel first, g from HBM
             phip_value_head(a.vh_ypart, a.vh_slots, a.vh_b, a.vh_t, a.K, a.vh_y, const_cast<float*>(a.fold_g), a.vh_gb,
-                            a.vh_loss);
+                            a.vh_loss, &a.vh_vc);
             a.vh_ypart = nullptr;
         }
     }
@@ -1283,12 +1293,12 @@ void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bi
 
 void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
                          const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum);
+                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc);
 
 // zeroed: gW / gb already hold zeros (one memset per backward); otherwise they are cleared here
 void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed) {
     phip_x3_bwd_w_vhead(gW, gb, g, nullptr, nullptr, nullptr, x, m, n, l, zeroed, nullptr, 0, nullptr, nullptr, nullptr,
-                        nullptr, nullptr);
+                        nullptr, nullptr, nullptr);
 }
 
 // value-head fold (fold_g): g = h [m, l] (fp32, its mask is the operand), x scaled by fold_g per row, the
@@ -1297,15 +1307,16 @@ void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, 
 void phip_x3_bwd_w_fold(float* gW, float* gb, const float* g, const float* fold_g, const float* fold_w,
                         float* fold_gw, const float* x, int m, int n, int l, int zeroed) {
     phip_x3_bwd_w_vhead(gW, gb, g, const_cast<float*>(fold_g), fold_w, fold_gw, x, m, n, l, zeroed, nullptr, 0, nullptr,
-                        nullptr, nullptr, nullptr, nullptr);
+                        nullptr, nullptr, nullptr, nullptr, nullptr);
 }
 
 // + the carried value head (ypart set): g (fold_g, written) from the forward's partial dots, y, the output
-// bias gradient gb_out and the loss, in this launch (X3Args vh_*)
+// bias gradient gb_out and the loss, in this launch (X3Args vh_*); vc: that head's value-loss clipping (null: off)
 void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
                          const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum) {
+                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc) {
     if (l <= 0 || n <= 0) return;
+    PPO_REQUIRE(!vc || !vc->v_old || (ypart && vc->counts && vc->eps > 0.f), "phip_x3_bwd_w: value-clip operands");
     PPO_REQUIRE(!ypart || (fold_g && slots > 0 && b && tgt && y && gb_out), "phip_x3_bwd_w: carried value head operands");
     PPO_REQUIRE(gW && g && x && n % 4 == 0 && l % 4 == 0 && al16(g) && al16(x), "phip_x3_bwd_w: unsupported operands");
     PPO_REQUIRE(!fold_g || (fold_w && fold_gw && gb), "phip_x3_bwd_w: value-head fold operands");
@@ -1344,6 +1355,7 @@ void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, co
     a.gbias = gb;
     a.fold_g = fold_g; a.fold_w = fold_w; a.fold_gw = fold_gw;
     a.vh_ypart = ypart; a.vh_slots = slots; a.vh_b = b; a.vh_t = tgt; a.vh_y = y; a.vh_gb = gb_out; a.vh_loss = loss_accum;
+    if (vc) a.vh_vc = *vc;
     // split-K partials: per-split slabs written with plain stores and summed by one reduce launch
     // (16 MB of f32 atomics at ≈1.3 TB/s set the grad_W time of small batches; the slab path moves
     // the same bytes at store / load rate, and its sum is deterministic); the bias gradient keeps

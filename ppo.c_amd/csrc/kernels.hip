@@ -10,6 +10,7 @@
 // Arithmetic mirrors the reference's C promotions (its double exp/pow temporaries) so results
 // match the oracle to a few ulps; reductions use wave shuffles + one f32 atomic per workgroup.
 #include "dev.h"
+#include "vclip.h"
 
 #include <algorithm>
 
@@ -81,21 +82,28 @@ __global__ void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, 
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) y[i] += x[i];
 }
 
-// loss.cu:5-23 semantics: L = Σ(t−y)²/count, grad = 2(y−t)/count
+// loss.cu:5-23 semantics: L = Σ(t−y)²/count, grad = 2(y−t)/count; vc (vclip.h; v_old null: off) clips the
+// value loss of the update's plain head (phip_mse_vclip: count < 2^31 rows)
 __global__ void mse_kernel(const float* __restrict__ y, const float* __restrict__ t, long n,
-                           float* __restrict__ grad, float* d_loss, float* d_loss_accum) {
+                           float* __restrict__ grad, float* d_loss, float* d_loss_accum, PhipVClip vc) {
     __shared__ float red[TPB / 64];
     float s = 0.f;
     const float inv = 1.0f / (float)n;
+    int nclip = 0, nrow = 0;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
-        const float d = t[i] - y[i];
-        s += d * d;
-        if (grad) grad[i] = 2 * (y[i] - t[i]) / (float)n;
+        float gv;
+        s += ppo::value_head_row(y[i], t[i], (float)n, vc, (int)i, gv, nclip);
+        if (grad) grad[i] = gv;
+        ++nrow;
     }
     s = block_sum(s, red);
     if (threadIdx.x == 0) {
         if (d_loss) atomicAdd(d_loss, s * inv);
         if (d_loss_accum) atomicAdd(d_loss_accum, s * inv);
+    }
+    if (vc.v_old) {     // per wave (≤ 2^17 rows of a count < 2^31 on ≤ 4096 workgroups: the fp32 sums are exact)
+        const float fc = wave_sum((float)nclip), fr = wave_sum((float)nrow);
+        if ((threadIdx.x & 63) == 0) ppo::value_clip_count(vc, (unsigned long long)fc, (unsigned long long)fr);
     }
 }
 
@@ -108,27 +116,31 @@ __global__ void mse_kernel(const float* __restrict__ y, const float* __restrict_
 // kernel runs only when that launch has no LDS room for its split's g.
 __global__ void value_head_kernel(const float* __restrict__ ypart, int slots, const float* __restrict__ b,
                                   const float* __restrict__ t, int m, float* __restrict__ y, float* __restrict__ g,
-                                  float* gb, float* d_loss_accum) {
+                                  float* gb, float* d_loss_accum, PhipVClip vc) {
     __shared__ float red[TPB / 64];
     const float bias = b[0];
     float s = 0.f, sg = 0.f;
+    int nclip = 0, nrow = 0;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < m; i += gridDim.x * TPB) {
         float yv = 0.f;
         for (int q = 0; q < slots; ++q) yv += ypart[(long)q * m + i];
         yv += bias;
-        const float tv = t[i];
-        const float d = tv - yv;
-        s += d * d;
-        const float gv = 2 * (yv - tv) / (float)m;
+        float gv;
+        s += ppo::value_head_row(yv, t[i], (float)m, vc, i, gv, nclip);     // vclip.h (vc.v_old null: plain MSE)
         y[i] = yv;
         g[i] = gv;
         sg += gv;
+        ++nrow;
     }
     s = block_sum(s, red);
     sg = block_sum(sg, red);
     if (threadIdx.x == 0) {
         atomicAdd(gb, sg);
         if (d_loss_accum) atomicAdd(d_loss_accum, s * (1.0f / (float)m));
+    }
+    if (vc.v_old) {     // per wave (< 2^24 rows: the fp32 sums are exact)
+        const float fc = wave_sum((float)nclip), fr = wave_sum((float)nrow);
+        if ((threadIdx.x & 63) == 0) ppo::value_clip_count(vc, (unsigned long long)fc, (unsigned long long)fr);
     }
 }
 
@@ -377,12 +389,12 @@ void phip_axpy(float* y, const float* x, long count) {
 }
 
 void phip_value_head(const float* ypart, int slots, const float* b, const float* tgt, int m, float* y, float* g,
-                     float* gb, float* d_loss_accum) {
+                     float* gb, float* d_loss_accum, const PhipVClip* vc) {
     if (m <= 0) return;
     ppo::ProfScope ps(PPO_K_HEAD, 4.0 * m * (slots + 3));
     const int hb = std::min(ppo_divup(m, TPB), 256);
     hipLaunchKernelGGL(value_head_kernel, dim3(hb), dim3(TPB), 0, ppo::stream(), ypart, slots, b, tgt, m, y, g, gb,
-                       d_loss_accum);
+                       d_loss_accum, vc ? *vc : PhipVClip{});
     PPO_LAUNCH_CHECK();
 }
 
@@ -391,7 +403,17 @@ void phip_mse(const float* y, const float* t, long count, float* grad, float* d_
     if (d_loss) phip_memset(d_loss, 0, sizeof(float));
     ppo::ProfScope ps(PPO_K_HEAD, 12.0 * count);
     hipLaunchKernelGGL(mse_kernel, dim3(grid_for(count, 8)), dim3(TPB), 0, ppo::stream(), y, t, count, grad,
-                       d_loss, d_loss_accum);
+                       d_loss, d_loss_accum, PhipVClip{});
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_mse_vclip(const float* y, const float* t, long count, float* grad, float* d_loss_accum, const PhipVClip* vc) {
+    if (count <= 0) return;
+    PPO_REQUIRE(count < (1L << 31), "phip_mse_vclip: row count out of range");
+    PPO_REQUIRE(!vc || !vc->v_old || (vc->counts && vc->eps > 0.f), "phip_mse_vclip: value-clip operands");
+    ppo::ProfScope ps(PPO_K_HEAD, 12.0 * count);
+    hipLaunchKernelGGL(mse_kernel, dim3(grid_for(count, 8)), dim3(TPB), 0, ppo::stream(), y, t, count, grad,
+                       (float*)nullptr, d_loss_accum, vc ? *vc : PhipVClip{});
     PPO_LAUNCH_CHECK();
 }
 

@@ -25,6 +25,7 @@
 // profiles/r02_out_head_ab.txt).  It takes out_bwd_wide_kernel (head + backward, thread per column)
 // after the forward GEMM, or policy_out_fused_kernel (forward + head + backward) up to 8192 rows.
 #include "dev.h"
+#include "vclip.h"
 
 #include <algorithm>
 #include <cmath>
@@ -66,6 +67,7 @@ struct OutArgs {
     const void* x; const void* W; const float* b;     // x [m, n] (the last hidden activation), W [A, n], b [A]
     int m, n, relu_in;                                // relu_in: gx masked by x > 0
     const float* tgt;                                 // value head: targets [m]
+    PhipVClip vc;                                     // value head: loss clipping (vclip.h; v_old null: off)
     const float* log_std; const float* action; const float* adv; const float* old_lp;   // policy head
     float eps, ent_coeff;
     float* y; void* gx; float* gW; float* gb; float* grad_log_std; float* loss_accum;
@@ -163,9 +165,13 @@ __device__ __forceinline__ void store_cols(float* __restrict__ p, const float (&
 #define OUTHEAD_PF 4                                 // rows in flight per wave (one wave per row)
 #endif
 
-template <int NPL, int A, int HEAD, int WPR, typename T>
+// VC: the value head with loss clipping (vclip.h) — its own instantiation, so that with clipping off the
+// kernel is the one compiled without it (the clip branch costs the width-256 kernels a wave of occupancy)
+template <int NPL, int A, int HEAD, int WPR, typename T, bool VC = false>
 __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
     constexpr bool B16 = sizeof(T) == 2;
+    static_assert(!VC || HEAD == 0, "value-loss clipping: the value head");
+    const PhipVClip vc = VC ? p.vc : PhipVClip{};
     const T* __restrict__ X = static_cast<const T*>(p.x);
     const T* __restrict__ Wp = static_cast<const T*>(p.W);
     T* __restrict__ GX = static_cast<T*>(p.gx);
@@ -200,6 +206,7 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
         for (int q = 0; q < NPL; ++q) gWacc[a][q] = 0.f;
     }
     float loss = 0.f;
+    int nclip = 0;                                     // value-loss clipping: this wave's clipped rows (wave-uniform)
 
     int it = 0;
     const int stride = gridDim.x * SLOTS;
@@ -252,10 +259,10 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
         const bool owner = part == 0;                  // one wave per row counts the row-wide sums
         float g[A];
         if (HEAD == 0) {                                   // loss.cu:5-23 (kernels.hip mse_kernel)
-            const float t = p.tgt[row];
-            const float d = t - yv[0];
-            if (owner) loss += d * d;
-            g[0] = 2 * (yv[0] - t) / (float)m;
+            int c = 0;
+            const float l = ppo::value_head_row(yv[0], p.tgt[row], (float)m, vc, row, g[0], c);   // vclip.h
+            if (owner) loss += l;
+            nclip += __builtin_amdgcn_readfirstlane(c);    // every lane evaluated the same row: a scalar counter
         } else {                                           // kernels.hip policy_head_kernel, per row
             float act[A];
 #pragma unroll
@@ -328,6 +335,10 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
             atomicAdd(p.grad_log_std + threadIdx.x, l);
         }
     }
+    if (VC && vc.v_old && part == 0 && lane == 0) {   // one count per row: its owner wave's; the rows of
+        const int nrow = first < m ? (m - first + stride - 1) / stride : 0;      // slot `slot`: first, first + stride, …
+        ppo::value_clip_count(vc, (unsigned long long)nclip, (unsigned long long)nrow);
+    }
     if (threadIdx.x == 0 && p.loss_accum) {
         float s = 0.f;
 #pragma unroll
@@ -346,12 +357,12 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
     }
 }
 
-template <int NPL, int A, int HEAD, int WPR, typename T>
-void launch(const OutArgs& a) {
+template <int NPL, int A, int HEAD, int WPR, typename T, bool VC>
+void launch_k(const OutArgs& a) {
     constexpr int N = 64 * NPL * WPR, SLOTS = NW / WPR;
     const size_t lds = sizeof(float) * (size_t)std::max(SLOTS * A * N, 2 * SLOTS * WPR * A);
     static_assert(sizeof(float) * SLOTS * A * N <= 150 * 1024, "out_head: LDS");
-    auto kern = out_head_kernel<NPL, A, HEAD, WPR, T>;
+    auto kern = out_head_kernel<NPL, A, HEAD, WPR, T, VC>;
     if (lds > 64 * 1024) {
         static bool attr = false;
         if (!attr) {
@@ -367,6 +378,14 @@ void launch(const OutArgs& a) {
     if (grid < 1) grid = 1;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(NTH), lds, ppo::stream(), a);
     PPO_LAUNCH_CHECK();
+}
+
+template <int NPL, int A, int HEAD, int WPR, typename T>
+void launch(const OutArgs& a) {
+    if constexpr (HEAD == 0) {
+        if (a.vc.v_old) { launch_k<NPL, A, HEAD, WPR, T, true>(a); return; }
+    }
+    launch_k<NPL, A, HEAD, WPR, T, false>(a);
 }
 
 // one wave per row up to width 512; at width 1024 (value networks) two waves per row in fp32
@@ -869,9 +888,10 @@ int phip_out_head_supported(int head, int n, int A) {
 void phip_out_head(int head, int bf16, const void* x, int relu_in, const void* W, const float* b, int m, int n,
                    int A, const float* tgt, const float* log_std, const float* action, const float* adv,
                    const float* old_lp, float eps, float ent_coeff, float* y, void* gx, float* gW, float* gb,
-                   float* grad_log_std, float* loss_accum) {
+                   float* grad_log_std, float* loss_accum, const PhipVClip* vc) {
     if (m <= 0) return;
     PPO_REQUIRE(phip_out_head_supported(head, n, A), "phip_out_head: unsupported shape");
+    PPO_REQUIRE(!vc || !vc->v_old || (head == 0 && vc->counts && vc->eps > 0.f), "phip_out_head: value-clip operands");
     PPO_REQUIRE(x && W && b && y && gx && gW && gb, "phip_out_head: null operand");
     PPO_REQUIRE(head == 0 ? tgt != nullptr : (log_std && action && adv && old_lp && grad_log_std),
                 "phip_out_head: missing head inputs");
@@ -879,7 +899,7 @@ void phip_out_head(int head, int bf16, const void* x, int relu_in, const void* W
     ppo::ProfScope ps(PPO_K_HEAD, 8.0 * m * n);
     OutArgs a{};
     a.x = x; a.W = W; a.b = b; a.m = m; a.n = n; a.relu_in = relu_in;
-    a.tgt = tgt; a.log_std = log_std; a.action = action; a.adv = adv; a.old_lp = old_lp;
+    a.tgt = tgt; a.vc = vc ? *vc : PhipVClip{}; a.log_std = log_std; a.action = action; a.adv = adv; a.old_lp = old_lp;
     a.eps = eps; a.ent_coeff = ent_coeff;
     a.y = y; a.gx = gx; a.gW = gW; a.gb = gb; a.grad_log_std = grad_log_std; a.loss_accum = loss_accum;
     using b16 = unsigned short;

@@ -36,6 +36,17 @@ void  phip_side_join(void);
 void  phip_record_error(const char* msg);
 void  phip_drain(void);                 /* synchronise both streams, ignoring errors (before a fatal exit) */
 
+/* ---------------- PPO2 value-loss clipping (vclip.h) ---------------- */
+/* what every form of the value head takes (ppo_ext.h ppo_set_value_clip; csrc/vclip.h value_head_row holds
+ * the arithmetic once): row i of the minibatch reads its old value at v_old[rows[i]].  A NULL PhipVClip*,
+ * or v_old == NULL, is "off": today's arithmetic and launches. */
+typedef struct {
+    const float* v_old;             /* old values indexed by buffer row (device); NULL: off */
+    const int* rows;                /* minibatch slot -> buffer row (device); NULL: the identity */
+    float eps;                      /* the clip range eps_v > 0 */
+    unsigned long long* counts;     /* device [2]: += clipped rows, += rows (integer atomics: exact) */
+} PhipVClip;
+
 /* ---------------- dense layers (gemm.hip) ---------------- */
 /* y[m,l] = x[m,n]·W[l,n]ᵀ + b[l], optional ReLU (mat_mul.cu:132-163 + K1/K5 fused) */
 void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu);
@@ -93,10 +104,11 @@ void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, co
 void phip_x3_bwd_w_fold(float* gW, float* gb, const float* h, const float* fold_g, const float* fold_w, float* fold_gw,
                         const float* x, int m, int n, int l, int zeroed);
 /* phip_x3_bwd_w_fold carrying the value head: g (into fold_g) from the forward's partial dots ypart [slots][m]
- * + b against tgt, y, the output bias gradient gb_out and loss_accum (+= loss / m) — value_head_kernel's work */
+ * + b against tgt, y, the output bias gradient gb_out and loss_accum (+= loss / m) — value_head_kernel's work;
+ * vc: value-loss clipping of that head (NULL: off) */
 void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* h, float* fold_g, const float* fold_w, float* fold_gw,
                          const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum);
+                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc);
 /* dst[i, :] = bf16(src[rows[i], :]) for i < m (S % 4 == 0): layer 0's gather in bf16 mode */
 void phip_gather_rows_bf16(unsigned short* dst, const float* src, const int* rows, int m, int S);
 void phip_f32_to_bf16(unsigned short* dst, const float* src, long count);
@@ -154,14 +166,17 @@ void phip_axpy(float* y, const float* x, long count);
 /* d_loss[0] = Σ(t−y)²/count (written), d_loss_accum[0] += same (if non-NULL);
  * grad = 2(y−t)/count (if non-NULL).  loss.cu:25-83 fused, no host sync. */
 void phip_mse(const float* y, const float* t, long count, float* grad, float* d_loss, float* d_loss_accum);
+/* the same kernel as the update's plain value head: value-loss clipping per vc (NULL: off), the loss into
+ * d_loss_accum only */
+void phip_mse_vclip(const float* y, const float* t, long count, float* grad, float* d_loss_accum, const PhipVClip* vc);
 /* the folded value head (kernels.hip): y = Σ ypart slots + b, loss += Σ(t−y)²/m, g = 2(y−t)/m, gb += Σ g;
  * and Ws = diag(w)·W for the hidden layer's grad_x (W [l][n], w [l]) */
 void phip_value_head(const float* ypart, int slots, const float* b, const float* tgt, int m, float* y, float* g,
-                     float* gb, float* d_loss_accum);
+                     float* gb, float* d_loss_accum, const PhipVClip* vc);
 /* out_head.hip: output layer forward + loss head + output-layer backward in one pass (ppo_update;
  * head 0 = value, A = 1, MSE against tgt; 1 = policy, clipped surrogate); gW / gb / grad_log_std
  * accumulated into zeroed outputs, loss into loss_accum; widths 64…1024, A ∈ {1, 6}; bf16 != 0:
- * x, W and gx stored bf16 (bf16 compute mode, value head) */
+ * x, W and gx stored bf16 (bf16 compute mode, value head); vc: the value head's loss clipping (NULL: off) */
 int  phip_out_head_supported(int head, int n, int A);
 /* gemm.hip: 1 when ppo_gemm_tune(·, 1) asked for atomic-free (deterministic) gradient products */
 int  phip_gemm_deterministic(void);
@@ -185,7 +200,7 @@ int  phip_policy_head_bwd_wide(const float* mu, const float* log_std, const floa
 void phip_out_head(int head, int bf16, const void* x, int relu_in, const void* W, const float* b, int m, int n,
                    int A, const float* tgt, const float* log_std, const float* action, const float* adv,
                    const float* old_lp, float eps, float ent_coeff, float* y, void* gx, float* gW, float* gb,
-                   float* grad_log_std, float* loss_accum);
+                   float* grad_log_std, float* loss_accum, const PhipVClip* vc);
 void phip_log_prob(const float* mu, const float* log_std, const float* action, float* out, int m, int A);
 void phip_log_prob_bwd(const float* mu, const float* log_std, const float* action, const float* grad_in,
                        float* grad_mu, float* grad_log_std, int m, int A);

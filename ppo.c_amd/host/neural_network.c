@@ -379,6 +379,7 @@ typedef struct {
     float* g; const float* w; float* gw_out;
     /* the value head carried by the hidden layer's grad_W launch (phip_x3_bwd_w_vhead) */
     const float* ypart; int slots; const float* b; const float* tgt; float* y; float* gb; float* loss;
+    const PhipVClip* vc;          /* value-loss clipping of that head (NULL: off) */
 } FoldBwd;
 
 static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int m, int want_grad_x0,
@@ -445,7 +446,7 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
             const float* h = nn->layers[i + 1].d_input;
             phip_x3_defer_reduce(want_gx);                    /* its slab reduce rides on grad_x */
             phip_x3_bwd_w_vhead(ly->d_grad_weights, ly->d_grad_biases, h, fold->g, fold->w, fold->gw_out, x, m, n, l, 1,
-                                fold->ypart, fold->slots, fold->b, fold->tgt, fold->y, fold->gb, fold->loss);
+                                fold->ypart, fold->slots, fold->b, fold->tgt, fold->y, fold->gb, fold->loss, fold->vc);
             if (want_gx) {
                 if (relu_in && !bits) die("nn_value_fold_step: the forward's ReLU′ bits are missing");
                 phip_x3_bwd_x_fold(ly->d_grad_x, NULL, act_bits(nn, i + 1), fold->g, fold->w, ly->d_weights, bits, m, n,
@@ -494,7 +495,7 @@ int nn_out_head_ok(const NeuralNetwork* nn, int head) {
 void nn_out_head_step(NeuralNetwork* nn, int head, const float* d_x, const int* d_rows, float* d_xcopy, int m,
                       int grads_zero, long reduce_extra, const float* tgt, const float* log_std, const float* action,
                       const float* adv, const float* old_lp, float eps, float ent_coeff, float* grad_log_std,
-                      float* loss_accum) {
+                      float* loss_accum, const PhipVClip* vc) {
     const int L = nn->num_layers - 1;
     nn_forward_dev_upto(nn, d_x, d_rows, d_xcopy, m, L - 1, NULL);
     nn_ensure_grad(nn, m);
@@ -506,7 +507,7 @@ void nn_out_head_step(NeuralNetwork* nn, int head, const float* d_x, const int* 
                                                                      : (const void*)ly->d_weights,
                   ly->d_biases, m, ly->input_size, ly->output_size, tgt, log_std, action, adv, old_lp, eps, ent_coeff,
                   nn->layers[L].d_input, ly->d_grad_x, ly->d_grad_weights, ly->d_grad_biases, grad_log_std,
-                  loss_accum);
+                  loss_accum, vc);
     nn->d_output = nn->layers[L].d_input;
     nn_backward_dev_top(nn, ly->d_grad_x, m, 0, 1, reduce_extra, L - 1, NULL);
 }
@@ -532,7 +533,7 @@ int nn_value_fold_ok(const NeuralNetwork* nn, int m) {
 }
 
 void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, float* d_xcopy, int m, int grads_zero,
-                        long reduce_extra, const float* tgt, float* loss_accum) {
+                        long reduce_extra, const float* tgt, float* loss_accum, const PhipVClip* vc) {
     const int L = nn->num_layers - 1;
     Layer* hid = &nn->layers[L - 2];
     Layer* out = &nn->layers[L - 1];
@@ -556,7 +557,7 @@ void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, 
      * grad_W launch (y, g, the output bias gradient, the loss) */
     nn->d_output = nn->layers[L].d_input;
     const FoldBwd fb = {g, out->d_weights, out->d_grad_weights, ypart, ff.slots, out->d_biases, tgt,
-                        nn->layers[L].d_input, out->d_grad_biases, loss_accum};
+                        nn->layers[L].d_input, out->d_grad_biases, loss_accum, vc};
     nn_backward_dev_top(nn, NULL, m, 0, 1, reduce_extra, L - 1, &fb);
 }
 

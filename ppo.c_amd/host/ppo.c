@@ -63,6 +63,12 @@ typedef struct {
      * the per-step KL history of the last update */
     float target_kl;
     PhipKlRec* kl;
+    /* PPO2 value-loss clipping (ppo_set_value_clip; 0 = off): the clip range, the caller's old values by
+     * buffer row (ppo_value_clip_old_values; NULL = the default, the update's own GAE values g_v) and the
+     * device counters {clipped rows, rows} of the value steps since the last reset */
+    float value_clip;
+    const float* v_old_user;
+    unsigned long long* vclip_counts;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -115,6 +121,7 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d->clip[0] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->kl = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+        d->vclip_counts = (unsigned long long*)phip_malloc(2 * sizeof(unsigned long long));
         ppo->dev = d;
     }
     if (B > d->cap_B) {
@@ -151,6 +158,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ph_olp); phip_free(d->ph_adv);
     phip_free(d->clip[0]); phip_free(d->clip[1]);
     phip_free(d->kl);
+    phip_free(d->vclip_counts);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -454,6 +462,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int 
     if (d->max_grad_norm > 0.f) return -1;
     /* … and they neither measure the KL nor read a stop word: target-KL early stopping takes that loop too */
     if (d->target_kl > 0.f) return -1;
+    /* … and their value heads are plain MSE: value-loss clipping takes that loop as well */
+    if (d->value_clip > 0.f) return -1;
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -599,16 +609,25 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
         phip_gather_rows(perm, c->keys_v[j], k * B, c->limit, B, c->S, c->A, buf->state_p, buf->action_p,
                          buf->logprob_p, buf->advantage_p, buf->adv_target_p, NULL, NULL, NULL, NULL, d->tgt, d->rows);
     }
+    /* value-loss clipping (off: NULL, every head runs its arithmetic and launches as before): slot i's old
+     * value is v_old[rows[i]], read inside whichever form of the head the step takes — no launch of its own.
+     * The default old values are g_v, the V(state) of every buffer row that this update's own GAE left behind:
+     * a global that any later compute_gae_cuda call overwrites, but inside ppo_update the GAE has just run and
+     * nothing rewrites it before the update returns, so it is valid for every value step.  The head is
+     * element-wise: no collective is added, and the order of collectives does not depend on the setting. */
+    PhipVClip vclip = {d->v_old_user ? d->v_old_user : g_v, rows, d->value_clip, d->vclip_counts};
+    const PhipVClip* vc = !tab && d->value_clip > 0.f ? &vclip : NULL;
     /* with a communicator: the gradients all-reduced after the backward (comm.hip: one all-reduce in
      * this stream by default; PPO_COMM_ASYNC=1 per-layer buckets on the comm stream), joined before Adam */
     if (c->fold_v && !tab) {   /* output layer + MSE folded into the last hidden layer (nn_value_fold_step) */
-        nn_value_fold_step(V, buf->state_p, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0);
+        nn_value_fold_step(V, buf->state_p, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0, vc);
     } else if (c->fuse_v) {    /* output layer + MSE + output-layer backward in one pass (out_head.hip) */
         nn_out_head_step(V, 0, buf->state_p, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, NULL, NULL,
-                         NULL, NULL, 0.f, 0.f, NULL, d->stats + 0);
+                         NULL, NULL, 0.f, 0.f, NULL, d->stats + 0, vc);
     } else {
         nn_forward_dev_rows(V, buf->state_p, rows, d->states, B);
-        phip_mse(V->d_output, tgt, B, d->gv, NULL, d->stats + 0);
+        if (vc) phip_mse_vclip(V->d_output, tgt, B, d->gv, d->stats + 0, vc);      /* the same kernel and grid */
+        else phip_mse(V->d_output, tgt, B, d->gv, NULL, d->stats + 0);
         nn_backward_dev_z(V, d->gv, B, 0, v_zero, c->comm ? 0 : -1);
     }
     phip_allreduce_join();
@@ -649,7 +668,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         nn_out_head_step(mu, 1, buf->state_p, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
                          pol->d_log_std, act, adv, olp, ppo->epsilon, ppo->ent_coeff,
-                         pol->d_log_std_grad, d->stats + 1);
+                         pol->d_log_std_grad, d->stats + 1, NULL);
     } else if (c->wide_p) { /* A = 17: policy head + output-layer backward in one pass (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         nn_policy_wide_step(mu, buf->state_p, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1,
@@ -735,6 +754,7 @@ static int step_graphs_ok(const StepCtx* c) {
     if (!(e && *e && *e != '0') || c->comm || phip_comm_world() > 1 || c->B > 2048 || c->A > 32) return 0;
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
     if (c->d->target_kl > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
+    if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
     for (int i = 0; i < 3; i++) {
@@ -1073,6 +1093,7 @@ void ppo_reset_stats(void* vppo) {
     /* norm, coef and the clipped-step counter (the 16 bytes ahead of the ticket) */
     for (int i = 0; i < 2; i++) phip_memset(d->clip[i], 0, offsetof(PhipClipRec, ticket));
     phip_memset(d->kl, 0, offsetof(PhipKlRec, ticket));      /* the head: KL, clip fraction, stop state, applied */
+    phip_memset(d->vclip_counts, 0, 2 * sizeof(unsigned long long));
     d->n_v = d->n_p = d->n_graph = 0;
 }
 
@@ -1082,8 +1103,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[17] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[19] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1100,7 +1121,52 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         v[15] = (double)r.applied;
         v[16] = r.stopped ? (double)r.stop_step : -1.0;
     }
-    for (int i = 0; i < n && i < 17; i++) out[i] = v[i];
+    if (n > 17 && d->value_clip > 0.f) {        /* value-loss clipping: zeros while it is off */
+        unsigned long long cnt[2];
+        phip_d2h(cnt, d->vclip_counts, sizeof(cnt));
+        v[17] = (double)cnt[0];
+        v[18] = (double)cnt[1];
+    }
+    for (int i = 0; i < n && i < 19; i++) out[i] = v[i];
+}
+
+/* ppo_ext.h: PPO2 value-loss clipping */
+int ppo_set_value_clip(void* vppo, float eps_v) {
+    if (isnan(eps_v)) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    d->value_clip = (eps_v > 0.f && !isinf(eps_v)) ? eps_v : 0.f;
+    return 0;
+}
+
+float ppo_get_value_clip(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo->dev ? ((PPODev*)ppo->dev)->value_clip : 0.f;
+}
+
+int ppo_value_clip_old_values(void* vppo, const float* d_v_old, long n) {
+    PPO* ppo = (PPO*)vppo;
+    if (d_v_old && n < (long)ppo->buffer->capacity) return -1;     /* indexed by buffer row: every row must exist */
+    dev_ws(ppo, 1)->v_old_user = d_v_old;
+    return 0;
+}
+
+int ppo_value_clip_head_device(const float* d_y, const float* d_v_old, const int* d_rows, const float* d_tgt, int m,
+                               float eps_v, float* d_g, double* out3) {
+    static float* loss = NULL;                    /* [0] the loss, then the two counters (8-B aligned) */
+    if (!d_y || !d_v_old || !d_tgt || !d_g || !out3 || m <= 0 || !(eps_v > 0.f)) return -1;
+    if (!loss) loss = (float*)phip_malloc(2 * sizeof(float) + 2 * sizeof(unsigned long long));
+    unsigned long long* cnt = (unsigned long long*)(loss + 2);
+    phip_memset(loss, 0, 2 * sizeof(float) + 2 * sizeof(unsigned long long));
+    const PhipVClip vc = {d_v_old, d_rows, eps_v, cnt};
+    phip_mse_vclip(d_y, d_tgt, m, d_g, loss, &vc);
+    float l = 0.f;
+    unsigned long long c[2] = {0, 0};
+    phip_d2h(&l, loss, sizeof(float));
+    phip_d2h(c, cnt, sizeof(c));
+    out3[0] = (double)l;
+    out3[1] = (double)c[0];
+    out3[2] = (double)c[1];
+    return 0;
 }
 
 /* ppo_ext.h: target-KL early stopping */

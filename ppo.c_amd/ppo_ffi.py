@@ -157,6 +157,10 @@ _SIGS = {
     "ppo_get_target_kl": (C.c_float, [_P]),
     "ppo_kl_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "ppo_policy_kl_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double)]),
+    "ppo_set_value_clip": (C.c_int, [_P, C.c_float]),
+    "ppo_get_value_clip": (C.c_float, [_P]),
+    "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
+    "ppo_value_clip_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_double)]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
