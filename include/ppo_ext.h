@@ -116,7 +116,11 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[17]=Σ clipped rows over the value steps since the last reset, out[18]=Σ rows of those steps (value-loss
  * clipping, ppo_set_value_clip: exact integer counts, under data parallelism THIS RANK's rows; both 0 while it
  * is off; callers passing n <= 17 see no change).  While value-loss clipping is on, out[0] accumulates the
- * clipped loss. */
+ * clipped loss.
+ * out[19]=the observation normaliser's running count, out[20]=elements clamped by the last update's state
+ * normalisation (an exact integer: integer atomics only; under data parallelism THIS RANK's rows),
+ * out[21]=elements it normalised (limit·S) (observation normalisation, ppo_set_obs_norm: all three 0 while it
+ * is off; callers passing n <= 19 see no change). */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
 
@@ -200,6 +204,58 @@ int    ppo_value_clip_old_values(void* ppo, const float* d_v_old, long n);
  * clipped rows, rows}; returns 0, −1 for bad arguments (a NULL array, m <= 0, eps_v not > 0); synchronises */
 int    ppo_value_clip_head_device(const float* d_y, const float* d_v_old, const int* d_rows, const float* d_tgt, int m,
                                   float eps_v, float* d_g, double* out3);
+/* Running observation normalisation (off by default; not in the reference; Stable-Baselines3 VecNormalize,
+ * CleanRL NormalizeObservation).  Per observation column j the running state is, in double, a shared count n,
+ * mean[j] and M2[j] (the sum of squared deviations; population variance M2/n, as SB3's RunningMeanStd).  The
+ * fp32 affine pair is refreshed on the device after every change of that state,
+ *     m[j] = (float)mean[j]
+ *     r[j] = (float)(1.0 / sqrt(M2[j]/n + 1e-8))        (double arithmetic, one rounding to fp32)
+ * and one element normalises, in fp32 and in this order, as
+ *     t = (x − m[j]) · r[j]
+ *     y = t < −c ? −c : (t > c ? c : t)                  (NaN propagates; c = clip, +inf = no clamp)
+ * An element counts as "clamped" when y != t and t is not NaN.  While n == 0 the map is the exact identity
+ * (m = 0, r = 1, the clamp ignored): an un-warmed normaliser never truncates raw observations.
+ * While it is on, ppo_update — stream-ordered, ahead of GAE — (1) writes norm(state[0:limit]) under the pair as
+ * it stands on entry (the pair the rollout that filled the buffer sampled under) into a shadow of `state`
+ * (capacity × S floats, allocated on first use), (2) unless frozen, folds the statistics of the RAW
+ * state[0:limit] into the running state (Chan's combine) and refreshes the pair — nothing later in that
+ * update reads it, the next rollout does — and (3) GAE, the single-workgroup / cluster phases, both loops and
+ * captured graphs read the shadow.  Of next_state only the rows GAE forwards on their own are normalised, into
+ * a compact scratch (PPO_GAE_FULL=1: every row).  The caller's buffer is never written.  The statistics are
+ * deterministic (no floating-point atomics, shifted sums in double).  ppo_rollout_device normalises each
+ * step's observations into the shadow and forwards μ from there; ppo_fill_synthetic samples from
+ * μ(norm(state)).  compute_gae_cuda / compute_gae called on their own have no PPO and stay un-normalised, and
+ * the host rollout (collect_trajectories) has no handle to the normaliser: train_ppo_epoch / eval_ppo END THE
+ * PROCESS with a message while the feature is on.  Unlike the options above this one keeps the
+ * single-workgroup / cluster phases and PPO_GRAPH=1 replay available.
+ * Under data parallelism each rank's batch triple (1 + 2S doubles; n = 0 for an empty shard) is all-gathered
+ * right behind GAE's own all-gather, combined in rank order and folded, so every rank holds bit-identical
+ * statistics: EVERY RANK MUST HOLD THE SAME on/off AND frozen SETTING, or the ranks issue different sequences
+ * of collectives.  While it is on, ppo_param_hash and the replica check also cover the 1 + 2S doubles.
+ * Not part of a checkpoint (save_ppo keeps the reference's byte layout): save and restore the state with
+ * ppo_obs_norm_get_state / _set_state and set the option again after load_ppo.  Turning it off keeps the state.
+ * clip > 0: on (+inf: normalise, never clamp); <= 0: off.  Returns 0, or −1 for NaN (setting unchanged). */
+int    ppo_set_obs_norm(void* ppo, float clip);
+float  ppo_get_obs_norm(void* ppo);                       /* 0 when off */
+/* evaluation: normalise, never fold; returns the previous value */
+int    ppo_obs_norm_freeze(void* ppo, int frozen);
+/* fold the device buffer's current rows (state[0:limit]) now — warm-up after a random rollout; the collective
+ * included at world > 1 (every rank calls it); asynchronous.  Returns 0, or −1 when off or frozen */
+int    ppo_obs_norm_fold_buffer(void* ppo);
+/* The five below synchronise.  out = {n, mean[S], M2[S]}; returns 1 + 2S, or −1 when n (the doubles out
+ * holds) is too small */
+int    ppo_obs_norm_get_state(void* ppo, double* out, long n);
+/* returns 0, or −1 (state unchanged) for n != 1 + 2S, a negative count or M2, NaN or infinity */
+int    ppo_obs_norm_set_state(void* ppo, const double* in, long n);
+/* the fp32 pair in use, to the host (either may be NULL); −1 when S is not the buffer's state size */
+int    ppo_obs_norm_affine(void* ppo, float* mean, float* rstd, int S);
+/* the update's normalisation kernel on caller-supplied device rows, m rows × S, under the current pair and
+ * clip; d_out may be d_in.  Nothing is counted: ppo_read_stats out[20] / out[21] keep describing the last
+ * update.  Returns 0, or −1 while the feature is off or for bad arguments */
+int    ppo_obs_normalize_device(void* ppo, const float* d_in, float* d_out, long m);
+/* the update's statistics kernel alone: d_x [n, S] → out = {n, mean[S], M2[S]} (host, 1 + 2S doubles);
+ * returns 0, −1 for bad arguments */
+int    ppo_obs_stats_device(const float* d_x, long n, int S, double* out);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

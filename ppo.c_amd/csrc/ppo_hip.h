@@ -352,6 +352,23 @@ void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global);
 /* the host waits for the launches issued so far on the current stream only (an event recorded there) */
 void phip_stream_wait(void);
 
+/* ---------------- observation normalisation (obsnorm.hip) ---------------- */
+/* A triple is 1 + 2S device doubles {n, mean[S], M2[S]} (M2: the sum of squared deviations per column).
+ * triple ← the exact-in-double statistics of x [n, S] (n = 0: the zero triple); deterministic (no
+ * floating-point atomics, partials per workgroup folded in a fixed order, shifted sums); two launches */
+void phip_obs_stats(const float* x, long n, int S, double* triple);
+/* `count` triples (consecutive, rank order; empty ones skipped) combined, then folded into `run` (Chan) */
+void phip_obs_fold(const double* triples, int count, int S, double* run);
+/* the fp32 affine pair of a running triple: m = (float)mean, r = (float)(1/sqrt(M2/n + 1e-8)); n = 0: (0, 1) */
+void phip_obs_affine(const double* run, int S, float* m, float* r);
+/* y[0:n] ← clamp((x − m)·r, ±clip) per column (y may be x); run[0] == 0: no clamp; counts (may be NULL):
+ * [0] += clamped elements, [1] += n·S (integer atomics) */
+void phip_obs_normalize(const float* x, float* y, long n, int S, const float* m, const float* r, float clip,
+                        const double* run, unsigned long long* counts);
+/* dst[dst_rows[i]] ← the same map of src[src_rows[i]], i < rows (a NULL list: the identity) */
+void phip_obs_normalize_rows(const float* src, const int* src_rows, float* dst, const int* dst_rows, int rows, int S,
+                             const float* m, const float* r, float clip, const double* run);
+
 /* ---------------- sampling / synthetic data (sample.hip) ---------------- */
 void phip_sample(const float* mu, const float* log_std, float* action, float* logprob, int m, int A,
                  uint64_t seed, uint64_t offset);

@@ -69,6 +69,22 @@ typedef struct {
     float value_clip;
     const float* v_old_user;
     unsigned long long* vclip_counts;
+    /* running observation normalisation (ppo_set_obs_norm; 0 = off; csrc/obsnorm.hip): the clamp, the freeze
+     * flag, the running triple {n, mean[S], M2[S]} in double and its fp32 affine pair (m, r = m + S), the
+     * shadow of `state` every consumer inside the update reads (capacity × S), the compact scratch of the
+     * next_state rows GAE forwards on their own, this rank's batch triple and the all-gathered ones, and the
+     * counters {clamped, normalised} of the last state normalisation.  All NULL until first used. */
+    float obs_clip;
+    int obs_frozen;
+    double* obs_run;
+    float* obs_m;
+    float* obs_shadow;
+    float* obs_next;
+    long obs_next_cap;
+    double* obs_batch;
+    double* obs_all;
+    int obs_all_world;
+    unsigned long long* obs_counts;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -159,6 +175,8 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->clip[0]); phip_free(d->clip[1]);
     phip_free(d->kl);
     phip_free(d->vclip_counts);
+    phip_free(d->obs_run); phip_free(d->obs_m); phip_free(d->obs_shadow); phip_free(d->obs_next);
+    phip_free(d->obs_batch); phip_free(d->obs_all); phip_free(d->obs_counts);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -239,26 +257,102 @@ static int gae_full_forwards(void) {
     return e && *e && *e != '0';
 }
 
-void ppo_gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda) {
+/* ------------------------------------------------------------------ */
+/* running observation normalisation (ppo_ext.h ppo_set_obs_norm)      */
+/* ------------------------------------------------------------------ */
+static int obs_on(const PPODev* d) { return d && d->obs_clip > 0.f; }
+
+/* the running triple and its affine pair (the identity until something is folded or set) */
+static void obs_ws(PPO* ppo, PPODev* d) {
+    if (d->obs_run) return;
+    const int S = ppo->buffer->state_size;
+    d->obs_run = (double*)phip_malloc(sizeof(double) * (size_t)(1 + 2L * S));
+    d->obs_batch = (double*)phip_malloc(sizeof(double) * (size_t)(1 + 2L * S));
+    d->obs_m = (float*)phip_malloc(sizeof(float) * 2 * (size_t)S);
+    d->obs_counts = (unsigned long long*)phip_malloc(2 * sizeof(unsigned long long));
+    phip_obs_affine(d->obs_run, S, d->obs_m, d->obs_m + S);
+}
+
+static float* obs_shadow(PPO* ppo, PPODev* d) {
+    obs_ws(ppo, d);
+    if (!d->obs_shadow)
+        d->obs_shadow = (float*)phip_malloc(sizeof(float) * (size_t)ppo->buffer->capacity * ppo->buffer->state_size);
+    return d->obs_shadow;
+}
+
+/* this rank's batch triple (d->obs_batch, already queued) into the running triple: all-gathered and combined
+ * in rank order at world > 1, so every rank folds the same bits; then the affine pair is refreshed */
+static void obs_fold_batch(PPO* ppo, PPODev* d) {
+    const int S = ppo->buffer->state_size;
+    const int world = phip_comm_world();
+    if (world > 1) {
+        if (world > d->obs_all_world) {
+            phip_free(d->obs_all);
+            d->obs_all = (double*)phip_malloc(sizeof(double) * (size_t)(1 + 2L * S) * (size_t)world);
+            d->obs_all_world = world;
+        }
+        phip_allgather_f64(d->obs_batch, d->obs_all, 1 + 2L * S);
+        phip_obs_fold(d->obs_all, world, S, d->obs_run);
+    } else {
+        phip_obs_fold(d->obs_batch, 1, S, d->obs_run);
+    }
+    phip_obs_affine(d->obs_run, S, d->obs_m, d->obs_m + S);
+}
+
+/* steps 1 and 2 of the update while the feature is on, stream-ordered ahead of GAE: the shadow of
+ * state[0:limit] under the affine pair as it stands (the pair the rollout sampled under), and — unless
+ * frozen — this rank's batch triple over the RAW rows; gae_device folds it behind its own all-gather.
+ * Returns the shadow. */
+static const float* obs_prepare(PPO* ppo, PPODev* d, int limit) {
+    TrajectoryBuffer* buf = ppo->buffer;
+    const int S = buf->state_size;
+    float* sh = obs_shadow(ppo, d);
+    phip_memset(d->obs_counts, 0, 2 * sizeof(unsigned long long));
+    phip_obs_normalize(buf->state_p, sh, limit, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run, d->obs_counts);
+    if (!d->obs_frozen) phip_obs_stats(buf->state_p, limit, S, d->obs_batch);
+    return sh;
+}
+
+/* the next_state rows listed in `rows` (NULL: the first m rows) normalised into the compact scratch */
+static const float* obs_next_rows(PPODev* d, TrajectoryBuffer* b, const int* rows, int m) {
+    const int S = b->state_size;
+    if (m > d->obs_next_cap) {
+        phip_free(d->obs_next);
+        d->obs_next = (float*)phip_malloc(sizeof(float) * (size_t)m * S);
+        d->obs_next_cap = m;
+    }
+    phip_obs_normalize_rows(b->next_state_p, rows, d->obs_next, NULL, m, S, d->obs_m, d->obs_m + S, d->obs_clip,
+                            d->obs_run);
+    return d->obs_next;
+}
+
+/* ppo: NULL (compute_gae_cuda / compute_gae: no normaliser, raw states), or the PPO whose update runs this
+ * GAE with observation normalisation on (obs_prepare has run): the forwards read the shadow, the own
+ * next_state rows are normalised into a compact scratch, and the batch triple is folded behind the scan */
+static void gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda, PPO* ppo) {
+    PPODev* od = ppo ? (PPODev*)ppo->dev : NULL;
+    const float* state = od ? od->obs_shadow : b->state_p;
     const int n = b->full ? b->capacity : b->idx;
     g_gae_own_rows = 0;                     /* an empty buffer reports no own-row forward */
     g_gae_n = n;
     ensure_gae_ws(n);
     if (n > 0 && gae_full_forwards()) {     /* the reference's two full forwards (ppo.cu:333-336) */
-        nn_forward_dev(V, b->next_state_p, n);
+        nn_forward_dev(V, od ? obs_next_rows(od, b, NULL, n) : b->next_state_p, n);
         phip_d2d(g_vn, V->d_output, sizeof(float) * (size_t)n);
         g_gae_own_rows = n;
-        nn_forward_dev(V, b->state_p, n);
+        nn_forward_dev(V, state, n);
         phip_d2d(g_v, V->d_output, sizeof(float) * (size_t)n);
     } else if (n > 0) {
         /* V(state) once; V(next_state[t]) = V(state[t+1]) wherever the rows are bitwise equal
          * (every transition that did not end an episode); the rest get their own forward */
-        nn_forward_dev(V, b->state_p, n);
+        nn_forward_dev(V, state, n);
         phip_d2d(g_v, V->d_output, sizeof(float) * (size_t)n);
+        /* the raw rows are compared: equal raw rows give equal normalised rows */
         const int own = phip_next_value_map(b->next_state_p, b->state_p, g_v, g_vn, g_own, n, V->layers[0].input_size);
         g_gae_own_rows = own;
         if (own > 0) {
-            nn_forward_dev_rows(V, b->next_state_p, g_own, NULL, own);
+            if (od) nn_forward_dev(V, obs_next_rows(od, b, g_own, own), own);
+            else nn_forward_dev_rows(V, b->next_state_p, g_own, NULL, own);
             phip_scatter_values(g_vn, g_own, V->d_output, own);
         }
     }
@@ -269,7 +363,14 @@ void ppo_gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float la
         phip_allgather_f64(g_welford, g_welford_all, 3);
         phip_welford_combine(g_welford_all, world, g_welford);
     }
+    /* right behind the Welford all-gather and ahead of the update's empty-shard agreement: every rank
+     * reaches this collective (an empty shard contributes the zero triple) */
+    if (od && !od->obs_frozen) obs_fold_batch(ppo, od);
     phip_normalize(b->advantage_p, n, g_welford, g_adv_stats);
+}
+
+void ppo_gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda) {
+    gae_device(V, b, gamma, lambda, NULL);
 }
 
 long ppo_gae_state(double* welford, float* v, float* v_next, long n) {
@@ -452,7 +553,9 @@ static const int* tiny_perms(PPO* ppo, PPODev* d, int shuffle_mode, int n_epochs
     return perms;
 }
 
-static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int n_epochs_value, int shuffle_mode) {
+/* state: the rows the phases read — the buffer's, or their normalised shadow */
+static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n_epochs_policy, int n_epochs_value,
+                           int shuffle_mode) {
     TrajectoryBuffer* buf = ppo->buffer;
     const int limit = buf->full ? buf->capacity : buf->idx;
     const int num_batches = buf->capacity / B;
@@ -482,7 +585,7 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, int B, int n_epochs_policy, int 
     np.v_ls = ppo->adam_entropy->v;
     PhipTinyPhase ph;
     memset(&ph, 0, sizeof(ph));
-    ph.state = buf->state_p; ph.action = buf->action_p; ph.logprob = buf->logprob_p;
+    ph.state = state; ph.action = buf->action_p; ph.logprob = buf->logprob_p;
     ph.adv = buf->advantage_p; ph.adv_target = buf->adv_target_p;
     ph.limit = limit; ph.B = B; ph.num_batches = num_batches;
     ph.b1 = 0.9f; ph.b2 = 0.999f; ph.eps = ppo->epsilon; ph.ent_coeff = ppo->ent_coeff;
@@ -582,6 +685,7 @@ typedef struct {
     int K;                        /* requested steps per graph (PPO_GRAPH_STEPS, default 16) */
     long Kv, Kp;                  /* steps per graph as captured */
     int phg;                      /* the phases' inputs were gathered up front (PPODev ph_*) */
+    const float* state;           /* layer 0's rows: buf->state_p, or its normalised shadow (obs_prepare) */
 } StepCtx;
 
 /* value step iv (tab: the step-table form captured into a graph: gather and Adam read their
@@ -606,7 +710,7 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
         const int* perm = c->perms_v ? c->perms_v + (long)j * c->limit : NULL;
         /* gather fused into layer 0: the kernel emits row indices (+ targets); the layer-0 GEMM
          * reads the buffer rows through them and leaves the gathered copy for its grad_W */
-        phip_gather_rows(perm, c->keys_v[j], k * B, c->limit, B, c->S, c->A, buf->state_p, buf->action_p,
+        phip_gather_rows(perm, c->keys_v[j], k * B, c->limit, B, c->S, c->A, c->state, buf->action_p,
                          buf->logprob_p, buf->advantage_p, buf->adv_target_p, NULL, NULL, NULL, NULL, d->tgt, d->rows);
     }
     /* value-loss clipping (off: NULL, every head runs its arithmetic and launches as before): slot i's old
@@ -620,12 +724,12 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
     /* with a communicator: the gradients all-reduced after the backward (comm.hip: one all-reduce in
      * this stream by default; PPO_COMM_ASYNC=1 per-layer buckets on the comm stream), joined before Adam */
     if (c->fold_v && !tab) {   /* output layer + MSE folded into the last hidden layer (nn_value_fold_step) */
-        nn_value_fold_step(V, buf->state_p, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0, vc);
+        nn_value_fold_step(V, c->state, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0, vc);
     } else if (c->fuse_v) {    /* output layer + MSE + output-layer backward in one pass (out_head.hip) */
-        nn_out_head_step(V, 0, buf->state_p, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, NULL, NULL,
+        nn_out_head_step(V, 0, c->state, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, NULL, NULL,
                          NULL, NULL, 0.f, 0.f, NULL, d->stats + 0, vc);
     } else {
-        nn_forward_dev_rows(V, buf->state_p, rows, d->states, B);
+        nn_forward_dev_rows(V, c->state, rows, d->states, B);
         if (vc) phip_mse_vclip(V->d_output, tgt, B, d->gv, d->stats + 0, vc);      /* the same kernel and grid */
         else phip_mse(V->d_output, tgt, B, d->gv, NULL, d->stats + 0);
         nn_backward_dev_z(V, d->gv, B, 0, v_zero, c->comm ? 0 : -1);
@@ -659,23 +763,23 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     } else {
         const int j = (int)(ip / c->num_batches), k = (int)(ip % c->num_batches);
         const int* perm = c->perms_p ? c->perms_p + (long)j * c->limit : NULL;
-        phip_gather_rows(perm, c->keys_p[j], k * B, c->limit, B, c->S, A, buf->state_p, buf->action_p,
+        phip_gather_rows(perm, c->keys_p[j], k * B, c->limit, B, c->S, A, c->state, buf->action_p,
                          buf->logprob_p, buf->advantage_p, buf->adv_target_p, NULL, d->actions, d->old_lp, d->adv,
                          NULL, d->rows_p);
     }
     /* μ grads + (top bucket) the log σ gradient behind them */
     if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
-        nn_out_head_step(mu, 1, buf->state_p, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
+        nn_out_head_step(mu, 1, c->state, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
                          pol->d_log_std, act, adv, olp, ppo->epsilon, ppo->ent_coeff,
                          pol->d_log_std_grad, d->stats + 1, NULL);
     } else if (c->wide_p) { /* A = 17: policy head + output-layer backward in one pass (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
-        nn_policy_wide_step(mu, buf->state_p, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1,
+        nn_policy_wide_step(mu, c->state, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1,
                             pol->d_log_std, act, adv, olp, ppo->epsilon, ppo->ent_coeff,
                             pol->d_log_std_grad, d->stats + 1);
     } else {
-        nn_forward_dev_rows(mu, buf->state_p, rows, d->states_p, B);
+        nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
         phip_policy_head(mu->d_output, pol->d_log_std, act, adv, olp, B, A, ppo->epsilon,
                          ppo->ent_coeff, d->gmu, pol->d_log_std_grad, d->stats + 1, *ls_zero);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
@@ -885,7 +989,7 @@ static void phase_gather(StepCtx* c) {
             const long o = j * per;
             if (steps * B >= (1L << 31)) die("ppo_update: a phase epoch exceeds 2^31 rows");
             phip_gather_rows(perms ? perms + j * c->limit : NULL, keys[j], 0, c->limit, (int)(steps * B), c->S, c->A,
-                             buf->state_p, buf->action_p, buf->logprob_p, buf->advantage_p, buf->adv_target_p, NULL,
+                             c->state, buf->action_p, buf->logprob_p, buf->advantage_p, buf->adv_target_p, NULL,
                              ph ? d->ph_act + o * A : NULL, ph ? d->ph_olp + o : NULL, ph ? d->ph_adv + o : NULL,
                              ph ? NULL : d->ph_tgt + o, d->ph_rows[ph] + o);
         }
@@ -896,9 +1000,15 @@ static void phase_gather(StepCtx* c) {
 /* the replica check's parameter spans in HBM: μ, log σ, V */
 static void replica_hash(PPO* ppo) {
     GaussianPolicy* pol = ppo->policy;
-    const float* spans[3] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params};
-    const long lens[3] = {pol->mu->num_params, pol->action_size, ppo->V->num_params};
-    phip_param_hash(spans, lens, 3);
+    /* … and, while observation normalisation is on, the running triple's 1 + 2S doubles as 32-bit words
+     * (off: the three spans, the hash as before) */
+    PPODev* d = (PPODev*)ppo->dev;
+    const int obs = obs_on(d);
+    if (obs) obs_ws(ppo, d);      /* on but never folded or set: the zero triple, hashed like a peer's zeros */
+    const float* spans[4] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params, obs ? (const float*)d->obs_run : NULL};
+    const long lens[4] = {pol->mu->num_params, pol->action_size, ppo->V->num_params,
+                          obs ? 2 * (1 + 2L * ppo->buffer->state_size) : 0};
+    phip_param_hash(spans, lens, obs ? 4 : 3);
 }
 
 unsigned long long ppo_param_hash(void* vppo) {
@@ -965,14 +1075,19 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     GaussianPolicy* pol = ppo->policy;
     NeuralNetwork* mu = pol->mu;
 
-    ppo_gae_device(V, buf, gamma, ppo->lambda);
+    /* observation normalisation (off: nothing launched, every consumer reads buf->state_p as before): the
+     * shadow under the affine pair on entry and the batch triple first; GAE, the phases and both loops then
+     * read the shadow.  The caller's buffer is never written. */
+    const int obs = obs_on(d);
+    const float* state = obs ? obs_prepare(ppo, d, limit) : buf->state_p;
+    gae_device(V, buf, gamma, ppo->lambda, obs ? ppo : NULL);
     /* D19: an empty buffer (idx = 0, not full) has nothing to train on; the reference would divide
      * by zero (rand() % 0 in shuffle_buffer, % limit in get_batch) — here the update ends after GAE.
      * At world > 1 the ranks agree first (min over ranks): one empty shard ends the update on every
      * rank, so no rank waits in a gradient all-reduce the others never issue. */
     if ((world > 1 ? phip_comm_min_i32(limit) : limit) <= 0) return;
 
-    if (ppo_update_tiny(ppo, d, B, n_epochs_policy, n_epochs_value, shuffle_mode) == 0) return;
+    if (ppo_update_tiny(ppo, d, state, B, n_epochs_policy, n_epochs_value, shuffle_mode) == 0) return;
 
     /* The policy loop reads only the buffer and the advantages — nothing the value loop writes —
      * so on one GPU the two run concurrently: value steps on libppo's stream, policy steps on its
@@ -996,7 +1111,7 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const int fuse_p = nn_out_head_ok(mu, 1);
     StepCtx c = {ppo, d, B, S, A, limit, num_batches, comm, nn_out_head_ok(V, 0), fuse_p,
                  !fuse_p && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
-                 NULL, NULL, NULL, NULL, 16, 1, 1, 0};
+                 NULL, NULL, NULL, NULL, 16, 1, 1, 0, state};
     {
         const char* ge = getenv("PPO_GRAPH_STEPS");
         if (ge && atoi(ge) > 0) c.K = atoi(ge);
@@ -1103,8 +1218,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[19] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[22] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1127,7 +1242,112 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         v[17] = (double)cnt[0];
         v[18] = (double)cnt[1];
     }
-    for (int i = 0; i < n && i < 19; i++) out[i] = v[i];
+    if (n > 19 && obs_on(d) && d->obs_run) {    /* observation normalisation: zeros while it is off */
+        unsigned long long cnt[2];
+        phip_d2h(&v[19], d->obs_run, sizeof(double));
+        phip_d2h(cnt, d->obs_counts, sizeof(cnt));
+        v[20] = (double)cnt[0];
+        v[21] = (double)cnt[1];
+    }
+    for (int i = 0; i < n && i < 22; i++) out[i] = v[i];
+}
+
+/* ppo_ext.h: running observation normalisation */
+int ppo_set_obs_norm(void* vppo, float clip) {
+    if (isnan(clip)) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    d->obs_clip = clip > 0.f ? clip : 0.f;                   /* +inf stays: normalise, never clamp */
+    return 0;
+}
+
+float ppo_get_obs_norm(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo->dev ? ((PPODev*)ppo->dev)->obs_clip : 0.f;
+}
+
+int ppo_obs_norm_freeze(void* vppo, int frozen) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    const int was = d->obs_frozen;
+    d->obs_frozen = frozen != 0;
+    return was;
+}
+
+int ppo_obs_norm_fold_buffer(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    TrajectoryBuffer* buf = ppo->buffer;
+    if (!obs_on(d) || d->obs_frozen) return -1;
+    if (!buf->on_device) die("ppo_obs_norm_fold_buffer: buffer must be device-resident");
+    obs_ws(ppo, d);
+    phip_obs_stats(buf->state_p, buf->full ? buf->capacity : buf->idx, buf->state_size, d->obs_batch);
+    obs_fold_batch(ppo, d);
+    return 0;
+}
+
+int ppo_obs_norm_get_state(void* vppo, double* out, long n) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    const long len = 1 + 2L * ppo->buffer->state_size;
+    if (!out || n < len) return -1;
+    phip_sync();
+    if (d->obs_run) phip_d2h(out, d->obs_run, sizeof(double) * (size_t)len);
+    else memset(out, 0, sizeof(double) * (size_t)len);
+    return (int)len;
+}
+
+int ppo_obs_norm_set_state(void* vppo, const double* in, long n) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    const int S = ppo->buffer->state_size;
+    if (!in || n != 1 + 2L * S || !(in[0] >= 0.0) || isinf(in[0])) return -1;
+    for (int j = 0; j < S; j++)
+        if (!isfinite(in[1 + j]) || !(in[1 + S + j] >= 0.0) || isinf(in[1 + S + j])) return -1;
+    obs_ws(ppo, d);
+    phip_sync();                                             /* nothing queued still reads the old pair */
+    phip_h2d(d->obs_run, in, sizeof(double) * (size_t)n);
+    phip_obs_affine(d->obs_run, S, d->obs_m, d->obs_m + S);
+    phip_sync();
+    return 0;
+}
+
+int ppo_obs_norm_affine(void* vppo, float* mean, float* rstd, int S) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    if (S != ppo->buffer->state_size) return -1;
+    obs_ws(ppo, d);
+    phip_sync();
+    if (mean) phip_d2h(mean, d->obs_m, sizeof(float) * (size_t)S);
+    if (rstd) phip_d2h(rstd, d->obs_m + S, sizeof(float) * (size_t)S);
+    return 0;
+}
+
+int ppo_obs_normalize_device(void* vppo, const float* d_in, float* d_out, long m) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = dev_ws(ppo, 1);
+    const int S = ppo->buffer->state_size;
+    if (!obs_on(d) || !d_in || !d_out || m < 0) return -1;
+    obs_ws(ppo, d);
+    /* uncounted: ppo_read_stats out[20] / out[21] keep describing the last update */
+    phip_obs_normalize(d_in, d_out, m, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run, NULL);
+    phip_sync();
+    return 0;
+}
+
+int ppo_obs_stats_device(const float* d_x, long n, int S, double* out) {
+    /* one grow-only scratch per process, never freed (as g_v / g_welford above): libppo's entry points are
+     * called from one host thread and launch on libppo's stream, and this one synchronises before it returns */
+    static double* triple = NULL;
+    static int cap_S = 0;
+    if (!out || n < 0 || S <= 0 || (!d_x && n > 0)) return -1;
+    if (S > cap_S) {
+        phip_free(triple);
+        triple = (double*)phip_malloc(sizeof(double) * (size_t)(1 + 2L * S));
+        cap_S = S;
+    }
+    phip_obs_stats(d_x, n, S, triple);
+    phip_sync();
+    phip_d2h(out, triple, sizeof(double) * (size_t)(1 + 2L * S));
+    return 0;
 }
 
 /* ppo_ext.h: PPO2 value-loss clipping */
@@ -1242,6 +1462,10 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
 /* ppo.cu:451-558 */
 void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, int n_epochs_policy,
                      int n_epochs_value) {
+    /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
+    if (obs_on((PPODev*)ppo->dev))
+        die("train_ppo_epoch: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout; "
+            "use ppo_rollout_device + ppo_update");
     for (int i = 0; i < steps_per_epoch / ppo->buffer->capacity; i++) {
         collect_trajectories(ppo->buffer, env, ppo->policy, ppo->buffer->capacity);
         buffer_to_device(ppo->buffer);
@@ -1254,6 +1478,8 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
+    if (obs_on((PPODev*)ppo->dev))
+        die("eval_ppo: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout");
     reset_buffer(ppo->buffer);
     collect_trajectories(ppo->buffer, env, ppo->policy, steps);
     TrajectoryBuffer* b = ppo->buffer;
@@ -1311,9 +1537,15 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     GaussianPolicy* pol = ppo->policy;
     phip_env_first_obs(env_kind, d->env_state, b->d_state_p, E, T, S);
+    /* observation normalisation: each step's E rows are normalised through the row map into the shadow (the
+     * same rows there) and μ is forwarded from it; the buffer keeps the raw observations */
+    float* shadow = obs_on(d) ? obs_shadow(ppo, d) : NULL;
     for (int t = 0; t < T; t++) {
         const int* rows = d->ro_rows + (long)t * E;
-        nn_forward_dev_rows(pol->mu, b->d_state_p, rows, NULL, E);
+        if (shadow)
+            phip_obs_normalize_rows(b->d_state_p, rows, shadow, rows, E, S, d->obs_m, d->obs_m + S, d->obs_clip,
+                                    d->obs_run);
+        nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
         phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key,
                          d->ro_step++);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
@@ -1339,7 +1571,14 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     phip_link_next_state(b->d_next_state_p, b->d_state_p, (const uint8_t*)b->d_terminated_p, n_envs, horizon, S,
                          s0 ^ 0x3);
     phip_fill_normal(b->d_reward_p, N, s0 ^ 0x4, 0.1f);
-    ppo_sample_action_device(ppo->policy, b->d_state_p, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
+    /* observation normalisation: the actions are sampled from μ(norm(state)) */
+    float* obs = b->d_state_p;
+    if (ppo->dev && obs_on((PPODev*)ppo->dev)) {
+        PPODev* d = (PPODev*)ppo->dev;
+        obs = obs_shadow(ppo, d);
+        phip_obs_normalize(b->d_state_p, obs, N, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run, NULL);
+    }
+    ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
     phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
     b->idx = (int)(N % b->capacity);

@@ -161,6 +161,15 @@ _SIGS = {
     "ppo_get_value_clip": (C.c_float, [_P]),
     "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
     "ppo_value_clip_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_double)]),
+    "ppo_set_obs_norm": (C.c_int, [_P, C.c_float]),
+    "ppo_get_obs_norm": (C.c_float, [_P]),
+    "ppo_obs_norm_freeze": (C.c_int, [_P, C.c_int]),
+    "ppo_obs_norm_fold_buffer": (C.c_int, [_P]),
+    "ppo_obs_norm_get_state": (C.c_int, [_P, C.POINTER(C.c_double), C.c_long]),
+    "ppo_obs_norm_set_state": (C.c_int, [_P, C.POINTER(C.c_double), C.c_long]),
+    "ppo_obs_norm_affine": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ppo_obs_normalize_device": (C.c_int, [_P, _P, _P, C.c_long]),
+    "ppo_obs_stats_device": (C.c_int, [_P, C.c_long, C.c_int, C.POINTER(C.c_double)]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
