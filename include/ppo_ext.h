@@ -120,7 +120,11 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[19]=the observation normaliser's running count, out[20]=elements clamped by the last update's state
  * normalisation (an exact integer: integer atomics only; under data parallelism THIS RANK's rows),
  * out[21]=elements it normalised (limit·S) (observation normalisation, ppo_set_obs_norm: all three 0 while it
- * is off; callers passing n <= 19 see no change). */
+ * is off; callers passing n <= 19 see no change).
+ * out[22]=the reward normaliser's running count, out[23]=rewards clamped by the last update's scaling (an exact
+ * integer: integer atomics only; under data parallelism THIS RANK's rows), out[24]=rewards it scaled (limit)
+ * (reward normalisation, ppo_set_reward_norm: all three 0 while it is off; callers passing n <= 22 see no
+ * change). */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
 
@@ -256,6 +260,76 @@ int    ppo_obs_normalize_device(void* ppo, const float* d_in, float* d_out, long
 /* the update's statistics kernel alone: d_x [n, S] → out = {n, mean[S], M2[S]} (host, 1 + 2S doubles);
  * returns 0, −1 for bad arguments */
 int    ppo_obs_stats_device(const float* d_x, long n, int S, double* out);
+/* Running return-based reward normalisation (off by default; not in the reference; the reward half of
+ * Stable-Baselines3's VecNormalize): rewards are divided by the running standard deviation of the discounted
+ * return and clamped; they are not centred.  Per PPO the running state is three doubles {n, mean, M2} of the
+ * discounted returns (population variance M2/n, as SB3's RunningMeanStd; the mean is kept only because Chan's
+ * combine needs it).  With g = (double)gamma — the gamma argument of this ppo_update — and the rows of
+ * reward[0:limit] in buffer order,
+ *     k_i = !(terminated[i] || truncated[i])                 (k_{-1} = 0)
+ *     R_i = (double)r_i + g · (k_{i-1} · R_{i-1} + c_i)      (double throughout)
+ * where c_i is a carried return, non-zero only at the first row of an environment's segment (below) and 0 for
+ * every buffer ppo_rollout_device did not fill.  While it is on, ppo_update — stream-ordered, ahead of GAE's
+ * forwards, no read back to the host —
+ *   1. scans the RAW rewards into R_0 … R_{limit−1} and their exact-in-double triple (deterministic: no
+ *      floating-point atomics, per-workgroup partials folded in a fixed order; csrc/retnorm.hip);
+ *   2. unless frozen, folds that triple into the running state (Chan's combine);
+ *   3. refreshes the scale  s = (float)(1.0 / sqrt(M2/n + 1e-8))  (double arithmetic, one rounding to fp32;
+ *      n == 0: s = 1 and the clamp ignored, the exact identity, as for observations);
+ *   4. writes a shadow of the rewards (capacity floats, allocated on first use), per element in fp32 and in
+ *      this order:  t = r · s;  y = t < −c ? −c : (t > c ? c : t)  (NaN propagates; an element counts as
+ *      "clamped" when y != t and t is not NaN);
+ *   5. points GAE at the shadow.  The caller's buffer is never written: train_ppo_epoch's printed J / R stay
+ *      raw, and a second update over the same buffer does not scale twice.
+ * ORDER: this option folds first and scales with the refreshed state, as SB3 does (the step's own return
+ * enters the variance before its reward is divided), so the first update already sees scaled rewards.
+ * Observation normalisation does the opposite — it normalises under the pair on entry and folds afterwards —
+ * because a rollout sampled under that pair; nothing samples under the reward scale.  While frozen the update
+ * scales under the state as it stands and neither scans nor folds.
+ * Only GAE reads rewards, so the minibatch loops, the single-workgroup / cluster phases and PPO_GRAPH=1 replay
+ * all stay available.  compute_gae_cuda / compute_gae called on their own have no PPO and stay raw.
+ * train_ppo_epoch keeps working: its buffer is scanned with no carry (collect_trajectories resets the
+ * environment at each call).
+ * CARRY ACROSS DEVICE ROLLOUTS: ppo_rollout_device lays transition (e, t) at row e·T + t and ends every segment
+ * with truncated = 1 although episodes continue across calls.  It records cont[e] = 1 when environment e was
+ * not reset after its last step (whether or not the feature is on, so it may be turned on between a rollout
+ * and its update).  The scan of such a buffer (limit == E·T) adds g·carry_in[e] at row e·T — c_{e·T} above —
+ * and writes carry_out[e] = cont[e] ? R_{e·T+T−1} : 0.  Carries change at rollout time only: at the start of
+ * ppo_rollout_device carry_out becomes carry_in if an update has scanned the rollout just before it, otherwise
+ * carry_in is zeroed; an environment reset (a change of n_envs or env_kind) zeroes it.  Repeated updates over
+ * one rollout read the same carry_in: idempotent apart from the fold.  ppo_fill_synthetic, train_ppo_epoch and
+ * a limit that is not E·T mean "not rollout-laid": one stream, no carry.  (A buffer the caller refills through
+ * the device pointers after a rollout keeps the rollout's layout and carry.)  Carries are per rank, not hashed.
+ * Under data parallelism each rank's 3-double batch triple (the zero triple for an empty shard) is all-gathered
+ * at one fixed point ahead of GAE's forwards — every rank reaches it, empty shard or not — combined in rank
+ * order and folded, so every rank holds bit-identical state: EVERY RANK MUST HOLD THE SAME on/off AND frozen
+ * SETTING, or the ranks issue different sequences of collectives.  While it is on, ppo_param_hash and the
+ * replica check also cover the three doubles (a function of the state only).  Loopback caveat
+ * (PPO_COMM_LOOPBACK=k): the loopback all-gather hands the peers registered by ppo_comm_loopback_peers to any
+ * gather of their length, and this triple has the length of GAE's Welford triple — registered peers would feed
+ * both gathers, so do not combine them with this option.
+ * Not part of a checkpoint: save and restore the state with ppo_reward_norm_get_state / _set_state.  Turning
+ * it off keeps the state.
+ * clip > 0: on (+inf: scale, never clamp); <= 0: off.  Returns 0, or −1 for NaN (setting unchanged). */
+int    ppo_set_reward_norm(void* ppo, float clip);
+float  ppo_get_reward_norm(void* ppo);                    /* 0 when off */
+/* scale, never scan or fold; returns the previous value */
+int    ppo_reward_norm_freeze(void* ppo, int frozen);
+/* The three below synchronise.  out3 = {n, mean, M2} */
+void   ppo_reward_norm_get_state(void* ppo, double* out3);
+/* returns 0, or −1 (state unchanged) for a negative count or M2, NaN or infinity */
+int    ppo_reward_norm_set_state(void* ppo, const double* in3);
+/* the fp32 scale s in use */
+float  ppo_reward_norm_scale(void* ppo);
+/* the update's scan alone, on caller-supplied device arrays (synchronises).  seg_len = 0: one stream, no carry
+ * (d_carry_in / d_cont / d_carry_out unused, may be NULL); seg_len = T > 0: n must be a multiple of T, row e·T
+ * takes d_carry_in[e] and d_carry_out[e] (may be NULL) = d_cont[e] ? R_{e·T+T−1} : 0.  d_returns (may be
+ * NULL) ← the n returns in double; out3 (host) ← their triple {n, mean, M2}.  Returns 0 (n = 0: the zero
+ * triple), −1 for bad arguments.  PPO_RET_CHUNK: the rows one workgroup of the scan composes. */
+#define PPO_RET_CHUNK 2048
+int    ppo_reward_returns_device(const float* d_reward, const unsigned char* d_term, const unsigned char* d_trunc,
+                                 long n, float gamma, int seg_len, const double* d_carry_in,
+                                 const unsigned char* d_cont, double* d_returns, double* d_carry_out, double* out3);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

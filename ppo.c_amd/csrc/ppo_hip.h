@@ -120,8 +120,10 @@ void phip_env_reset(int kind, float* env_state, float* state, int E, int T, int 
 void phip_env_first_obs(int kind, const float* env_state, float* state, int E, int T, int S);
 void phip_sample_rows(const float* mu, const float* log_std, const int* rows, float* action, float* logprob, int E,
                       int A, uint64_t seed, uint64_t step);
+/* cont (may be NULL) [E], written at t = T − 1: 1 when the environment was not reset after that step — the next
+ * rollout's first observation continues the episode — 0 otherwise */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
-                   uint8_t* term, uint8_t* trunc, int E, int T, int t, int S, int A, uint64_t seed);
+                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, int S, int A, uint64_t seed);
 
 /* ---------------- single-workgroup update phase for small networks (tiny.hip) ---------------- */
 typedef struct {
@@ -368,6 +370,27 @@ void phip_obs_normalize(const float* x, float* y, long n, int S, const float* m,
 /* dst[dst_rows[i]] ← the same map of src[src_rows[i]], i < rows (a NULL list: the identity) */
 void phip_obs_normalize_rows(const float* src, const int* src_rows, float* dst, const int* dst_rows, int rows, int S,
                              const float* m, const float* r, float clip, const double* run);
+
+/* ---------------- return-based reward normalisation (retnorm.hip) ---------------- */
+/* The segmented forward scan of the discounted returns R_i = r_i + g·(k_{i-1}·R_{i-1} + c_i) over reward[0:n]
+ * (g = (double)gamma, k = !(term ∨ trunc), double throughout; seg_len > 0: n % seg_len == 0 and row e·seg_len
+ * takes c = carry_in[e]; seg_len = 0: no carry, carry_in / cont / carry_out unused) and what follows it, four
+ * launches (block aggregates, carry, apply, finish; n = 0: the finish alone), none with a host read:
+ * returns (may be NULL) ← the n returns; carry_out (may be NULL; needs cont) [n / seg_len] ← cont[e] ?
+ * R_{e·seg_len + seg_len − 1} : 0; batch ← the exact-in-double triple {n, mean, M2} of the returns,
+ * deterministic (no floating-point atomics, per-workgroup partials folded in a fixed order); run (may be NULL)
+ * ← run ⊕ batch (Chan); scale (may be NULL; needs run) ← (float)(1/sqrt(M2/n + 1e-8)) of run, 1 for n = 0;
+ * counts (may be NULL) [2] ← 0 */
+void phip_ret_scan(const float* reward, const uint8_t* term, const uint8_t* trunc, long n, float gamma, int seg_len,
+                   const double* carry_in, const uint8_t* cont, double* returns, double* carry_out, double* batch,
+                   double* run, float* scale, unsigned long long* counts);
+/* the finish alone: `count` triples (consecutive, rank order; empty ones skipped; count = 0: none) folded into
+ * run, scale (may be NULL) refreshed, counts (may be NULL) cleared */
+void phip_ret_fold(const double* triples, int count, double* run, float* scale, unsigned long long* counts);
+/* y[0:n] ← clamp(reward·scale[0], ±clip) in fp32 (y may be reward); run[0] == 0: no clamp; counts (may be NULL):
+ * [0] += clamped elements, [1] += n (integer atomics) */
+void phip_ret_scale(const float* reward, float* y, long n, const float* scale, float clip, const double* run,
+                    unsigned long long* counts);
 
 /* ---------------- sampling / synthetic data (sample.hip) ---------------- */
 void phip_sample(const float* mu, const float* log_std, float* action, float* logprob, int m, int A,

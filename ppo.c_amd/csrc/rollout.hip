@@ -81,7 +81,8 @@ __device__ __forceinline__ float angle_normalize(float x) {
 __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__ state,
                                      const float* __restrict__ action, float* __restrict__ next_state,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
-                                     uint8_t* __restrict__ trunc, int E, int T, int t, uint64_t seed) {
+                                     uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
+                                     uint64_t seed) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
@@ -102,6 +103,7 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
     const bool limit = steps >= 200.f;
     term[row] = 0;
     trunc[row] = (limit || t == T - 1) ? 1 : 0;
+    if (cont && t == T - 1) cont[e] = limit ? 0 : 1;     // not reset: the next rollout continues this episode
     if (limit) {                                         // TimeLimit reset
         const u32x4 r = philox((uint64_t)e, kReset + (uint64_t)t, seed);
         th = -(float)M_PI + 2.f * (float)M_PI * u01(r.x);
@@ -122,8 +124,8 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
 // by every thread of the env identically (same Philox draw), so no cross-thread exchange
 __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ state, const float* __restrict__ action,
                                   float* __restrict__ next_state, float* __restrict__ reward,
-                                  uint8_t* __restrict__ term, uint8_t* __restrict__ trunc, int E, int T, int t,
-                                  int S, int A, uint64_t seed) {
+                                  uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
+                                  uint8_t* __restrict__ cont, int E, int T, int t, int S, int A, uint64_t seed) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
@@ -142,6 +144,7 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
         reward[row] = -0.01f * ss / (float)A + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
         term[row] = done ? 1 : 0;
         trunc[row] = (!done && t == T - 1) ? 1 : 0;
+        if (cont && t == T - 1) cont[e] = done ? 0 : 1;
     }
     const float nxt = done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + (uint64_t)t, seed).x) : o2;
     es[k] = nxt;
@@ -215,15 +218,15 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 }
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
-                   uint8_t* term, uint8_t* trunc, int E, int T, int t, int S, int A, uint64_t seed) {
+                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, int S, int A, uint64_t seed) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && A == 1, "phip_env_step: Pendulum-v1 needs S = 3, A = 1");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
-                           state, action, next_state, reward, term, trunc, E, T, t, seed);
+                           state, action, next_state, reward, term, trunc, cont, E, T, t, seed);
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
-                           env_state, state, action, next_state, reward, term, trunc, E, T, t, S, A, seed);
+                           env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, S, A, seed);
     }
     PPO_LAUNCH_CHECK();
 }

@@ -342,7 +342,7 @@ const char* ppo_build_info(void) {
     return "libppo: hand-written HIP for gfx950 (MI355X); fp32 MFMA v_mfma_f32_32x32x2_f32 GEMMs; "
            "kernels: gemm{NT,NN,TN}, relu, mse, policy_head, log_prob, gae_scan, welford, normalize, "
            "gather, adam_flat/multi, grad_norm, policy_kl, obs_stats, obs_fold, obs_affine, obs_norm, obs_norm_rows, "
-           "sample, synthetic fill; comm: RCCL";
+           "ret_scan, ret_finish, ret_scale, sample, synthetic fill; comm: RCCL";
 }
 
 void* ppo_dev_alloc(size_t bytes) { return phip_malloc(bytes); }

@@ -85,6 +85,26 @@ typedef struct {
     double* obs_all;
     int obs_all_world;
     unsigned long long* obs_counts;
+    /* running return-based reward normalisation (ppo_set_reward_norm; 0 = off; csrc/retnorm.hip): the clamp,
+     * the freeze flag, the running triple {n, mean, M2} of the discounted returns in double, the fp32 scale, the
+     * shadow of `reward` GAE reads (capacity floats), this rank's batch triple and the all-gathered ones, and the
+     * counters {clamped, scaled} of the last update's scaling.  All NULL until first used. */
+    float rew_clip;
+    int rew_frozen;
+    double* rew_run;
+    float* rew_scale;
+    float* rew_shadow;
+    double* rew_batch;
+    double* rew_all;
+    int rew_all_world;
+    unsigned long long* rew_counts;
+    /* the carry of the returns across device rollouts, kept whether or not the feature is on: ro_cont[e] = the
+     * last rollout left environment e's episode running; carry_in[e] enters row e·T of the buffer's scan,
+     * carry_out[e] is what the last scan left for the next rollout (both [ro_E] doubles).  ro_laid: the buffer
+     * holds the last ppo_rollout_device's E × T rows; rew_scanned: an update has scanned that rollout. */
+    unsigned char* ro_cont;
+    double *rew_carry_in, *rew_carry_out;
+    int ro_laid, rew_scanned;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -177,6 +197,9 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->vclip_counts);
     phip_free(d->obs_run); phip_free(d->obs_m); phip_free(d->obs_shadow); phip_free(d->obs_next);
     phip_free(d->obs_batch); phip_free(d->obs_all); phip_free(d->obs_counts);
+    phip_free(d->rew_run); phip_free(d->rew_scale); phip_free(d->rew_shadow); phip_free(d->rew_batch);
+    phip_free(d->rew_all); phip_free(d->rew_counts);
+    phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -326,10 +349,60 @@ static const float* obs_next_rows(PPODev* d, TrajectoryBuffer* b, const int* row
     return d->obs_next;
 }
 
+/* ------------------------------------------------------------------ */
+/* running return-based reward normalisation (ppo_ext.h ppo_set_reward_norm) */
+/* ------------------------------------------------------------------ */
+static int rew_on(const PPODev* d) { return d && d->rew_clip > 0.f; }
+
+/* the running triple and its scale (the identity, s = 1, until something is folded or set) */
+static void rew_ws(PPODev* d) {
+    if (d->rew_run) return;
+    d->rew_run = (double*)phip_malloc(3 * sizeof(double));
+    d->rew_batch = (double*)phip_malloc(3 * sizeof(double));
+    d->rew_scale = (float*)phip_malloc(sizeof(float));
+    d->rew_counts = (unsigned long long*)phip_malloc(2 * sizeof(unsigned long long));
+    phip_ret_fold(NULL, 0, d->rew_run, d->rew_scale, NULL);
+}
+
+/* the update's steps 1 to 4 while the feature is on, stream-ordered ahead of GAE's forwards and with no host
+ * read: the scan of the raw reward[0:limit] into this rank's batch triple and carry_out, the fold (at world > 1
+ * behind the all-gather every rank reaches here, an empty shard with the zero triple), the refreshed scale and
+ * the scaled, clamped shadow.  Frozen: the shadow alone, under the scale as it stands.  Returns the shadow. */
+static const float* rew_prepare(PPO* ppo, PPODev* d, int limit, float gamma) {
+    TrajectoryBuffer* buf = ppo->buffer;
+    rew_ws(d);
+    if (!d->rew_shadow) d->rew_shadow = (float*)phip_malloc(sizeof(float) * (size_t)buf->capacity);
+    if (d->rew_frozen) {
+        phip_memset(d->rew_counts, 0, 2 * sizeof(unsigned long long));
+    } else {
+        /* rows e·T of a buffer ppo_rollout_device laid take carry_in[e]; any other buffer is one stream */
+        const int laid = d->ro_laid && limit > 0 && (long)d->ro_E * d->ro_T == limit;
+        const int world = phip_comm_world();
+        phip_ret_scan(buf->reward_p, (const uint8_t*)buf->terminated_p, (const uint8_t*)buf->truncated_p, limit, gamma,
+                      laid ? d->ro_T : 0, laid ? d->rew_carry_in : NULL, laid ? d->ro_cont : NULL, NULL,
+                      laid ? d->rew_carry_out : NULL, d->rew_batch, world > 1 ? NULL : d->rew_run,
+                      world > 1 ? NULL : d->rew_scale, d->rew_counts);
+        if (laid) d->rew_scanned = 1;
+        if (world > 1) {
+            if (world > d->rew_all_world) {
+                phip_free(d->rew_all);
+                d->rew_all = (double*)phip_malloc(3 * sizeof(double) * (size_t)world);
+                d->rew_all_world = world;
+            }
+            phip_allgather_f64(d->rew_batch, d->rew_all, 3);
+            phip_ret_fold(d->rew_all, world, d->rew_run, d->rew_scale, NULL);
+        }
+    }
+    phip_ret_scale(buf->reward_p, d->rew_shadow, limit, d->rew_scale, d->rew_clip, d->rew_run, d->rew_counts);
+    return d->rew_shadow;
+}
+
 /* ppo: NULL (compute_gae_cuda / compute_gae: no normaliser, raw states), or the PPO whose update runs this
  * GAE with observation normalisation on (obs_prepare has run): the forwards read the shadow, the own
- * next_state rows are normalised into a compact scratch, and the batch triple is folded behind the scan */
-static void gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda, PPO* ppo) {
+ * next_state rows are normalised into a compact scratch, and the batch triple is folded behind the scan.
+ * reward: the rows the scan reads — the buffer's, or their scaled shadow (rew_prepare) */
+static void gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda, PPO* ppo,
+                       const float* reward) {
     PPODev* od = ppo ? (PPODev*)ppo->dev : NULL;
     const float* state = od ? od->obs_shadow : b->state_p;
     const int n = b->full ? b->capacity : b->idx;
@@ -356,7 +429,7 @@ static void gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float
             phip_scatter_values(g_vn, g_own, V->d_output, own);
         }
     }
-    phip_gae_scan(g_v, g_vn, b->reward_p, (const uint8_t*)b->terminated_p, (const uint8_t*)b->truncated_p, n, gamma,
+    phip_gae_scan(g_v, g_vn, reward, (const uint8_t*)b->terminated_p, (const uint8_t*)b->truncated_p, n, gamma,
                   lambda, b->advantage_p, b->adv_target_p, g_welford);
     const int world = phip_comm_world();
     if (world > 1) {       /* global advantage statistics across env shards */
@@ -370,7 +443,7 @@ static void gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float
 }
 
 void ppo_gae_device(NeuralNetwork* V, TrajectoryBuffer* b, float gamma, float lambda) {
-    gae_device(V, b, gamma, lambda, NULL);
+    gae_device(V, b, gamma, lambda, NULL, b->reward_p);
 }
 
 long ppo_gae_state(double* welford, float* v, float* v_next, long n) {
@@ -1005,10 +1078,18 @@ static void replica_hash(PPO* ppo) {
     PPODev* d = (PPODev*)ppo->dev;
     const int obs = obs_on(d);
     if (obs) obs_ws(ppo, d);      /* on but never folded or set: the zero triple, hashed like a peer's zeros */
-    const float* spans[4] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params, obs ? (const float*)d->obs_run : NULL};
-    const long lens[4] = {pol->mu->num_params, pol->action_size, ppo->V->num_params,
-                          obs ? 2 * (1 + 2L * ppo->buffer->state_size) : 0};
-    phip_param_hash(spans, lens, obs ? 4 : 3);
+    const float* spans[5] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params, obs ? (const float*)d->obs_run : NULL,
+                             NULL};
+    long lens[5] = {pol->mu->num_params, pol->action_size, ppo->V->num_params,
+                    obs ? 2 * (1 + 2L * ppo->buffer->state_size) : 0, 0};
+    int n_spans = obs ? 4 : 3;
+    /* … and, while reward normalisation is on, the returns' running triple (3 doubles), likewise */
+    if (rew_on(d)) {
+        rew_ws(d);
+        spans[n_spans] = (const float*)d->rew_run;
+        lens[n_spans++] = 6;
+    }
+    phip_param_hash(spans, lens, n_spans);
 }
 
 unsigned long long ppo_param_hash(void* vppo) {
@@ -1080,7 +1161,10 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
      * read the shadow.  The caller's buffer is never written. */
     const int obs = obs_on(d);
     const float* state = obs ? obs_prepare(ppo, d, limit) : buf->state_p;
-    gae_device(V, buf, gamma, ppo->lambda, obs ? ppo : NULL);
+    /* reward normalisation (off: nothing launched, GAE reads buf->reward_p as before): only GAE reads rewards,
+     * so the scan, the fold, its collective and the scaled shadow all come here, once per update */
+    const float* reward = rew_on(d) ? rew_prepare(ppo, d, limit, gamma) : buf->reward_p;
+    gae_device(V, buf, gamma, ppo->lambda, obs ? ppo : NULL, reward);
     /* D19: an empty buffer (idx = 0, not full) has nothing to train on; the reference would divide
      * by zero (rand() % 0 in shuffle_buffer, % limit in get_batch) — here the update ends after GAE.
      * At world > 1 the ranks agree first (min over ranks): one empty shard ends the update on every
@@ -1218,8 +1302,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[22] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[25] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1249,7 +1333,75 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         v[20] = (double)cnt[0];
         v[21] = (double)cnt[1];
     }
-    for (int i = 0; i < n && i < 22; i++) out[i] = v[i];
+    if (n > 22 && rew_on(d) && d->rew_run) {    /* reward normalisation: zeros while it is off */
+        unsigned long long cnt[2];
+        phip_d2h(&v[22], d->rew_run, sizeof(double));
+        phip_d2h(cnt, d->rew_counts, sizeof(cnt));
+        v[23] = (double)cnt[0];
+        v[24] = (double)cnt[1];
+    }
+    for (int i = 0; i < n && i < 25; i++) out[i] = v[i];
+}
+
+/* ppo_ext.h: running return-based reward normalisation */
+int ppo_set_reward_norm(void* vppo, float clip) {
+    if (isnan(clip)) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    d->rew_clip = clip > 0.f ? clip : 0.f;                   /* +inf stays: scale, never clamp */
+    return 0;
+}
+
+float ppo_get_reward_norm(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo->dev ? ((PPODev*)ppo->dev)->rew_clip : 0.f;
+}
+
+int ppo_reward_norm_freeze(void* vppo, int frozen) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    const int was = d->rew_frozen;
+    d->rew_frozen = frozen != 0;
+    return was;
+}
+
+void ppo_reward_norm_get_state(void* vppo, double* out3) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    phip_sync();
+    if (d->rew_run) phip_d2h(out3, d->rew_run, 3 * sizeof(double));
+    else memset(out3, 0, 3 * sizeof(double));
+}
+
+int ppo_reward_norm_set_state(void* vppo, const double* in3) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    if (!in3 || !(in3[0] >= 0.0) || isinf(in3[0]) || !isfinite(in3[1]) || !(in3[2] >= 0.0) || isinf(in3[2])) return -1;
+    rew_ws(d);
+    phip_sync();                                             /* nothing queued still reads the old scale */
+    phip_h2d(d->rew_run, in3, 3 * sizeof(double));
+    phip_ret_fold(NULL, 0, d->rew_run, d->rew_scale, NULL);
+    phip_sync();
+    return 0;
+}
+
+float ppo_reward_norm_scale(void* vppo) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    float s = 1.f;
+    rew_ws(d);
+    phip_sync();
+    phip_d2h(&s, d->rew_scale, sizeof(float));
+    return s;
+}
+
+int ppo_reward_returns_device(const float* d_reward, const unsigned char* d_term, const unsigned char* d_trunc, long n,
+                              float gamma, int seg_len, const double* d_carry_in, const unsigned char* d_cont,
+                              double* d_returns, double* d_carry_out, double* out3) {
+    static double* triple = NULL;                 /* one per process, never freed (as ppo_obs_stats_device's) */
+    if (!out3 || n < 0 || seg_len < 0 || isnan(gamma) || (n > 0 && (!d_reward || !d_term || !d_trunc))) return -1;
+    if (seg_len > 0 && (n % seg_len != 0 || (n > 0 && (!d_carry_in || (d_carry_out && !d_cont))))) return -1;
+    if (!triple) triple = (double*)phip_malloc(3 * sizeof(double));
+    phip_ret_scan(d_reward, d_term, d_trunc, n, gamma, n > 0 ? seg_len : 0, d_carry_in, d_cont, d_returns,
+                  seg_len > 0 ? d_carry_out : NULL, triple, NULL, NULL, NULL);
+    phip_sync();
+    phip_d2h(out3, triple, 3 * sizeof(double));
+    return 0;
 }
 
 /* ppo_ext.h: running observation normalisation */
@@ -1466,6 +1618,9 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
     if (obs_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout; "
             "use ppo_rollout_device + ppo_update");
+    /* the host rollout resets the environment at each call: its buffer is scanned with no carry (reward
+     * normalisation), and a device rollout after it starts from a zero carry */
+    if (ppo->dev) ((PPODev*)ppo->dev)->ro_laid = ((PPODev*)ppo->dev)->rew_scanned = 0;
     for (int i = 0; i < steps_per_epoch / ppo->buffer->capacity; i++) {
         collect_trajectories(ppo->buffer, env, ppo->policy, ppo->buffer->capacity);
         buffer_to_device(ppo->buffer);
@@ -1530,10 +1685,28 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         phip_free(d->env_state);
         d->env_state = (float*)phip_malloc(sizeof(float) * (size_t)E * (S > 3 ? S : 3));
         phip_env_reset(env_kind, d->env_state, b->d_state_p, E, T, S, splitmix64(seed));
+        /* fresh episodes: nothing continues, nothing is carried (phip_malloc zeroes) */
+        phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
+        d->ro_cont = (unsigned char*)phip_malloc((size_t)E);
+        d->rew_carry_in = (double*)phip_malloc(sizeof(double) * (size_t)E);
+        d->rew_carry_out = (double*)phip_malloc(sizeof(double) * (size_t)E);
+        d->rew_scanned = 0;
         d->ro_E = E;
         d->ro_kind = env_kind;
         d->ro_S = S;
     }
+    /* the returns' carry (reward normalisation; kept with the feature off too, so that it may be turned on
+     * between a rollout and its update): what an update's scan of the rollout just before this one left
+     * becomes this one's carry_in; with no such scan every return restarts from 0 */
+    if (d->rew_scanned) {
+        double* t = d->rew_carry_in;
+        d->rew_carry_in = d->rew_carry_out;
+        d->rew_carry_out = t;
+    } else {
+        phip_memset(d->rew_carry_in, 0, sizeof(double) * (size_t)E);
+    }
+    d->rew_scanned = 0;
+    d->ro_laid = 1;
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     GaussianPolicy* pol = ppo->policy;
     phip_env_first_obs(env_kind, d->env_state, b->d_state_p, E, T, S);
@@ -1549,7 +1722,7 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key,
                          d->ro_step++);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
-                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, E, T, t, S, A, key);
+                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, S, A, key);
     }
     phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
     phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
@@ -1584,6 +1757,8 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     b->idx = (int)(N % b->capacity);
     b->full = N == b->capacity;
     buffer_point_device(b);
+    /* not laid by a device rollout: scanned as one stream, and the next rollout starts from a zero carry */
+    if (ppo->dev) ((PPODev*)ppo->dev)->ro_laid = ((PPODev*)ppo->dev)->rew_scanned = 0;
     (void)A;
 }
 

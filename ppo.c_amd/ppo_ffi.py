@@ -170,6 +170,14 @@ _SIGS = {
     "ppo_obs_norm_affine": (C.c_int, [_P, _P, _P, C.c_int]),
     "ppo_obs_normalize_device": (C.c_int, [_P, _P, _P, C.c_long]),
     "ppo_obs_stats_device": (C.c_int, [_P, C.c_long, C.c_int, C.POINTER(C.c_double)]),
+    "ppo_set_reward_norm": (C.c_int, [_P, C.c_float]),
+    "ppo_get_reward_norm": (C.c_float, [_P]),
+    "ppo_reward_norm_freeze": (C.c_int, [_P, C.c_int]),
+    "ppo_reward_norm_get_state": (None, [_P, C.POINTER(C.c_double)]),
+    "ppo_reward_norm_set_state": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "ppo_reward_norm_scale": (C.c_float, [_P]),
+    "ppo_reward_returns_device": (C.c_int, [_P, _P, _P, C.c_long, C.c_float, C.c_int, _P, _P, _P, _P,
+                                            C.POINTER(C.c_double)]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
