@@ -356,7 +356,10 @@ void ppo_fill_synthetic(void* ppo, int n_envs, int horizon, unsigned long long s
  * env-major into the device buffer (transition (e, t) at row e·horizon + t; each segment ends
  * truncated), ready for ppo_update.  env_kind 0 = Pendulum-v1 (S = 3, A = 1; gymnasium dynamics),
  * 1 = synthetic (any S, A).  Episodes continue across calls; the first call (or a change of
- * n_envs / env_kind) resets every environment from `seed`. */
+ * n_envs / env_kind) resets every environment from `seed`.  `seed` keys the Philox streams of the
+ * policy noise, the environment's noise and its resets; the position in them advances with every
+ * step of every call (a counter that starts at 0 with the PPO), so passing the same seed to every
+ * call is the intended use and a fresh PPO with that seed reproduces the same rollouts. */
 void ppo_rollout_device(void* ppo, int n_envs, int horizon, int env_kind, unsigned long long seed);
 
 /* layer 0's input of the last device forward of a NeuralNetwork*, m rows × input_size fp32, to the

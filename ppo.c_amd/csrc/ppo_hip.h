@@ -121,9 +121,11 @@ void phip_env_first_obs(int kind, const float* env_state, float* state, int E, i
 void phip_sample_rows(const float* mu, const float* log_std, const int* rows, float* action, float* logprob, int E,
                       int A, uint64_t seed, uint64_t step);
 /* cont (may be NULL) [E], written at t = T − 1: 1 when the environment was not reset after that step — the next
- * rollout's first observation continues the episode — 0 otherwise */
+ * rollout's first observation continues the episode — 0 otherwise.  t addresses the row and ends the segment;
+ * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h) */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
-                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, int S, int A, uint64_t seed);
+                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
+                   uint64_t seed);
 
 /* ---------------- single-workgroup update phase for small networks (tiny.hip) ---------------- */
 typedef struct {

@@ -15,41 +15,19 @@
 //            0.05·ε, −1, 1); r = −0.01·mean(a²) + 0.1·ε; terminated ~ Bernoulli(1/500), reset
 //            o ~ U(−1, 1).
 #include "dev.h"
+#include "rng.h"
 
 #include <cmath>
 
 namespace {
 
+using namespace ppo_rng;
+
 constexpr int TPB = 256;
 
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox(uint64_t counter, uint64_t offset, uint64_t seed) {
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32);
-    uint32_t c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return u32x4{c0, c1, c2, c3};
-}
-
-__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ float normal_at(uint64_t idx, uint64_t offset, uint64_t seed) {
-    const u32x4 r = philox(idx, offset, seed);
-    return sqrtf(-2.f * logf(u01(r.x))) * cosf(2.f * (float)M_PI * u01(r.y));
-}
-
-// Streams of the Philox key space used here (offset high bits): policy noise, env noise, resets.
-constexpr uint64_t kNoise = 1ull << 40, kEnv = 2ull << 40, kReset = 3ull << 40;
+// `step` below is the rollout's global step counter (it advances with every step of every
+// ppo_rollout_device call): the position in the policy-noise, env and reset streams of rng.h.  `t`
+// is the step inside this call: row addressing and the segment-end truncation only.
 
 // a = μ + ε·σ written to buffer row rows[e]; log π(a) as policy.cu:67-74 (same as sample.hip)
 __global__ void sample_rows_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
@@ -82,7 +60,7 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
                                      const float* __restrict__ action, float* __restrict__ next_state,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
                                      uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
-                                     uint64_t seed) {
+                                     uint64_t step, uint64_t seed) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
@@ -105,7 +83,7 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
     trunc[row] = (limit || t == T - 1) ? 1 : 0;
     if (cont && t == T - 1) cont[e] = limit ? 0 : 1;     // not reset: the next rollout continues this episode
     if (limit) {                                         // TimeLimit reset
-        const u32x4 r = philox((uint64_t)e, kReset + (uint64_t)t, seed);
+        const u32x4 r = philox((uint64_t)e, kReset + step, seed);
         th = -(float)M_PI + 2.f * (float)M_PI * u01(r.x);
         thdot = -1.f + 2.f * u01(r.y);
         steps = 0.f;
@@ -125,16 +103,17 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
 __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ state, const float* __restrict__ action,
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
-                                  uint8_t* __restrict__ cont, int E, int T, int t, int S, int A, uint64_t seed) {
+                                  uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
+                                  uint64_t seed) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
     const float* ar = action + row * A;
-    const u32x4 d = philox((uint64_t)e, kEnv + 2 * (uint64_t)t, seed);
+    const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
     const bool done = u01(d.z) < 1.f / 500.f;
     const float o = es[k];
-    const float eps = normal_at((uint64_t)k, kEnv + 2 * (uint64_t)t + 1, seed);
+    const float eps = normal_at((uint64_t)k, kEnv + 2 * step + 1, seed);
     float o2 = 0.95f * o + 0.05f * tanhf(ar[j % A]) + 0.05f * eps;
     o2 = fminf(fmaxf(o2, -1.f), 1.f);
     next_state[row * S + j] = o2;
@@ -146,7 +125,7 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
         trunc[row] = (!done && t == T - 1) ? 1 : 0;
         if (cont && t == T - 1) cont[e] = done ? 0 : 1;
     }
-    const float nxt = done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + (uint64_t)t, seed).x) : o2;
+    const float nxt = done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + step, seed).x) : o2;
     es[k] = nxt;
     if (t + 1 < T) state[(row + 1) * S + j] = nxt;
 }
@@ -218,15 +197,17 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 }
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
-                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, int S, int A, uint64_t seed) {
+                   uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
+                   uint64_t seed) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && A == 1, "phip_env_step: Pendulum-v1 needs S = 3, A = 1");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
-                           state, action, next_state, reward, term, trunc, cont, E, T, t, seed);
+                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed);
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
-                           env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, S, A, seed);
+                           env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
+                           seed);
     }
     PPO_LAUNCH_CHECK();
 }

@@ -7,40 +7,15 @@
 //   a = μ + ε·exp(log_std),   log π(a) as in policy.cu:67-74.
 // The synthetic-rollout fills implement SURVEY §8d's generator on the device.
 #include "dev.h"
+#include "rng.h"
 
 #include <cmath>
 
 namespace {
 
+using namespace ppo_rng;
+
 constexpr int TPB = 256;
-
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox(uint64_t counter, uint64_t offset, uint64_t seed) {
-    uint32_t c0 = (uint32_t)counter, c1 = (uint32_t)(counter >> 32);
-    uint32_t c2 = (uint32_t)offset, c3 = (uint32_t)(offset >> 32);
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-        const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return u32x4{c0, c1, c2, c3};
-}
-
-// uniform in (0, 1): 24 random bits, centred in their bucket
-__device__ __forceinline__ float u01(uint32_t x) { return ((x >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-
-__device__ __forceinline__ float normal_at(uint64_t idx, uint64_t offset, uint64_t seed) {
-    const u32x4 r = philox(idx, offset, seed);
-    const float u1 = u01(r.x), u2 = u01(r.y);
-    return sqrtf(-2.f * logf(u1)) * cosf(2.f * (float)M_PI * u2);
-}
 
 __device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
     const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));

@@ -1719,10 +1719,12 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
             phip_obs_normalize_rows(b->d_state_p, rows, shadow, rows, E, S, d->obs_m, d->obs_m + S, d->obs_clip,
                                     d->obs_run);
         nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
-        phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key,
-                         d->ro_step++);
+        /* one position in the Philox streams per step of every call: the policy noise and the environment's
+         * draws never repeat under a constant seed */
+        const uint64_t step = d->ro_step++;
+        phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
-                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, S, A, key);
+                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key);
     }
     phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
     phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
