@@ -330,6 +330,79 @@ float  ppo_reward_norm_scale(void* ppo);
 int    ppo_reward_returns_device(const float* d_reward, const unsigned char* d_term, const unsigned char* d_trunc,
                                  long n, float gamma, int seg_len, const double* d_carry_in,
                                  const unsigned char* d_cont, double* d_returns, double* d_carry_out, double* out3);
+/* Episode-return statistics of device rollouts and device evaluation (always on; not in the reference; what
+ * Stable-Baselines3's Monitor / evaluate_policy and CleanRL's episodic_return report; csrc/episode.hip).
+ * THE SCAN.  A rollout-laid buffer is E segments of T rows, transition (e, t) at row e·T + t.  Row (e, t) ENDS AN
+ * EPISODE iff
+ *     terminated || (truncated && (t < T−1 || cont == NULL || !cont[e]))
+ * (cont[e] = 1: environment e was not reset after the segment's last step, so the truncation ppo_rollout_device
+ * writes there ends nothing).  Each environment carries four doubles {ret, disc, w, len}, fresh = {0, 0, 1, 0},
+ * and its rows are taken in row order, in double, with g = (double)gamma and r the row's fp32 reward:
+ *     ret  = ret + (double)r
+ *     disc = disc + w·(double)r            (the product rounded, then the sum: no fused multiply-add — libppo is
+ *     w    = w·g                            built with -ffp-contract=off and episode.hip repeats it as a pragma)
+ *     len  = len + 1
+ *     at an end row: the episode (ret, disc, len) is emitted and the state set fresh
+ * d_row_ret / d_row_disc receive ret / disc after each row's update, before an end row's reset.
+ * THE AGGREGATE of a set of episodes is PPO_EP_NBATCH doubles
+ *     {n, mean of ret, M2 of ret (Σ squared deviations), min ret, max ret, Σ len, mean of disc}
+ * — all zero for the empty set — and two aggregates combine as a ⊕ b (Chan et al.; an empty side returns the
+ * other unchanged):
+ *     n = na + nb;  f = nb / n;  δ = mean_b − mean_a
+ *     mean = mean_a + δ·f;   M2 = (M2a + M2b) + (δ·δ)·(na·f);   mdisc = mdisc_a + (mdisc_b − mdisc_a)·f
+ *     min = b.min < a.min ? b.min : a.min;  max likewise;  Σlen = Σlen_a + Σlen_b
+ * The batch aggregate of one scan: environment e's aggregate P_e starts empty and takes each episode it emits, in
+ * the order they end, as P_e ← P_e ⊕ {1, ret, 0, ret, ret, len, disc}; then 256 partials
+ * Q_i = P_{i·per} ⊕ … ⊕ P_{min(E, (i+1)·per) − 1} (left to right from the empty aggregate, per = ⌈E/256⌉) are folded
+ * by a pairwise tree: for stride = 1, 2, 4, …, 128, every i that is a multiple of 2·stride takes Q_i ← Q_i ⊕
+ * Q_{i+stride}; Q_0 is the batch.  No floating-point atomics; the order depends on E alone, never on the grid or
+ * on scheduling.  The scan and its fold are two launches whatever E and T are.
+ * THE TRACKER.  ppo_rollout_device runs the scan once behind its step loop, stream-ordered and with no host
+ * read, over the rows it has just laid, with the cont[] it has just written, the PPO's per-environment state and
+ * the tracker's gamma.  The batch becomes "the last rollout's" and is folded into a running window, window ←
+ * window ⊕ batch: "since the last reset".  The per-environment state lives exactly as long as cont[]: it is
+ * allocated and set fresh on the first call and on a change of n_envs, env_kind or state_size, which drops the
+ * episodes in progress and keeps the window.  ppo_fill_synthetic, the host rollout and ppo_update do not touch the
+ * tracker.  Under data parallelism the statistics are THIS RANK's environments; no collective is added.  Not
+ * hashed (ppo_param_hash) and not part of a checkpoint.
+ * ppo_episode_stats: out[0..7] since the last reset, out[8..15] the last rollout, each
+ *     {episodes n, mean return, population std sqrt(M2/n), min, max, mean length Σlen/n, mean discounted
+ *      return, M2}                          (host double arithmetic on the aggregate; all 0 where n == 0) */
+#define PPO_EP_NBATCH 7
+#define PPO_EP_NSTAT 16
+/* returns the values written (min(n, 16), 0 for n <= 0 or a NULL out); synchronises */
+int    ppo_episode_stats(void* ppo, double* out, int n);
+/* clears the window, NOT the episodes in progress (nor the last rollout's out[8..15]); stream-ordered */
+void   ppo_episode_reset_stats(void* ppo);
+/* the discount of `disc`; returns the previous value; NaN or a value outside [0, 1] only queries; default 0.99;
+ * applies from the next row scanned (the w carried by an episode in progress keeps its earlier factors) */
+float  ppo_episode_gamma(void* ppo, float gamma);
+/* The scan alone, on caller-supplied device arrays; synchronises.  d_cont may be NULL; d_state [E][4] doubles in
+ * and out (NULL: every environment fresh, nothing written back); d_row_ret / d_row_disc [E·T] doubles, may be
+ * NULL; out (host) ← the batch aggregate, PPO_EP_NBATCH doubles.  Returns 0, or −1 — nothing recorded for
+ * ppo_last_error, no device work — for a NULL d_reward / d_term / d_trunc / out, E <= 0 or T <= 0. */
+int    ppo_episode_scan_device(const float* d_reward, const unsigned char* d_term, const unsigned char* d_trunc,
+                               const unsigned char* d_cont, int E, int T, float gamma, double* d_state,
+                               double* d_row_ret, double* d_row_disc, double* out);
+/* DEVICE EVALUATION.  Steps n_envs fresh environments for `horizon` steps without touching the training state:
+ * the environments are reset exactly as a fresh PPO's first ppo_rollout_device(…, seed) resets them, the Philox
+ * keys are derived from `seed` as there, and the step counter is local and starts at 0 — so with deterministic
+ * == 0 a fresh PPO's evaluation sees, bit for bit, the trajectory of that PPO's first training rollout.
+ * deterministic != 0: the action is μ's output bit for bit (no noise drawn, no log-prob).  Rewards and flags go
+ * to an n_envs × horizon scratch (written as the rollout writes the buffer's, the segment-end truncation and
+ * cont[] included) and are scanned once at the end by the scan above with `gamma`, from fresh states:
+ * out[0..7] has the layout of ppo_episode_stats over the episodes completed within the horizon, out[8] is the
+ * number of environments whose last episode was still running (unfinished episodes are not counted).  While
+ * observation normalisation is on, observations are normalised under the pair as it stands, as if frozen:
+ * nothing is folded and the clamp counters of ppo_read_stats out[20] / out[21] keep describing the last update;
+ * reward normalisation does not apply (returns are raw).  The trajectory buffer, the training environments, the
+ * rollout's step counter and cont[], both return carries, the tracker, both normalisers and every parameter and
+ * Adam state are left bit-identical; only μ's forward workspaces (its activations of the last forward) change.
+ * Scratch is O(n_envs·(S + A) + n_envs·horizon·6 B), kept for the next call and freed by free_ppo.
+ * Returns the values written (9), synchronising once to fill out; or −1 — no die, nothing run — for a NULL ppo or
+ * out, n_envs <= 0, horizon <= 0, env_kind not 0 or 1, Pendulum with S != 3 or A != 1, a NaN gamma or n < 9. */
+int    ppo_eval_device(void* ppo, int n_envs, int horizon, int env_kind, unsigned long long seed, int deterministic,
+                       float gamma, double* out, int n);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
  * (n, mean, M2) triple the normalisation used (global at world > 1; out[3..5] the local triple);
  * v / v_next (may be NULL) ← the first n values of V(state) and V(next_state) the scan read.

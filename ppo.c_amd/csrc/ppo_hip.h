@@ -126,6 +126,22 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
                    uint64_t seed);
+/* the evaluation's step (ppo_eval_device): the same dynamics (shared __device__ functions) over compact arrays —
+ * obs [E, S] is the current observation, read and replaced in place, action [E, A]; reward / term / trunc are
+ * written at row e·T + t and cont as phip_env_step writes them; nothing else is kept */
+void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
+                        uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
+                        uint64_t seed);
+
+/* ---------------- episode statistics (episode.hip) ---------------- */
+/* The scan of ppo_ext.h ppo_episode_scan_device plus its fold, two launches: E segments of T rows, cont (may be
+ * NULL) [E]; state_in (NULL: fresh) and state_out (NULL: not written) [E][4] doubles, may be the same array;
+ * row_ret / row_disc (may be NULL) [E·T]; out [8] ← the batch aggregate (PPO_EP_NBATCH doubles) and, at [7], the
+ * number of environments left mid-episode; window (may be NULL) [8] ← window ⊕ batch, [7] ← out[7]. */
+void phip_episode_scan(const float* reward, const uint8_t* term, const uint8_t* trunc, const uint8_t* cont, int E,
+                       int T, float gamma, const double* state_in, double* state_out, double* row_ret,
+                       double* row_disc, double* out, double* window);
+void phip_mean_action(const float* mu, float* action, long n);      /* action[0:n] ← mu[0:n], bit for bit */
 
 /* ---------------- single-workgroup update phase for small networks (tiny.hip) ---------------- */
 typedef struct {

@@ -55,6 +55,36 @@ __device__ __forceinline__ float angle_normalize(float x) {
     return y - (float)M_PI;
 }
 
+// One Pendulum-v1 step of environment e from (θ, θ̇, steps) under action a: the transition's reward and next
+// observation; on return (θ, θ̇, steps) is what the next step starts from — the TimeLimit reset drawn where
+// `limit`.  The training and the evaluation kernels both step through this, so the two cannot drift.
+struct PendulumStep { float reward, next[3]; bool limit; };
+
+__device__ __forceinline__ PendulumStep pendulum_advance(float& th, float& thdot, float& steps, float a, uint64_t e,
+                                                         uint64_t step, uint64_t seed) {
+    PendulumStep o;
+    const float u = fminf(fmaxf(a, -2.f), 2.f);
+    const float an = angle_normalize(th);
+    const float cost = an * an + 0.1f * thdot * thdot + 0.001f * u * u;
+    float nthdot = thdot + (3.f * 10.f / 2.f * sinf(th) + 3.f * u) * 0.05f;
+    nthdot = fminf(fmaxf(nthdot, -8.f), 8.f);
+    th = th + nthdot * 0.05f;
+    thdot = nthdot;
+    steps += 1.f;
+    o.next[0] = cosf(th);
+    o.next[1] = sinf(th);
+    o.next[2] = thdot;
+    o.reward = -cost;
+    o.limit = steps >= 200.f;
+    if (o.limit) {                                       // TimeLimit reset
+        const u32x4 r = philox(e, kReset + step, seed);
+        th = -(float)M_PI + 2.f * (float)M_PI * u01(r.x);
+        thdot = -1.f + 2.f * u01(r.y);
+        steps = 0.f;
+    }
+    return o;
+}
+
 // Pendulum-v1: env state (θ, θ̇, steps) in es[3e .. 3e+2]
 __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__ state,
                                      const float* __restrict__ action, float* __restrict__ next_state,
@@ -66,28 +96,14 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
     const long row = (long)e * T + t;
     float th = es[3 * e], thdot = es[3 * e + 1];
     float steps = es[3 * e + 2];
-    const float u = fminf(fmaxf(action[row], -2.f), 2.f);
-    const float an = angle_normalize(th);
-    const float cost = an * an + 0.1f * thdot * thdot + 0.001f * u * u;
-    float nthdot = thdot + (3.f * 10.f / 2.f * sinf(th) + 3.f * u) * 0.05f;
-    nthdot = fminf(fmaxf(nthdot, -8.f), 8.f);
-    th = th + nthdot * 0.05f;
-    thdot = nthdot;
-    steps += 1.f;
-    next_state[3 * row] = cosf(th);
-    next_state[3 * row + 1] = sinf(th);
-    next_state[3 * row + 2] = thdot;
-    reward[row] = -cost;
-    const bool limit = steps >= 200.f;
+    const PendulumStep o = pendulum_advance(th, thdot, steps, action[row], (uint64_t)e, step, seed);
+    next_state[3 * row] = o.next[0];
+    next_state[3 * row + 1] = o.next[1];
+    next_state[3 * row + 2] = o.next[2];
+    reward[row] = o.reward;
     term[row] = 0;
-    trunc[row] = (limit || t == T - 1) ? 1 : 0;
-    if (cont && t == T - 1) cont[e] = limit ? 0 : 1;     // not reset: the next rollout continues this episode
-    if (limit) {                                         // TimeLimit reset
-        const u32x4 r = philox((uint64_t)e, kReset + step, seed);
-        th = -(float)M_PI + 2.f * (float)M_PI * u01(r.x);
-        thdot = -1.f + 2.f * u01(r.y);
-        steps = 0.f;
-    }
+    trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
+    if (cont && t == T - 1) cont[e] = o.limit ? 0 : 1;   // not reset: the next rollout continues this episode
     es[3 * e] = th;
     es[3 * e + 1] = thdot;
     es[3 * e + 2] = steps;
@@ -98,8 +114,54 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
     }
 }
 
-// synthetic env: one thread per (env, obs element); the reward / done decision per env is taken
-// by every thread of the env identically (same Philox draw), so no cross-thread exchange
+// the evaluation's form: obs [E, 3] is the current observation, replaced in place; action [E]
+__global__ void pendulum_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
+                                     float* __restrict__ reward, uint8_t* __restrict__ term,
+                                     uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
+                                     uint64_t step, uint64_t seed) {
+    const int e = blockIdx.x * TPB + threadIdx.x;
+    if (e >= E) return;
+    const long row = (long)e * T + t;
+    float th = es[3 * e], thdot = es[3 * e + 1];
+    float steps = es[3 * e + 2];
+    const PendulumStep o = pendulum_advance(th, thdot, steps, action[e], (uint64_t)e, step, seed);
+    reward[row] = o.reward;
+    term[row] = 0;
+    trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
+    if (t == T - 1) cont[e] = o.limit ? 0 : 1;
+    es[3 * e] = th;
+    es[3 * e + 1] = thdot;
+    es[3 * e + 2] = steps;
+    obs[3 * e] = cosf(th);
+    obs[3 * e + 1] = sinf(th);
+    obs[3 * e + 2] = thdot;
+}
+
+// One synthetic step of observation element k = e·S + j under the action row ar: o2 the transition's next
+// observation, nxt what the next step starts from (the reset drawn where done), the reward for j == 0 only.  The
+// reward / done decision per env is taken by every thread of the env identically (same Philox draw).
+struct SynthStep { float o2, nxt, reward; bool done; };
+
+__device__ __forceinline__ SynthStep synth_advance(float o, const float* __restrict__ ar, long k, int e, int j, int A,
+                                                   uint64_t step, uint64_t seed) {
+    SynthStep s;
+    const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
+    s.done = u01(d.z) < 1.f / 500.f;
+    const float eps = normal_at((uint64_t)k, kEnv + 2 * step + 1, seed);
+    float o2 = 0.95f * o + 0.05f * tanhf(ar[j % A]) + 0.05f * eps;
+    o2 = fminf(fmaxf(o2, -1.f), 1.f);
+    s.o2 = o2;
+    s.reward = 0.f;
+    if (j == 0) {
+        float ss = 0.f;
+        for (int q = 0; q < A; ++q) ss += ar[q] * ar[q];
+        s.reward = -0.01f * ss / (float)A + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
+    }
+    s.nxt = s.done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + step, seed).x) : o2;
+    return s;
+}
+
+// synthetic env: one thread per (env, obs element); no cross-thread exchange
 __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ state, const float* __restrict__ action,
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
@@ -109,25 +171,36 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const float* ar = action + row * A;
-    const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
-    const bool done = u01(d.z) < 1.f / 500.f;
-    const float o = es[k];
-    const float eps = normal_at((uint64_t)k, kEnv + 2 * step + 1, seed);
-    float o2 = 0.95f * o + 0.05f * tanhf(ar[j % A]) + 0.05f * eps;
-    o2 = fminf(fmaxf(o2, -1.f), 1.f);
-    next_state[row * S + j] = o2;
+    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed);
+    next_state[row * S + j] = s.o2;
     if (j == 0) {
-        float ss = 0.f;
-        for (int q = 0; q < A; ++q) ss += ar[q] * ar[q];
-        reward[row] = -0.01f * ss / (float)A + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
-        term[row] = done ? 1 : 0;
-        trunc[row] = (!done && t == T - 1) ? 1 : 0;
-        if (cont && t == T - 1) cont[e] = done ? 0 : 1;
+        reward[row] = s.reward;
+        term[row] = s.done ? 1 : 0;
+        trunc[row] = (!s.done && t == T - 1) ? 1 : 0;
+        if (cont && t == T - 1) cont[e] = s.done ? 0 : 1;
     }
-    const float nxt = done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + step, seed).x) : o2;
-    es[k] = nxt;
-    if (t + 1 < T) state[(row + 1) * S + j] = nxt;
+    es[k] = s.nxt;
+    if (t + 1 < T) state[(row + 1) * S + j] = s.nxt;
+}
+
+// the evaluation's form: obs [E, S] is the current observation, replaced in place; action [E, A]
+__global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
+                                  float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
+                                  uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
+                                  uint64_t seed) {
+    const long k = (long)blockIdx.x * TPB + threadIdx.x;
+    if (k >= (long)E * S) return;
+    const int e = (int)(k / S), j = (int)(k % S);
+    const long row = (long)e * T + t;
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed);
+    if (j == 0) {
+        reward[row] = s.reward;
+        term[row] = s.done ? 1 : 0;
+        trunc[row] = (!s.done && t == T - 1) ? 1 : 0;
+        if (t == T - 1) cont[e] = s.done ? 0 : 1;
+    }
+    es[k] = s.nxt;
+    obs[k] = s.nxt;
 }
 
 // reset every env; write row e·T (t = 0) of the buffer
@@ -208,6 +281,23 @@ void phip_env_step(int kind, float* env_state, float* state, const float* action
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
                            seed);
+    }
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
+                        uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
+                        uint64_t seed) {
+    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * S + A + 2));
+    PPO_REQUIRE(env_state && obs && action && reward && term && trunc && cont && E > 0 && t >= 0 && t < T,
+                "phip_env_step_eval: operands");
+    if (kind == 0) {
+        PPO_REQUIRE(S == 3 && A == 1, "phip_env_step_eval: Pendulum-v1 needs S = 3, A = 1");
+        hipLaunchKernelGGL(pendulum_eval_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state, obs,
+                           action, reward, term, trunc, cont, E, T, t, step, seed);
+    } else {
+        hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
+                           env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed);
     }
     PPO_LAUNCH_CHECK();
 }

@@ -105,6 +105,22 @@ typedef struct {
     unsigned char* ro_cont;
     double *rew_carry_in, *rew_carry_out;
     int ro_laid, rew_scanned;
+    /* episode statistics (ppo_episode_stats; csrc/episode.hip): the discount of `disc`, the per-environment state
+     * {ret, disc, w, len} ([ro_E][4] doubles, living exactly as long as ro_cont) and two aggregates of 8 doubles,
+     * [0..7] the window since the last reset, [8..15] the last rollout */
+    float ep_gamma;
+    int ep_fresh;                 /* the next scan starts every environment fresh (ep_state not yet written) */
+    double* ep_state;
+    double* ep_agg;
+    /* ppo_eval_device's scratch, kept across calls: the environments' state, the current observation and its
+     * normalised copy, actions, log-probs and the identity row list ([ev_E] rows), the E × T rewards and flags
+     * ([ev_N] rows), cont and the aggregate */
+    int ev_E;
+    long ev_N;
+    float *ev_env, *ev_obs, *ev_obsn, *ev_act, *ev_lp, *ev_reward;
+    int* ev_rows;
+    unsigned char *ev_term, *ev_trunc, *ev_cont;
+    double* ev_agg;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -154,6 +170,7 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d = (PPODev*)xcalloc(1, sizeof(PPODev));
         d->stats = (float*)phip_malloc(4 * sizeof(float));
         d->max_v = d->max_p = -1;
+        d->ep_gamma = 0.99f;
         d->clip[0] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->kl = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
@@ -200,6 +217,10 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->rew_run); phip_free(d->rew_scale); phip_free(d->rew_shadow); phip_free(d->rew_batch);
     phip_free(d->rew_all); phip_free(d->rew_counts);
     phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
+    phip_free(d->ep_state); phip_free(d->ep_agg);
+    phip_free(d->ev_env); phip_free(d->ev_obs); phip_free(d->ev_obsn); phip_free(d->ev_act); phip_free(d->ev_lp);
+    phip_free(d->ev_reward); phip_free(d->ev_rows); phip_free(d->ev_term); phip_free(d->ev_trunc);
+    phip_free(d->ev_cont); phip_free(d->ev_agg);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -1404,6 +1425,126 @@ int ppo_reward_returns_device(const float* d_reward, const unsigned char* d_term
     return 0;
 }
 
+/* ppo_ext.h: episode statistics */
+/* the eight reported values of one aggregate {n, mean, M2, min, max, Σlen, mean disc} */
+static void ep_report(const double* a, double* v) {
+    memset(v, 0, 8 * sizeof(double));
+    if (!(a[0] > 0.0)) return;
+    v[0] = a[0];
+    v[1] = a[1];
+    v[2] = sqrt(a[2] / a[0]);
+    v[3] = a[3];
+    v[4] = a[4];
+    v[5] = a[5] / a[0];
+    v[6] = a[6];
+    v[7] = a[2];
+}
+
+int ppo_episode_stats(void* vppo, double* out, int n) {
+    if (!vppo || !out || n <= 0) return 0;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    double agg[16], v[PPO_EP_NSTAT];
+    memset(agg, 0, sizeof(agg));
+    phip_sync();
+    if (d->ep_agg) phip_d2h(agg, d->ep_agg, sizeof(agg));
+    ep_report(agg, v);
+    ep_report(agg + 8, v + 8);
+    if (n > PPO_EP_NSTAT) n = PPO_EP_NSTAT;
+    memcpy(out, v, sizeof(double) * (size_t)n);
+    return n;
+}
+
+void ppo_episode_reset_stats(void* vppo) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    if (d->ep_agg) phip_memset(d->ep_agg, 0, 8 * sizeof(double));
+}
+
+float ppo_episode_gamma(void* vppo, float gamma) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    const float was = d->ep_gamma;
+    if (gamma >= 0.f && gamma <= 1.f) d->ep_gamma = gamma;       /* NaN fails both comparisons */
+    return was;
+}
+
+int ppo_episode_scan_device(const float* d_reward, const unsigned char* d_term, const unsigned char* d_trunc,
+                            const unsigned char* d_cont, int E, int T, float gamma, double* d_state, double* d_row_ret,
+                            double* d_row_disc, double* out) {
+    static double* agg = NULL;                    /* one per process, never freed (as ppo_reward_returns_device's) */
+    if (!d_reward || !d_term || !d_trunc || !out || E <= 0 || T <= 0) return -1;
+    if (!agg) agg = (double*)phip_malloc(8 * sizeof(double));
+    phip_episode_scan(d_reward, d_term, d_trunc, d_cont, E, T, gamma, d_state, d_state, d_row_ret, d_row_disc, agg,
+                      NULL);
+    phip_sync();
+    phip_d2h(out, agg, PPO_EP_NBATCH * sizeof(double));
+    return 0;
+}
+
+/* ppo_eval_device's scratch for E environments and N = E·T rows (grow-only per part) */
+static void eval_ws(PPODev* d, int E, long N, int S, int A) {
+    if (E > d->ev_E) {
+        phip_free(d->ev_env); phip_free(d->ev_obs); phip_free(d->ev_obsn); phip_free(d->ev_act);
+        phip_free(d->ev_lp); phip_free(d->ev_rows); phip_free(d->ev_cont);
+        d->ev_env = (float*)phip_malloc(sizeof(float) * (size_t)E * (S > 3 ? S : 3));
+        d->ev_obs = (float*)phip_malloc(sizeof(float) * (size_t)E * S);
+        d->ev_obsn = (float*)phip_malloc(sizeof(float) * (size_t)E * S);
+        d->ev_act = (float*)phip_malloc(sizeof(float) * (size_t)E * A);
+        d->ev_lp = (float*)phip_malloc(sizeof(float) * (size_t)E);
+        d->ev_rows = (int*)phip_malloc(sizeof(int) * (size_t)E);
+        d->ev_cont = (unsigned char*)phip_malloc((size_t)E);
+        phip_rollout_rows(d->ev_rows, E, 1);                     /* rows[e] = e */
+        d->ev_E = E;
+    }
+    if (N > d->ev_N) {
+        phip_free(d->ev_reward); phip_free(d->ev_term); phip_free(d->ev_trunc);
+        d->ev_reward = (float*)phip_malloc(sizeof(float) * (size_t)N);
+        d->ev_term = (unsigned char*)phip_malloc((size_t)N);
+        d->ev_trunc = (unsigned char*)phip_malloc((size_t)N);
+        d->ev_N = N;
+    }
+    if (!d->ev_agg) d->ev_agg = (double*)phip_malloc(8 * sizeof(double));
+}
+
+int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned long long seed, int deterministic,
+                    float gamma, double* out, int n) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !out || n < 9 || n_envs <= 0 || horizon <= 0 || isnan(gamma)) return -1;
+    if (env_kind != 0 && env_kind != 1) return -1;
+    const int E = n_envs, T = horizon;
+    const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
+    if (env_kind == 0 && (S != 3 || A != 1)) return -1;
+    PPODev* d = dev_ws(ppo, 1);
+    eval_ws(d, E, (long)E * T, S, A);
+    /* the first reset and the key of every later draw, as ppo_rollout_device derives them; the step counter is
+     * local: the training rollout's position in the streams does not move */
+    phip_env_reset(env_kind, d->ev_env, d->ev_obs, E, 1, S, splitmix64(seed));
+    phip_env_first_obs(env_kind, d->ev_env, d->ev_obs, E, 1, S);
+    const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
+    GaussianPolicy* pol = ppo->policy;
+    const int norm = obs_on(d);
+    if (norm) obs_ws(ppo, d);
+    for (int t = 0; t < T; t++) {
+        /* normalised under the pair as it stands, uncounted, nothing folded */
+        if (norm)
+            phip_obs_normalize_rows(d->ev_obs, NULL, d->ev_obsn, NULL, E, S, d->obs_m, d->obs_m + S, d->obs_clip,
+                                    d->obs_run);
+        /* through the row list, as the rollout forwards: the same kernels over the same E rows */
+        nn_forward_dev_rows(pol->mu, norm ? d->ev_obsn : d->ev_obs, d->ev_rows, NULL, E);
+        const uint64_t step = (uint64_t)t;
+        if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
+        else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
+        phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
+                           d->ev_cont, E, T, t, step, S, A, key);
+    }
+    phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
+                      d->ev_agg, NULL);
+    double agg[8];
+    phip_sync();
+    phip_d2h(agg, d->ev_agg, sizeof(agg));
+    ep_report(agg, out);
+    out[8] = agg[7];
+    return 9;
+}
+
 /* ppo_ext.h: running observation normalisation */
 int ppo_set_obs_norm(void* vppo, float clip) {
     if (isnan(clip)) return -1;
@@ -1691,6 +1832,10 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         d->rew_carry_in = (double*)phip_malloc(sizeof(double) * (size_t)E);
         d->rew_carry_out = (double*)phip_malloc(sizeof(double) * (size_t)E);
         d->rew_scanned = 0;
+        /* episode statistics: the episodes in progress are dropped with the environments, the window stays */
+        phip_free(d->ep_state);
+        d->ep_state = (double*)phip_malloc(4 * sizeof(double) * (size_t)E);
+        d->ep_fresh = 1;
         d->ro_E = E;
         d->ro_kind = env_kind;
         d->ro_S = S;
@@ -1726,6 +1871,13 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key);
     }
+    /* episode statistics: one scan of the rows just laid (two launches, no host read) — the batch becomes the
+     * last rollout's aggregate and is folded into the window */
+    if (!d->ep_agg) d->ep_agg = (double*)phip_malloc(16 * sizeof(double));
+    phip_episode_scan(b->d_reward_p, (const uint8_t*)b->d_terminated_p, (const uint8_t*)b->d_truncated_p, d->ro_cont,
+                      E, T, d->ep_gamma, d->ep_fresh ? NULL : d->ep_state, d->ep_state, NULL, NULL, d->ep_agg + 8,
+                      d->ep_agg);
+    d->ep_fresh = 0;
     phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
     phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
     b->idx = (int)(N % b->capacity);

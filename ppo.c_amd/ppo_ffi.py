@@ -178,6 +178,13 @@ _SIGS = {
     "ppo_reward_norm_scale": (C.c_float, [_P]),
     "ppo_reward_returns_device": (C.c_int, [_P, _P, _P, C.c_long, C.c_float, C.c_int, _P, _P, _P, _P,
                                             C.POINTER(C.c_double)]),
+    "ppo_episode_stats": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
+    "ppo_episode_reset_stats": (None, [_P]),
+    "ppo_episode_gamma": (C.c_float, [_P, C.c_float]),
+    "ppo_episode_scan_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P, _P, _P,
+                                          C.POINTER(C.c_double)]),
+    "ppo_eval_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_int, C.c_float,
+                                  C.POINTER(C.c_double), C.c_int]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
     "ppo_prof_enable": (None, [C.c_int]),
