@@ -208,6 +208,30 @@ int    ppo_value_clip_old_values(void* ppo, const float* d_v_old, long n);
  * clipped rows, rows}; returns 0, −1 for bad arguments (a NULL array, m <= 0, eps_v not > 0); synchronises */
 int    ppo_value_clip_head_device(const float* d_y, const float* d_v_old, const int* d_rows, const float* d_tgt, int m,
                                   float eps_v, float* d_g, double* out3);
+/* One form of the clipped-surrogate / Gaussian policy head on caller-supplied device arrays (a test entry: the
+ * update never calls it).  The head exists in five forms, all of the same per-row arithmetic:
+ *     form 0 "separate"  log_prob_kernel → policy_loss_kernel → log_prob_bwd_kernel (the reference-API kernels); any A
+ *     form 1 "head"      phip_policy_head: the tiled kernel for A <= 32, the generic one above; A <= 4096
+ *     form 2 "out_head"  phip_out_head(head = 1): output layer + head + its backward; A ∈ {1, 6}, n ∈ {64 … 512}
+ *     form 3 "wide"      phip_policy_head_bwd_wide: head + output-layer backward; A = 17, n ∈ {256, 512}
+ *     form 4 "fused"     phip_policy_out_fused: output layer + head + its backward; A = 17, n ∈ {256, 512}
+ * Inputs: log σ [A], action [m, A], adv [m], old log-prob [m], and μ [m, A] for forms 0, 1 and 3.  Forms 2 and 4
+ * compute μ = x·Wᵀ + b from x [m, n], W [A, n], b [A] and WRITE it to d_mu; form 3 reads x and W for its backward
+ * (d_b unused).  relu_in != 0 masks gx by x > 0.  Outputs: forms 0 and 1 d_grad_mu [m, A] (and form 0 d_lp [m]);
+ * forms 2–4 d_gx [m, n] and d_gW, ONE allocation of A·n + A floats, gW [A, n] followed by gb [A]; every form
+ * d_grad_log_std [A] and *loss (the loss word read back).  Forms 1–4 add −ent_coeff to every column of
+ * d_grad_log_std (ppo.cu:436-438), form 0's kernels leave that to their host caller, so form 0 returns the bare
+ * sum; every form's loss includes −ent_coeff · entropy once.  The entry zeroes what the kernels accumulate into
+ * (gW, gb, grad log σ, the loss word), calls the form's phip_* function and synchronises.  Arrays a form does not
+ * use may be NULL; x, W, gx and gW must be 16-byte aligned.
+ * Returns 0 when the form ran; 1 when the form does not take the shape (by the kernels' own predicates; no
+ * kernel was launched); −1 for bad arguments (form outside 0–4, a NULL or misaligned array the form needs,
+ * m <= 0, A <= 0, n <= 0 for forms 2–4, NaN eps), with nothing recorded for ppo_last_error. */
+int    ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float eps, float ent_coeff,
+                              const float* d_log_std, const float* d_action, const float* d_adv,
+                              const float* d_old_lp, float* d_mu, const float* d_x, const float* d_W, const float* d_b,
+                              float* d_lp, float* d_grad_mu, float* d_gx, float* d_gW, float* d_grad_log_std,
+                              double* loss);
 /* Running observation normalisation (off by default; not in the reference; Stable-Baselines3 VecNormalize,
  * CleanRL NormalizeObservation).  Per observation column j the running state is, in double, a shared count n,
  * mean[j] and M2[j] (the sum of squared deviations; population variance M2/n, as SB3's RunningMeanStd).  The

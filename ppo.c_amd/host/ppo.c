@@ -1727,6 +1727,72 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     return 0;
 }
 
+/* ppo_ext.h: one form of the policy head on caller-supplied device arrays */
+int ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float eps, float ent_coeff,
+                           const float* d_log_std, const float* d_action, const float* d_adv, const float* d_old_lp,
+                           float* d_mu, const float* d_x, const float* d_W, const float* d_b, float* d_lp,
+                           float* d_grad_mu, float* d_gx, float* d_gW, float* d_grad_log_std, double* loss) {
+    static float* word = NULL;                    /* [0] the loss, [1] form 0's entropy */
+    static float* glp = NULL;                     /* form 0: ∂L/∂lp [glp_cap] */
+    static long glp_cap = 0;
+    if (form < 0 || form > 4 || m <= 0 || A <= 0 || isnan(eps) || !d_log_std || !d_action || !d_adv || !d_old_lp ||
+        !d_mu || !d_grad_log_std || !loss)
+        return -1;
+    const int net = form >= 2;                    /* the forms that carry the output layer */
+    if (net) {
+        if (n <= 0 || !d_x || !d_W || !d_gx || !d_gW || (form != 3 && !d_b)) return -1;
+        if ((((uintptr_t)d_x | (uintptr_t)d_gx | (uintptr_t)d_W | (uintptr_t)d_gW) & 15u) != 0) return -1;
+    } else if (!d_grad_mu || (form == 0 && !d_lp)) {
+        return -1;
+    }
+    /* the shape, by the kernels' own predicates */
+    if (form == 0 && A > 16384) return 1;         /* log_prob_bwd_kernel: A column sums in 64 KiB of LDS */
+    if (form == 1 && A > 4096) return 1;          /* phip_policy_head's own limit */
+    if (form == 2 && !phip_out_head_supported(1, n, A)) return 1;
+    if (form == 3 && !phip_out_bwd_wide_ok(m, n, A, 1)) return 1;
+    if (!word) word = (float*)phip_malloc(4 * sizeof(float));
+    float* gb = net ? d_gW + (long)A * n : NULL;
+    phip_memset(word, 0, 4 * sizeof(float));
+    phip_memset(d_grad_log_std, 0, sizeof(float) * (size_t)A);
+    if (net) phip_memset(d_gW, 0, sizeof(float) * ((size_t)A * n + A));
+    switch (form) {
+        case 0:
+            if (glp_cap < m) {
+                if (glp) phip_free(glp);
+                glp = (float*)phip_malloc(sizeof(float) * (size_t)m);
+                glp_cap = m;
+            }
+            phip_log_prob(d_mu, d_log_std, d_action, d_lp, m, A);
+            phip_entropy(d_log_std, A, word + 1);
+            phip_policy_loss(d_adv, d_lp, d_old_lp, glp, m, eps, ent_coeff, word + 1, NULL, word);
+            phip_log_prob_bwd(d_mu, d_log_std, d_action, glp, d_grad_mu, d_grad_log_std, m, A);
+            break;
+        case 1:
+            phip_policy_head(d_mu, d_log_std, d_action, d_adv, d_old_lp, m, A, eps, ent_coeff, d_grad_mu,
+                             d_grad_log_std, word, 1);
+            break;
+        case 2:
+            phip_out_head(1, 0, d_x, relu_in, d_W, d_b, m, n, A, NULL, d_log_std, d_action, d_adv, d_old_lp, eps,
+                          ent_coeff, d_mu, d_gx, d_gW, gb, d_grad_log_std, word, NULL);
+            break;
+        case 3:
+            if (!phip_policy_head_bwd_wide(d_mu, d_log_std, d_action, d_adv, d_old_lp, eps, ent_coeff, d_grad_log_std,
+                                           word, d_x, d_W, relu_in, d_gW, gb, d_gx, m, n, A))
+                return 1;
+            break;
+        default:
+            if (!phip_policy_out_fused(d_x, d_W, d_b, d_mu, d_log_std, d_action, d_adv, d_old_lp, eps, ent_coeff,
+                                       d_grad_log_std, word, relu_in, d_gW, gb, d_gx, m, n, A))
+                return 1;
+            break;
+    }
+    phip_sync();
+    float l = 0.f;
+    phip_d2h(&l, word, sizeof(float));
+    *loss = (double)l;
+    return 0;
+}
+
 /* ppo_ext.h: global gradient-norm clipping */
 int ppo_set_max_grad_norm(void* vppo, float max_norm) {
     if (isnan(max_norm)) return -1;
