@@ -468,7 +468,9 @@ int ppo_nn_input_rows(void* nn, float* out, int m);
 /* ---------------- compute precision ---------------- */
 /* 0 = fp32 (default: exact fp32 MFMA GEMMs), 1 = bf16 MFMA GEMMs with fp32 accumulation, fp32
  * master parameters / Adam / heads / GAE, bf16 storage of hidden activations and their gradients
- * (BASELINE config C5).  Returns 0, or −1 for an invalid dtype. */
+ * (BASELINE config C5).  Returns 0, or −1 for an invalid dtype.  The bf16 kernels know ReLU and identity
+ * layers only: dtype 1 on a network with a "tanh" layer (for ppo_set_compute_dtype: in either network)
+ * returns −1 and leaves the setting unchanged; tanh networks run in fp32 mode, on both fp32 GEMM engines. */
 int ppo_set_compute_dtype(void* ppo, int dtype);
 int nn_set_compute_dtype(void* nn, int dtype);          /* NeuralNetwork* */
 
@@ -480,7 +482,9 @@ int    ppo_gemm_tune(int force_cfg, int splitk_target);
  * only queries; returns the previous value */
 int    ppo_gemm_flags(int flags);
 /* average device µs of one launch: op 0 = forward (bias+ReLU), 1 = grad_x, 2 = grad_W (+bias grad),
- * 3 = forward without activation (output layer);
+ * 3 = forward without activation (output layer), 6 = forward (bias+tanh), 7 = grad_x with a tanh layer's
+ * post-activation operand h (ppo_bench_gemm_x3: 4 – 6 are its value-head fold variants, 7 the same grad_x,
+ * 8 its forward with tanh);
  * m = batch, n = in, l = out; cfg −1 = automatic */
 double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg);
 /* two independent C4-shaped minibatch GEMM chains (B rows, `out` outputs), `steps` steps each,

@@ -48,6 +48,11 @@ inline long long gemm_key(int op, int engine, long m, long n, long l) {
            ((long long)(n & 0xFFFF) << 16) | (long long)(l & 0xFFFF);
 }
 
+// tanh′ through the post-activation h: g·(1 − h²) evaluated as g − (g·h)·h, three roundings in this order
+// (the _rn intrinsics are never contracted into a fused multiply-add).  h = ±1 gives exactly 0, NaN in g or
+// h propagates; tests/tanh_ref.py states the same order in numpy.
+__device__ __forceinline__ float tanh_bwd(float g, float h) { return __fsub_rn(g, __fmul_rn(__fmul_rn(g, h), h)); }
+
 // Cross-lane sums on DPP moves (no LDS round trips; a __shfl_xor tree compiles to ds_bpermute,
 // ≈ 100+ cycles of latency per step): sum over each 16-lane DPP row — the xor-1 / xor-2 / quad-swap /
 // half-swap tree — and over the wave (row sums in row order, read as scalars)

@@ -4,6 +4,8 @@
 //   forward   y = x·Wᵀ + b (+ReLU)       mat_mul.cu:122-163 (K1 add_bias + K2 sgemm) + K5 ReLU
 //   grad_x    gx = g·W (·1[y_prev>0])    mat_mul.cu:175-188 (K3) + activation_function.cu:24-29 (K6)
 //   grad_W    gW = gᵀ·x, gb = Σ_m g      mat_mul.cu:195-208 (K4) + neural_network.cu:108-118 (K7)
+// and, with no counterpart in the reference, tanh layers: forward y = tanhf(x·Wᵀ + b) (no mask bits) and
+// grad_x gx = a − (a·h)·h with a = g·W and h the stored post-activation of the layer below (ppo::tanh_bwd).
 //
 // Design (gfx950):
 //  * v_mfma_f32_32x32x2_f32 — exact fp32 (a k-ordered fma chain), 64 FLOP/clk/SIMD, the same
@@ -35,6 +37,9 @@ struct Args {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
     const float* bias; int relu;          // OP_NT epilogue
+    int tanh;                             // OP_NT: tanhf after the bias (relu = 0, no bits); OP_NN: `mask` is a tanh
+                                          // layer's post-activation h and gx = acc − (acc·h)·h.  The host picks the
+                                          // tiled TH kernels from it; the small-M kernel reads it (uniform over a launch).
     const float* mask; int ldmask;        // OP_NN epilogue (post-activation of the previous layer)
     const int* ridx;                      // OP_NT: A row r is memory row ridx[r] (fused gather)
     float* acopy;                         // OP_NT: tn == 0 workgroups write the gathered A rows here
@@ -203,7 +208,12 @@ constexpr int lds_floats() {
 
 // One workgroup's output tile: block b of an nwg-block grid (the kernels below pass their own
 // block id, or an offset one when two GEMMs share a launch).
-template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF>
+// TH: the tanh forms of the forward / grad_x epilogue (forward: tanhf after the bias, no bits; grad_x:
+// acc − (acc·h)·h with h = a.mask at C's own coordinates).  A kernel of its own, chosen on the host from
+// the launch's activation kind: the ReLU / identity kernels (TH = false) are instruction for instruction
+// what they were — inside one kernel the extra epilogue version raised the 128×128 grad_x tile past its
+// 128-VGPR budget (17 spills, also in the paired launch, which never takes a tanh layer).
+template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, bool TH = false>
 __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int nwg, float* __restrict__ lds) {
     constexpr int WARPS_N = 4 / WARPS_M;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
@@ -342,7 +352,12 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
             float bcol = 0.f;
             if (OP == OP_NT && a.bias) bcol = a.bias[colc];
             bool keep[16];
-            if (OP == OP_NN) {                                // mode is wave-uniform: loads unconditional
+            float hv[16];
+            if constexpr (OP == OP_NN && TH) {                // h at C's own coordinates, clamped into [M, N)
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    hv[e] = a.mask[(long)min(r0 + (e & 3) + 8 * (e >> 2), a.M - 1) * a.ldmask + colc];
+            } else if (OP == OP_NN) {                         // mode is wave-uniform: loads unconditional
                 if (a.bits_in) {
                     unsigned wv[16];
 #pragma unroll
@@ -369,7 +384,11 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
                 const bool ok = col_ok && row < a.M;
                 float v = acc[i][j][e];
                 float* dst = a.C + (long)row * a.ldc + col;
-                if (OP == OP_NT) {
+                if constexpr (TH) {
+                    if (OP == OP_NT) v = tanhf(v + bcol);
+                    else v = ppo::tanh_bwd(v, hv[e]);
+                    if (ok) *dst = v;
+                } else if (OP == OP_NT) {
                     v += bcol;
                     if (a.relu) v = v > 0.f ? v : 0.f;
                     if (ok) *dst = v;
@@ -384,17 +403,18 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
                     else *dst = v;
                 }
             }
-            if (OP == OP_NT && a.bits_out && r < 16) {
+            if (!TH && OP == OP_NT && a.bits_out && r < 16) {
                 const int row = r0 + (r & 3) + 8 * (r >> 2);
                 if (row < a.M && c0 < a.N) a.bits_out[(long)row * a.wpr + (c0 >> 5)] = word;
             }
         }
 }
 
-template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF>
+template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, bool TH = false>
 __global__ __launch_bounds__(NT_, min_waves(BM * BN, BK)) void gemm_f32_kernel(Args a) {
+    static_assert(!TH || OP != OP_TN, "tanh epilogues: forward and grad_x only");
     __shared__ __attribute__((aligned(16))) float lds[lds_floats<OP, BM, BN, BK, DBUF>()];
-    gemm_tile<OP, BM, BN, WARPS_M, BK, VEC, DBUF>(a, blockIdx.x, gridDim.x, lds);
+    gemm_tile<OP, BM, BN, WARPS_M, BK, VEC, DBUF, TH>(a, blockIdx.x, gridDim.x, lds);
 }
 
 // grad_W and grad_x of one layer in one launch (both 128x128/BK16, vector loads): blocks
@@ -530,13 +550,16 @@ __global__ __launch_bounds__(64 * SM_WAVES) void gemm_smallm_kernel(Args a) {
             if (OP == OP_NT) {
                 v += bc;
                 if (a.relu) v = v > 0.f ? v : 0.f;
+                else if (a.tanh) v = tanhf(v);               // uniform over the launch; no bits
                 if (ok) a.C[(long)row * a.ldc + col] = v;
                 if (a.bits_out) {
                     const unsigned long long bb = __ballot(ok && v > 0.f);
                     if (r == e) word = h ? (unsigned)(bb >> 32) : (unsigned)bb;
                 }
             } else if (OP == OP_NN) {
-                if (ok) {
+                if (ok && a.tanh) {                         // a.mask = h: acc − (acc·h)·h
+                    a.C[(long)row * a.ldc + col] = ppo::tanh_bwd(v, a.mask[(long)row * a.ldmask + col]);
+                } else if (ok) {
                     bool keep = true;
                     if (a.bits_in) keep = (a.bits_in[(long)row * a.wpr + (n0 >> 5)] >> r) & 1u;
                     else if (a.mask) keep = a.mask[(long)row * a.ldmask + col] > 0.f;
@@ -575,6 +598,18 @@ void launch(Args a) {
     a.flags = g_flags;
     const long grid = (long)a.tiles_m * a.tiles_n * a.splits;
     PPO_REQUIRE(grid > 0 && grid < (1L << 31), "gemm: grid out of range");
+    if constexpr (OP != OP_TN) {
+        if (a.tanh) {                      // the tanh epilogue's own kernels (gemm_tile TH)
+            if (a.vec_a && a.vec_b)
+                PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, true, DBUF, true>), dim3((unsigned)grid),
+                                   dim3(NT_), 0, ppo::stream(), a);
+            else
+                PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, false, DBUF, true>), dim3((unsigned)grid),
+                                   dim3(NT_), 0, ppo::stream(), a);
+            PPO_LAUNCH_CHECK();
+            return;
+        }
+    }
     if (a.vec_a && a.vec_b)
         PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, true, DBUF>), dim3((unsigned)grid), dim3(NT_),
                            0, ppo::stream(), a);
@@ -649,14 +684,15 @@ bool use_smallm(int m, int n, int l) {
     return m <= 1024 && n >= 64 && tiled_wgs < 64;
 }
 
-void fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu, unsigned* bits,
+// act: PHIP_ACT_* (any other nonzero value counts as ReLU, as `relu != 0` did); bits are written for ReLU only
+void fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act, unsigned* bits,
          int cfg, const int* ridx = nullptr, float* acopy = nullptr) {
     Args a{};
     a.ridx = ridx; a.acopy = acopy;
     a.A = x; a.lda = n; a.B = W; a.ldb = n; a.C = y; a.ldc = l;
     a.M = m; a.N = l; a.K = n; a.kchunk = n; a.splits = 1;
-    a.bias = b; a.relu = relu;
-    a.bits_out = bits; a.wpr = ppo_divup(l, 32);
+    a.bias = b; a.tanh = act == PHIP_ACT_TANH; a.relu = act != 0 && !a.tanh;
+    a.bits_out = a.relu ? bits : nullptr; a.wpr = ppo_divup(l, 32);
     a.vec_a = (n % 4 == 0) && aligned16(x);             // kcont, extent K = n
     a.vec_b = (n % 4 == 0) && aligned16(W);
     // small M (rollout over E envs, B = 64 minibatches): split-K inside a workgroup (the fused
@@ -668,21 +704,22 @@ void fwd(float* y, const float* x, const float* W, const float* b, int m, int n,
     launch_cfg<OP_NT>(cfg < 0 ? pick_cfg(OP_NT, m, l) : cfg, a);
 }
 
+// hpost: a tanh layer's post-activation [m, n] (then mask and bits are null): gx = acc − (acc·h)·h
 Args bwd_x_args(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m, int n,
-                int l) {
+                int l, const float* hpost = nullptr) {
     Args a{};
     a.A = g; a.lda = l; a.B = W; a.ldb = n; a.C = gx; a.ldc = n;
     a.M = m; a.N = n; a.K = l; a.kchunk = l; a.splits = 1;
-    a.mask = mask; a.ldmask = n;
-    a.bits_in = bits; a.wpr = ppo_divup(n, 32);
+    a.mask = hpost ? hpost : mask; a.ldmask = n; a.tanh = hpost != nullptr;
+    a.bits_in = hpost ? nullptr : bits; a.wpr = ppo_divup(n, 32);
     a.vec_a = (l % 4 == 0) && aligned16(g);             // kcont, extent K = l
     a.vec_b = (n % 4 == 0) && aligned16(W);             // mncont, extent N = n, ld = n
     return a;
 }
 
 void bwd_x(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m, int n, int l,
-           int cfg) {
-    const Args a = bwd_x_args(gx, g, W, mask, bits, m, n, l);
+           int cfg, const float* hpost = nullptr) {
+    const Args a = bwd_x_args(gx, g, W, mask, bits, m, n, l, hpost);
     if (cfg < 0 && g_force_cfg < 0 && use_smallm(m, l, n)) {
         launch_smallm<OP_NN>(a, a.vec_a);
         return;
@@ -799,36 +836,37 @@ void bwd_pair(float* gW, float* gb, float* gx, const float* g, const float* x, c
 
 extern "C" {
 
-void phip_linear_fwd_bits(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu,
+void phip_linear_fwd_bits(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act,
                           unsigned* bits) {
     if (m <= 0 || l <= 0) return;
     PPO_REQUIRE(y && x && W && n > 0, "phip_linear_fwd: null operand");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(0, 0, m, n, l));
-    fwd(y, x, W, b, m, n, l, relu, relu ? bits : nullptr, -1);
+    fwd(y, x, W, b, m, n, l, act, bits, -1);
 }
 
-void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu) {
-    phip_linear_fwd_bits(y, x, W, b, m, n, l, relu, nullptr);
+void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act) {
+    phip_linear_fwd_bits(y, x, W, b, m, n, l, act, nullptr);
 }
 
 void phip_linear_fwd_gather(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b,
-                            int m, int n, int l, int relu, unsigned* bits) {
+                            int m, int n, int l, int act, unsigned* bits) {
     if (m <= 0 || l <= 0) return;
     PPO_REQUIRE(y && x && ridx && W && n > 0, "phip_linear_fwd_gather: null operand");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(0, 0, m, n, l));
-    fwd(y, x, W, b, m, n, l, relu, relu ? bits : nullptr, -1, ridx, xcopy);
+    fwd(y, x, W, b, m, n, l, act, bits, -1, ridx, xcopy);
 }
 
-void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m,
-                            int n, int l) {
+void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits,
+                            const float* h, int m, int n, int l) {
     if (m <= 0 || n <= 0) return;
     PPO_REQUIRE(gx && g && W && l > 0, "phip_linear_bwd_x: null operand");
+    PPO_REQUIRE(!h || (!mask && !bits), "phip_linear_bwd_x: a tanh layer's h excludes a ReLU mask");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(1, 0, m, n, l));
-    bwd_x(gx, g, W, mask, bits, m, n, l, -1);
+    bwd_x(gx, g, W, mask, bits, m, n, l, -1, h);
 }
 
 void phip_linear_bwd_x(float* gx, const float* g, const float* W, const float* mask, int m, int n, int l) {
-    phip_linear_bwd_x_bits(gx, g, W, mask, nullptr, m, n, l);
+    phip_linear_bwd_x_bits(gx, g, W, mask, nullptr, nullptr, m, n, l);
 }
 
 void phip_linear_bwd_w_ex(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed) {
@@ -865,8 +903,9 @@ int ppo_gemm_tune(int force_cfg, int splitk_target) {
     return kNumCfgs;
 }
 
-// Tuning / roofline utility: average device time (µs) of one launch of `op` (0 fwd, 1 grad_x,
-// 2 grad_W) at the given shape, measured with HIP events on libppo's stream.
+// Tuning / roofline utility: average device time (µs) of one launch of `op` (0 fwd + ReLU, 1 grad_x,
+// 2 grad_W, 3 fwd without activation, 6 fwd + tanh, 7 grad_x with a tanh layer's h operand) at the given
+// shape, measured with HIP events on libppo's stream.
 double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
     ppo::ensure_device();
     const size_t sx = (size_t)m * n, sw = (size_t)l * n, sy = (size_t)m * l;
@@ -879,10 +918,14 @@ double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
     phip_fill_uniform(W, (long)sw, 2, -0.1f, 0.1f);
     phip_fill_uniform(y, (long)(sy > sx ? sy : sx), 3, -1.f, 1.f);
     phip_fill_uniform(b, (long)(l > n ? l : n), 4, -0.1f, 0.1f);
+    float* hp = op == 7 ? (float*)phip_malloc(sizeof(float) * sx) : nullptr;    // a tanh layer's post-activation
+    if (hp) phip_fill_uniform(hp, (long)sx, 5, -1.f, 1.f);
     auto run = [&]() {
         if (op == 0) fwd(y, x, W, b, m, n, l, 1, nullptr, cfg);
         else if (op == 3) fwd(y, x, W, b, m, n, l, 0, nullptr, cfg);        // output layer: no activation
         else if (op == 1) bwd_x(x, y, W, nullptr, nullptr, m, n, l, cfg);
+        else if (op == 6) fwd(y, x, W, b, m, n, l, PHIP_ACT_TANH, nullptr, cfg);     // forward + tanh
+        else if (op == 7) bwd_x(x, y, W, nullptr, nullptr, m, n, l, cfg, hp);         // grad_x with the h read
         else bwd_w(gw, b, y, x, m, n, l, 0, cfg);
     };
     for (int i = 0; i < 3; ++i) run();
@@ -897,7 +940,7 @@ double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
     PPO_CHECK(hipEventElapsedTime(&ms, e0, e1));
     PPO_CHECK(hipEventDestroy(e0));
     PPO_CHECK(hipEventDestroy(e1));
-    phip_free(x); phip_free(W); phip_free(y); phip_free(b); phip_free(gw);
+    phip_free(x); phip_free(W); phip_free(y); phip_free(b); phip_free(gw); phip_free(hp);
     return 1000.0 * ms / (iters > 0 ? iters : 1);
 }
 

@@ -5,6 +5,8 @@
 //   forward   y  = x·Wᵀ + b (+ReLU, +ReLU′ bit mask, + the minibatch gather of x's rows)   NT
 //   grad_x    gx = (g·W) ⊙ 1[y_prev > 0]                                                   NN
 //   grad_W    gW = gᵀ·x, gb = Σ_rows g      (split-K over the batch, f32 atomics)          TN
+// and tanh layers (not in the reference): forward y = tanhf(x·Wᵀ + b), no bits; grad_x gx = a − (a·h)·h, a = g·W,
+// h the layer below's stored post-activation read at gx's own coordinates (the TH kernels).
 //
 // Arithmetic.  Every fp32 operand value splits exactly into three bf16 planes x = x0 + x1 + x2
 // (round-to-nearest v_cvt_pk_bf16_f32 of x, of the residual, of the second residual: x0 carries 8
@@ -56,6 +58,9 @@ struct X3Args {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
     const float* bias; int relu;
+    int tanh;                             // forward: tanhf after the bias (relu = 0, no bits); uniform over a launch
+    const float* hpost;                   // grad_x: a tanh layer's post-activation [M][ldc], read at C's own
+                                          // coordinates — C = acc − (acc·h)·h (null: none)
     const int* ridx; float* acopy;        // forward: fused gather of A's rows + the gathered copy
     unsigned* bits_out; const unsigned* bits_in; int wpr;
     float* gbias;                         // grad_W: bias gradient (Σ over the batch of g)
@@ -349,7 +354,9 @@ struct StageX3 {
 // loop version of their own, grad_x's mask words brought into LDS (BM·BN/32 words, free on entry) by
 // one coalesced pass (they were 16 dependent loads per block).  Element stores in the accumulator
 // layout (each wave store: two 128-B row segments).
-template <int OP, int BM, int BN, int TM, int TN, int NTH, bool YD = false, bool FG = false>
+// TH: the tanh forms (forward: tanhf after the bias, no bits; grad_x: acc − (acc·h)·h, a block's 16 h values loaded
+// as one batch ahead of its stores) — kernels of their own (launch_x3), never with the value-head fold.
+template <int OP, int BM, int BN, int TM, int TN, int NTH, bool YD = false, bool FG = false, bool TH = false>
 __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[TM][TN], unsigned short* lds, int m0,
                                                 int n0, int wm, int wn, int tid) {
     constexpr int WM = TM * 32, WN = TN * 32;
@@ -429,6 +436,13 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                 const int r0 = m0 + lr0;
                 const bool col_ok = col < a.N;
                 unsigned word = 0;
+                float hv[16];
+                if constexpr (TH && OP == OP_NN) {             // clamped into [M, N): every load is in bounds
+                    const int colc = col_ok ? col : a.N - 1;
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        hv[e] = a.hpost[(long)min(r0 + (e & 3) + 8 * (e >> 2), a.M - 1) * a.ldc + colc];
+                }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int dr = (e & 3) + 8 * (e >> 2);
@@ -438,7 +452,8 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                     float* dst = a.C + (long)row * a.ldc + col;
                     if (OP == OP_NT) {
                         v += bcol[j];
-                        if (a.relu) v = v > 0.f ? v : 0.f;
+                        if constexpr (TH) v = tanhf(v);
+                        else if (a.relu) v = v > 0.f ? v : 0.f;
 #ifdef PPO_X3_NTSTORE
                         if (ok) __builtin_nontemporal_store(v, dst);
 #else
@@ -453,6 +468,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                     } else {
                         if (FG) v *= gsh[lr0 + dr];
                         if (masked && !((mk[(lr0 + dr) * WPT + ((c0 - n0) >> 5)] >> r) & 1u)) v = 0.f;
+                        if constexpr (TH) v = ppo::tanh_bwd(v, hv[e]);
 #ifdef PPO_X3_NTSTORE
                         if (ok) __builtin_nontemporal_store(v, dst);
 #else
@@ -468,14 +484,15 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
             if constexpr (YD) ydot_block(yp, i);
         }
     };
-    if (OP == OP_NT && a.bits_out) body(std::true_type{});
+    if (!TH && OP == OP_NT && a.bits_out) body(std::true_type{});
     else body(std::false_type{});
 }
 
 // FOLD: the value-head fold variant (forward: ydot / ypart; grad_x / grad_W: A synthesised from h).
 // The body of one workgroup (block b of a grid of `grid` blocks), a device function so that one launch
 // could run several products' tiles (a grad_W + grad_x pair was measured and not kept, see phip_x3_bwd_w)
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
+          bool TH = false>
 __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     constexpr int NTG = NTH / KG;                                  // threads per k-group
     constexpr int NW = NTG / 64, WARPS_N = NW / WARPS_M;
@@ -920,8 +937,8 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     }
     if constexpr (OP != OP_TN) {
         static_assert(BM * (BN / 32 + 1) * 4 <= KG * NS * BUF * 2, "x3 epilogue: mask words exceed LDS");
-        x3_epilogue_out<OP, BM, BN, TM, TN, NTH, OP == OP_NT && FOLD != 0, OP == OP_NN && FOLD != 0>(a, acc, lds, m0,
-                                                                                                  n0, wm, wn, tid);
+        x3_epilogue_out<OP, BM, BN, TM, TN, NTH, OP == OP_NT && FOLD != 0, OP == OP_NN && FOLD != 0, TH>(
+            a, acc, lds, m0, n0, wm, wn, tid);
         if (ABL & 32) stamp(3);
         return;
     }
@@ -994,9 +1011,10 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     if (ABL & 32) stamp(3);
 }
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
+          bool TH = false>
 __global__ __launch_bounds__(NTH, OCC) void gemm_x3_kernel(X3Args a) {
-    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB>(a, (int)blockIdx.x, (int)gridDim.x);
+    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, TH>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 #ifdef PPO_X3_DIAG
@@ -1005,8 +1023,18 @@ int g_x3_ablate = -1;
 
 int g_x3_last_slots = 0;                 // the last launch's ypart slots (tiles_n × waves along N)
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
+          bool TH = false>
 void launch_x3(X3Args a) {
+    // a tanh launch (forward: a.tanh; grad_x: a.hpost) runs the TH kernels — the tanh epilogue compiled apart, so
+    // the ReLU / identity kernels keep the registers they had (x3_epilogue_out)
+    if constexpr (!TH && OP != OP_TN && FOLD == 0 && ABL == 0) {
+        if (OP == OP_NT ? a.tanh != 0 : a.hpost != nullptr) {
+            launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, true>(a);
+            return;
+        }
+    }
+    PPO_REQUIRE(TH || (!a.tanh && !a.hpost), "gemm_x3: tanh operands on a variant without the tanh epilogue");
     a.tiles_m = ppo_divup(a.M, BM);
     a.tiles_n = ppo_divup(a.N, BN);
     g_x3_last_slots = a.tiles_n * (NTH / KG / 64 / WARPS_M);
@@ -1034,7 +1062,7 @@ void launch_x3(X3Args a) {
             a.vh_ypart = nullptr;
         }
     }
-    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB>;
+    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, TH>;
     if (lds > 64 * 1024) {
         static bool attr = false;                      // once per instantiation (the whole LDS)
         if (!attr) {
@@ -1243,15 +1271,17 @@ int phip_x3_supported(int op, int m, int n, int l) {
 // ydot / ypart (value-head fold): each wave's partial y = Σ relu(z)·ydot over its columns, per row, into
 // ypart [slots][m]; returns slots (0 without the fold)
 int phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                      int n, int l, int relu, unsigned* bits, const float* ydot, float* ypart) {
+                      int n, int l, int act, unsigned* bits, const float* ydot, float* ypart) {
     if (m <= 0 || l <= 0) return 0;
     PPO_REQUIRE(y && x && W && n > 0 && n % 4 == 0 && al16(x) && al16(W), "phip_x3_fwd: unsupported operands");
     PPO_REQUIRE(!ydot || ypart, "phip_x3_fwd: value-head fold without its partial buffer");
+    PPO_REQUIRE(!ydot || act != PHIP_ACT_TANH, "phip_x3_fwd: the value-head fold takes a ReLU layer only");
+    const int relu = act != 0 && act != PHIP_ACT_TANH;       // any other nonzero value: ReLU, as `relu != 0` was
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(0, 1, m, n, l));
     X3Args a{};
     a.A = x; a.lda = n; a.B = W; a.ldb = n; a.C = y; a.ldc = l;
     a.M = m; a.N = l; a.K = n; a.kchunk = n; a.splits = 1;
-    a.bias = b; a.relu = relu; a.ridx = ridx; a.acopy = ridx ? xcopy : nullptr;
+    a.bias = b; a.relu = relu; a.tanh = act == PHIP_ACT_TANH; a.ridx = ridx; a.acopy = ridx ? xcopy : nullptr;
     a.bits_out = relu ? bits : nullptr; a.wpr = ppo_divup(l, 32);
     a.ydot = ydot; a.ypart = ypart;
     launch_cfg_x3<OP_NT>(pick_x3(m, l, OP_NT), a);
@@ -1259,24 +1289,27 @@ int phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, c
 }
 
 void phip_x3_fwd(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                 int n, int l, int relu, unsigned* bits) {
-    (void)phip_x3_fwd_vhead(y, x, ridx, xcopy, W, b, m, n, l, relu, bits, nullptr, nullptr);
+                 int n, int l, int act, unsigned* bits) {
+    (void)phip_x3_fwd_vhead(y, x, ridx, xcopy, W, b, m, n, l, act, bits, nullptr, nullptr);
 }
 
 // the upper layer's gradient A = g [m, l]; value-head fold (fold_g): A = the 0/1 mask words of h
 // (fold_bits [m][⌈l/32⌉]), W scaled per k-row by the output weights fold_w as it is staged (diag(w)·W), the
 // product scaled by fold_g per row — grad_x = diag(g)·(mask·diag(w)·W) ⊙ the input mask
-void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
-                        const float* W, const unsigned* bits, int m, int n, int l) {
+// hpost (without the fold only): a tanh layer below's post-activation [m, n] — gx = acc − (acc·h)·h
+static void x3_bwd_x(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
+                     const float* W, const unsigned* bits, const float* hpost, int m, int n, int l) {
     if (m <= 0 || n <= 0) return;
     PPO_REQUIRE(gx && (g || fold_bits) && W && l > 0 && l % 4 == 0 && n % 4 == 0 && (!g || al16(g)) && al16(W),
                 "phip_x3_bwd_x: unsupported operands");
     PPO_REQUIRE(!fold_bits || (fold_g && fold_w), "phip_x3_bwd_x: value-head fold operands");
+    PPO_REQUIRE(!hpost || (!fold_bits && !bits), "phip_x3_bwd_x: a tanh layer's h excludes a ReLU mask and the fold");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(1, 1, m, n, l));
     X3Args a{};
     a.A = fold_bits ? W : g; a.lda = l; a.B = W; a.ldb = n; a.C = gx; a.ldc = n;
     a.M = m; a.N = n; a.K = l; a.kchunk = l; a.splits = 1;
     a.bits_in = bits; a.wpr = ppo_divup(n, 32);
+    a.hpost = hpost;
     a.fold_bits = fold_bits; a.fold_wpr = ppo_divup(l, 32); a.fold_g = fold_g; a.fold_w = fold_w;
     ppo::PendingReduce& pr = ppo::g_pending[phip_side_active() ? 1 : 0];
     if (pr.on) {
@@ -1287,8 +1320,14 @@ void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, co
     launch_cfg_x3<OP_NN>(pick_x3(m, n, OP_NN), a);
 }
 
-void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, int m, int n, int l) {
-    phip_x3_bwd_x_fold(gx, g, nullptr, nullptr, nullptr, W, bits, m, n, l);
+void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
+                        const float* W, const unsigned* bits, int m, int n, int l) {
+    x3_bwd_x(gx, g, fold_bits, fold_g, fold_w, W, bits, nullptr, m, n, l);
+}
+
+void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int m, int n,
+                   int l) {
+    x3_bwd_x(gx, g, nullptr, nullptr, nullptr, W, bits, h, m, n, l);
 }
 
 void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
@@ -1398,7 +1437,8 @@ int ppo_gemm_x3_tune(int force_cfg, int splitk_target) {
 
 // average device µs of one launch (op 0 forward + bias + ReLU + bits, 1 grad_x with bits, 2 grad_W
 // + bias grad (split-K from zero), 3 forward without activation, 4 – 6 the value-head fold variants of
-// 0 – 2); cfg −1 = automatic
+// 0 – 2, 7 grad_x with a tanh layer's h operand, 8 forward + bias + tanh — ppo_bench_gemm's 6, which the fold
+// holds here); cfg −1 = automatic
 double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int splitk_target) {
     ppo::ensure_device();
     const size_t sx = (size_t)m * n, sw = (size_t)l * n, sy = (size_t)m * l;
@@ -1418,12 +1458,16 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
     g_split_x3 = splitk_target;
     // ops 4 – 6: the value-head fold variants (forward with the partial dots; grad_x from the mask words
     // with the g row scale; grad_W from h with g / w scales and the output layer's gW)
-    float* fold = (op >= 4) ? (float*)phip_malloc(4 * ((size_t)m * (2 * ppo_divup(l, 64) + 1) + (size_t)l)) : nullptr;
+    float* hp = op == 7 ? (float*)phip_malloc(4 * sx) : nullptr;          // a tanh layer's post-activation [m, n]
+    if (hp) phip_fill_uniform(hp, (long)sx, 6, -1.f, 1.f);
+    float* fold = (op >= 4 && op <= 6) ? (float*)phip_malloc(4 * ((size_t)m * (2 * ppo_divup(l, 64) + 1) + (size_t)l)) : nullptr;
     if (fold) phip_fill_uniform(fold, (long)m * (2 * ppo_divup(l, 64) + 1) + l, 5, -0.1f, 0.1f);
     auto run = [&]() {
         if (op == 0) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits);
         else if (op == 3) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, 0, nullptr);
-        else if (op == 1) phip_x3_bwd_x(x, y, W, bits, m, n, l);
+        else if (op == 1) phip_x3_bwd_x(x, y, W, bits, nullptr, m, n, l);
+        else if (op == 7) phip_x3_bwd_x(x, y, W, nullptr, hp, m, n, l);
+        else if (op == 8) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, PHIP_ACT_TANH, nullptr);
         else if (op == 4) phip_x3_fwd_vhead(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits, fold, fold + l);
         else if (op == 5) phip_x3_bwd_x_fold(x, nullptr, bits, fold, fold + m, W, bits, m, n, l);
         else if (op == 6) phip_x3_bwd_w_fold(gw, b, y, fold, fold + m, fold + m + l, x, m, n, l, 0);
@@ -1444,6 +1488,7 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
     g_force_x3 = saved;
     g_split_x3 = saved_split;
     phip_free(x); phip_free(W); phip_free(y); phip_free(b); phip_free(gw); phip_free(bits); phip_free(fold);
+    phip_free(hp);
     return 1000.0 * ms / (iters > 0 ? iters : 1);
 }
 

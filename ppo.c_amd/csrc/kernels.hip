@@ -1,6 +1,7 @@
 // kernels.hip — element-wise and head kernels of the PPO update (gfx950).
 //
 //   ReLU / ReLU′                  activation_function.cu:17-43   (K5, K6 when not fused)
+//   tanh / tanh′                  (no reference counterpart; when not fused into a GEMM epilogue)
 //   MSE loss + derivative         loss.cu:25-83                  (K8 + K9 fused, no host sync)
 //   Gaussian log-prob / backward  policy.cu:67-74,101-169        (K11, K12; correct for any A)
 //   entropy                       policy.cu:171-193
@@ -55,6 +56,16 @@ __global__ void relu_kernel(float* __restrict__ x, long n) {
 __global__ void relu_bwd_kernel(const float* __restrict__ y, float* __restrict__ g, long n) {
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
         if (!(y[i] > 0.f)) g[i] = 0.f;
+}
+
+__global__ void tanh_kernel(float* __restrict__ x, long n) {
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) x[i] = tanhf(x[i]);
+}
+
+// g ← g·(1 − y²), y the post-activation, in the GEMM epilogues' order: g − (g·y)·y (no fused multiply-add)
+__global__ void tanh_bwd_kernel(const float* __restrict__ y, float* __restrict__ g, long n) {
+    for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB)
+        g[i] = ppo::tanh_bwd(g[i], y[i]);
 }
 
 // fp32 → bf16 (round to nearest even, NaN preserved: the plain cast lowers to v_cvt_pk_bf16_f32)
@@ -362,6 +373,20 @@ void phip_relu_bwd(const float* y, float* g, long count) {
     if (count <= 0) return;
     ppo::ProfScope ps(PPO_K_OTHER, 12.0 * count);
     hipLaunchKernelGGL(relu_bwd_kernel, dim3(grid_for(count, 4)), dim3(TPB), 0, ppo::stream(), y, g, count);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_tanh(float* x, long count) {
+    if (count <= 0) return;
+    ppo::ProfScope ps(PPO_K_OTHER, 8.0 * count);
+    hipLaunchKernelGGL(tanh_kernel, dim3(grid_for(count, 4)), dim3(TPB), 0, ppo::stream(), x, count);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_tanh_bwd(const float* y, float* g, long count) {
+    if (count <= 0) return;
+    ppo::ProfScope ps(PPO_K_OTHER, 12.0 * count);
+    hipLaunchKernelGGL(tanh_bwd_kernel, dim3(grid_for(count, 4)), dim3(TPB), 0, ppo::stream(), y, g, count);
     PPO_LAUNCH_CHECK();
 }
 

@@ -48,21 +48,27 @@ typedef struct {
 } PhipVClip;
 
 /* ---------------- dense layers (gemm.hip) ---------------- */
-/* y[m,l] = x[m,n]·W[l,n]ᵀ + b[l], optional ReLU (mat_mul.cu:132-163 + K1/K5 fused) */
-void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu);
-/* same, and (relu) writes the ReLU′ mask as bits: word (row, c/32) bit c%32 = y[row, c] > 0,
+/* activation kinds of the forward launchers' `act` argument (host: nn_act_kind); the value is uniform over a
+ * launch.  PHIP_ACT_TANH applies tanhf after the bias and writes no mask bits: tanh′ = 1 − h² needs only the
+ * stored post-activation h, which the grad_x launchers take as their `h` operand */
+enum { PHIP_ACT_NONE = 0, PHIP_ACT_RELU = 1, PHIP_ACT_TANH = 2 };
+/* y[m,l] = act(x[m,n]·W[l,n]ᵀ + b[l]) (mat_mul.cu:132-163 + K1/K5 fused) */
+void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act);
+/* same, and (act = relu) writes the ReLU′ mask as bits: word (row, c/32) bit c%32 = y[row, c] > 0,
  * ⌈l/32⌉ words per row — 1/32 of the bytes the float mask costs the backward */
-void phip_linear_fwd_bits(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int relu,
+void phip_linear_fwd_bits(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act,
                           unsigned* bits);
 /* gx[m,n] = g[m,l]·W[l,n]; if mask: gx = (mask > 0) ? gx : 0 (K3 + K6 fused) */
 void phip_linear_bwd_x(float* gx, const float* g, const float* W, const float* mask, int m, int n, int l);
 /* forward whose input row r is x[ridx[r]] (the minibatch gather fused into layer 0); the gathered
  * rows are also written to xcopy[m, n] (for the layer's grad_W) when xcopy != NULL */
 void phip_linear_fwd_gather(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b,
-                            int m, int n, int l, int relu, unsigned* bits);
-/* same with the mask given as bits (phip_linear_fwd_bits layout, ⌈n/32⌉ words per row) */
-void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m,
-                            int n, int l);
+                            int m, int n, int l, int act, unsigned* bits);
+/* same with the mask given as bits (phip_linear_fwd_bits layout, ⌈n/32⌉ words per row); or, for a tanh
+ * layer below, h [m, n] (ld = n) its stored post-activation: gx = acc − (acc·h)·h in fp32 (mask and bits
+ * are then NULL) */
+void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits,
+                            const float* h, int m, int n, int l);
 /* gW[l,n] = g[m,l]ᵀ·x[m,n] and gb[l] = Σ_m g[m,l] (K4 + K7 fused); overwrites */
 void phip_linear_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l);
 /* same, with gW/gb already zero on entry when `zeroed` (one memset per backward instead of two per layer) */
@@ -88,17 +94,20 @@ void phip_linear16_bwd_w(float* gW, float* gb, const void* g, int tg, const void
  * bias/ReLU/ReLU' bits; grad_x with the bit mask; grad_W (+gb) split-K. */
 int  phip_x3_supported(int op, int m, int n, int l);
 void phip_x3_fwd(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                 int n, int l, int relu, unsigned* bits);
+                 int n, int l, int act, unsigned* bits);
 /* the next phip_x3_bwd_w(_fold) leaves its split-K slab reduce to the next phip_x3_bwd_x(_fold) on the same
  * stream (extra workgroups of that launch) — the caller guarantees grad_x follows */
 void phip_x3_defer_reduce(int on);
-void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, int m, int n, int l);
+/* bits: the ReLU′ mask of the layer below (NULL: none); h: a tanh layer below's post-activation [m, n], read
+ * at gx's own coordinates — gx = acc − (acc·h)·h (NULL: none) */
+void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int m, int n,
+                   int l);
 void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed);
 /* value-head fold (nn_value_fold_step): forward partial y dots (returns ypart slots); backward with the
  * upper gradient g·w·1[h > 0] applied as the 0/1 mask of h with g, w as row / column scales (grad_x:
  * W pre-scaled by w) and the output layer's gW */
 int  phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                       int n, int l, int relu, unsigned* bits, const float* ydot, float* ypart);
+                       int n, int l, int act, unsigned* bits, const float* ydot, float* ypart);
 void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
                         const float* W, const unsigned* bits, int m, int n, int l);
 void phip_x3_bwd_w_fold(float* gW, float* gb, const float* h, const float* fold_g, const float* fold_w, float* fold_gw,
@@ -181,6 +190,9 @@ unsigned* phip_cluster_err_dev(void);  /* device pointer of the shared error wor
 /* ---------------- element-wise / heads (kernels.hip) ---------------- */
 void phip_relu(float* x, long count);
 void phip_relu_bwd(const float* y, float* g, long count);
+/* x ← tanhf(x); g ← g − (g·y)·y with y the post-activation (tanh′ = 1 − y²) */
+void phip_tanh(float* x, long count);
+void phip_tanh_bwd(const float* y, float* g, long count);
 /* y += x (host-pointer API: the reference's CPU backward accumulates, mat_mul.cu:67,79) */
 void phip_axpy(float* y, const float* x, long count);
 /* d_loss[0] = Σ(t−y)²/count (written), d_loss_accum[0] += same (if non-NULL);

@@ -41,7 +41,9 @@ void lin_bwd_w(float* gW, const float* g, const float* x, int m, int n, int l);
 /* neural_network.c internals used by policy.c / ppo.c */
 NeuralNetwork* nn_create_ex(int* layer_sizes, char** activation_functions, int num_layers, long extra_floats,
                             int init_from_rand);
-int  nn_is_relu(const NeuralNetwork* nn, int layer);
+int  nn_act_kind(const NeuralNetwork* nn, int layer);   /* 0 none, 1 relu, 2 tanh (ppo_hip.h PHIP_ACT_*) */
+int  nn_is_relu(const NeuralNetwork* nn, int layer);    /* kind == 1 */
+int  nn_has_tanh(const NeuralNetwork* nn);              /* any layer of kind 2 */
 void nn_ensure_act(NeuralNetwork* nn, int m);
 void nn_ensure_grad(NeuralNetwork* nn, int m);
 /* device forward using d_x as layer-0 input (no copy) */

@@ -68,11 +68,33 @@ void ReLU_derivative(float* x, float* grad, int m, int n) {
     phip_d2h(grad, dg, sizeof(float) * cnt);
 }
 
+/* tanh (no counterpart in the reference): x ← tanhf(x); grad ← grad − (grad·x)·x, x the post-activation */
+void Tanh_cuda(float* x, int m, int n) { phip_tanh(x, (long)m * n); }
+void Tanh_derivative_cuda(float* x, float* grad, int m, int n) { phip_tanh_bwd(x, grad, (long)m * n); }
+
+void Tanh(float* x, int m, int n) {
+    const size_t cnt = (size_t)m * n;
+    float* d = stage_up(ST_A, x, cnt);
+    phip_tanh(d, (long)cnt);
+    phip_d2h(x, d, sizeof(float) * cnt);
+}
+
+void Tanh_derivative(float* x, float* grad, int m, int n) {
+    const size_t cnt = (size_t)m * n;
+    float* dx = stage_up(ST_A, x, cnt);
+    float* dg = stage_up(ST_B, grad, cnt);
+    phip_tanh_bwd(dx, dg, (long)cnt);
+    phip_d2h(grad, dg, sizeof(float) * cnt);
+}
+
 static ActivationFunction* build(const char* name, int device) {
     ActivationFunction* a = (ActivationFunction*)xmalloc(sizeof(ActivationFunction));
     if (name && strcmp(name, "relu") == 0) {
         a->activation = device ? &ReLU_cuda : &ReLU;
         a->activation_derivative = device ? &ReLU_derivative_cuda : &ReLU_derivative;
+    } else if (name && strcmp(name, "tanh") == 0) {
+        a->activation = device ? &Tanh_cuda : &Tanh;
+        a->activation_derivative = device ? &Tanh_derivative_cuda : &Tanh_derivative;
     } else {                      /* any other name: identity (activation_function.cu:46-73) */
         a->activation = NULL;
         a->activation_derivative = NULL;

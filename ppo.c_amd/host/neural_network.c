@@ -9,6 +9,7 @@
  *   backward : gW_i, gb_i = g_{i+1}ᵀ·y_i, Σ g_{i+1}             (one kernel per layer)
  *              g_i = (g_{i+1}·W_i) ⊙ 1[y_i > 0]                (one kernel per layer, skipped
  *                                                               for layer 0 in the update)
+ *              tanh below: g_i = a − (a·y_i)·y_i, a = g_{i+1}·W_i  (the same kernel, y_i read in its epilogue)
  */
 #include "internal.h"
 
@@ -17,9 +18,22 @@
 #include <stdlib.h>
 #include <string.h>
 
-int nn_is_relu(const NeuralNetwork* nn, int layer) {
+/* 0 none (identity), 1 relu, 2 tanh (ppo_hip.h PHIP_ACT_*), decided by the layer's function pointer: a non-NULL
+ * pointer alone no longer means ReLU */
+int nn_act_kind(const NeuralNetwork* nn, int layer) {
     const ActivationFunction* a = nn->layers[layer].d_activation_function;
-    return a && a->activation != NULL;
+    if (!a || a->activation == NULL) return PHIP_ACT_NONE;
+    if (a->activation == &Tanh_cuda || a->activation == &Tanh) return PHIP_ACT_TANH;
+    return PHIP_ACT_RELU;         /* ReLU_cuda; any other non-NULL pointer reads as ReLU, as it always did */
+}
+
+int nn_is_relu(const NeuralNetwork* nn, int layer) { return nn_act_kind(nn, layer) == PHIP_ACT_RELU; }
+
+/* the fused and single-launch paths know ReLU and identity only: a network with a tanh layer declines them */
+int nn_has_tanh(const NeuralNetwork* nn) {
+    for (int i = 0; i < nn->num_layers - 1; i++)
+        if (nn_act_kind(nn, i) == PHIP_ACT_TANH) return 1;
+    return 0;
 }
 
 /* ---- host mirror <-> HBM reconciliation ------------------------------------------------------
@@ -285,7 +299,7 @@ void lin_fwd(float* y, const float* x, const float* W, const float* b, int m, in
 }
 void lin_bwd_x(float* gx, const float* g, const float* W, int m, int n, int l) {
     if (use_x3(m) && phip_x3_supported(1, m, n, l) && al16(gx) && al16(g) && al16(W))
-        phip_x3_bwd_x(gx, g, W, NULL, m, n, l);
+        phip_x3_bwd_x(gx, g, W, NULL, NULL, m, n, l);
     else phip_linear_bwd_x(gx, g, W, NULL, m, n, l);
 }
 void lin_bwd_w(float* gW, const float* g, const float* x, int m, int n, int l) {
@@ -334,18 +348,18 @@ static void nn_forward_dev_upto(NeuralNetwork* nn, const float* d_x, const int* 
         Layer* ly = &nn->layers[i];
         float* out = nn->layers[i + 1].d_input;
         const int n = ly->input_size, l = ly->output_size;
+        const int act = nn_act_kind(nn, i);     /* the kernels write mask bits for ReLU only (tanh′ reads h) */
         if (fold && i == upto - 1) {            /* nn_value_fold_ok: the x3 engine takes this layer */
             fold->slots = phip_x3_fwd_vhead(out, in, i == 0 ? d_rows : NULL, i == 0 ? d_xcopy : NULL, ly->d_weights,
-                                            ly->d_biases, m, n, l, nn_is_relu(nn, i), act_bits(nn, i + 1), fold->w,
-                                            fold->ypart);
+                                            ly->d_biases, m, n, l, act, act_bits(nn, i + 1), fold->w, fold->ypart);
         } else if (use_x3_layer(m, n, l) && phip_x3_supported(0, m, n, l)) {
             phip_x3_fwd(out, in, i == 0 ? d_rows : NULL, i == 0 ? d_xcopy : NULL, ly->d_weights, ly->d_biases, m, n,
-                        l, nn_is_relu(nn, i), act_bits(nn, i + 1));
+                        l, act, act_bits(nn, i + 1));
         } else if (i == 0 && d_rows) {
-            phip_linear_fwd_gather(out, in, d_rows, d_xcopy, ly->d_weights, ly->d_biases, m, n, l, nn_is_relu(nn, i),
+            phip_linear_fwd_gather(out, in, d_rows, d_xcopy, ly->d_weights, ly->d_biases, m, n, l, act,
                                    act_bits(nn, i + 1));
         } else {
-            phip_linear_fwd_bits(out, in, ly->d_weights, ly->d_biases, m, n, l, nn_is_relu(nn, i), act_bits(nn, i + 1));
+            phip_linear_fwd_bits(out, in, ly->d_weights, ly->d_biases, m, n, l, act, act_bits(nn, i + 1));
         }
         in = out;
     }
@@ -397,10 +411,12 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
     nn_ensure_grad(nn, m);
     const int L = nn->num_layers - 1;
     const float* g = d_grad_out;
-    if (top == L && nn_is_relu(nn, L - 1)) {      /* output activation: mask a copy (rare; the reference uses "none") */
+    if (top == L && nn_act_kind(nn, L - 1) != PHIP_ACT_NONE) {   /* output activation: its derivative on a copy
+                                                                  * (rare; the reference uses "none") */
         float* top = nn->layers[L].d_grad_x;
         if (top != d_grad_out) phip_d2d(top, d_grad_out, sizeof(float) * (size_t)m * nn->output_size);
-        phip_relu_bwd(nn->layers[L].d_input, top, (long)m * nn->output_size);
+        if (nn_act_kind(nn, L - 1) == PHIP_ACT_TANH) phip_tanh_bwd(nn->layers[L].d_input, top, (long)m * nn->output_size);
+        else phip_relu_bwd(nn->layers[L].d_input, top, (long)m * nn->output_size);
         g = top;
     }
     /* one memset for every layer's gradient (split-K grad_W accumulates atomically);
@@ -440,6 +456,10 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
         const int want_gx = i > 0 || want_grad_x0;
         const int relu_in = i > 0 && nn_is_relu(nn, i - 1);
         const unsigned* bits = relu_in && nn->bits_m == m ? act_bits(nn, i) : NULL;   /* this forward's bits */
+        /* a tanh layer below: grad_x's epilogue reads its stored post-activation, gx = acc − (acc·h)·h; bits are
+         * never required (nor written) for it.  The paired launch and the wide output pass know ReLU masks
+         * only: they are not taken, grad_W and grad_x go out as two launches */
+        const float* hin = i > 0 && nn_act_kind(nn, i - 1) == PHIP_ACT_TANH ? ly->d_input : NULL;
         if (fold && i == top - 1) {
             /* grad_W = diag(w)·(maskᵀ·diag(g)·x), grad_b = diag(w)·maskᵀ·g, the output layer's gW = Σ g·h;
              * grad_x = diag(g)·(mask·diag(w)·W) ⊙ the input mask (gemm_x3.hip) */
@@ -452,7 +472,7 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
                 phip_x3_bwd_x_fold(ly->d_grad_x, NULL, act_bits(nn, i + 1), fold->g, fold->w, ly->d_weights, bits, m, n,
                                    l);
             }
-        } else if (i == L - 1 && want_gx && (!relu_in || bits) &&
+        } else if (i == L - 1 && want_gx && !hin && (!relu_in || bits) &&
             phip_out_bwd_wide(ly->d_grad_weights, ly->d_grad_biases, ly->d_grad_x, g, x, ly->d_weights, relu_in, m, n,
                               l)) {
             /* wide output layer (A = 17): grad_x and grad_W in one pass over the rows (out_head.hip) */
@@ -460,15 +480,15 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
             const int pair = want_gx && (!relu_in || bits);
             phip_x3_defer_reduce(pair);                       /* its slab reduce rides on grad_x */
             phip_x3_bwd_w(ly->d_grad_weights, ly->d_grad_biases, g, x, m, n, l, 1);
-            if (pair) phip_x3_bwd_x(ly->d_grad_x, g, ly->d_weights, bits, m, n, l);
-            else if (want_gx) phip_linear_bwd_x_bits(ly->d_grad_x, g, ly->d_weights, ly->d_input, NULL, m, n, l);
-        } else if (want_gx && (!relu_in || bits)) {
+            if (pair) phip_x3_bwd_x(ly->d_grad_x, g, ly->d_weights, bits, hin, m, n, l);
+            else if (want_gx) phip_linear_bwd_x_bits(ly->d_grad_x, g, ly->d_weights, ly->d_input, NULL, NULL, m, n, l);
+        } else if (want_gx && !hin && (!relu_in || bits)) {
             phip_linear_bwd_pair(ly->d_grad_weights, ly->d_grad_biases, ly->d_grad_x, g, x, ly->d_weights, bits, m, n,
                                  l, 1);
         } else {
             phip_linear_bwd_w_ex(ly->d_grad_weights, ly->d_grad_biases, g, x, m, n, l, 1);
             if (want_gx)
-                phip_linear_bwd_x_bits(ly->d_grad_x, g, ly->d_weights, relu_in ? ly->d_input : NULL, NULL, m, n, l);
+                phip_linear_bwd_x_bits(ly->d_grad_x, g, ly->d_weights, relu_in ? ly->d_input : NULL, NULL, hin, m, n, l);
         }
         g = ly->d_grad_x;
         if (reduce_extra >= 0) bucket_flush(nn, i, &hi);
@@ -484,7 +504,8 @@ int nn_out_head_ok(const NeuralNetwork* nn, int head) {
     const char* e = getenv("PPO_OUT_HEAD");
     if ((e && e[0] == '0') || phip_gemm_deterministic()) return 0;     /* its gW sums use f32 atomics */
     const int L = nn->num_layers - 1;
-    if (L < 2 || nn_is_relu(nn, L - 1)) return 0;
+    if (L < 2 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE) return 0;
+    if (nn_has_tanh(nn)) return 0;          /* the head kernels take relu_in: a ReLU mask or none */
     if (nn->dtype == 1 && (head != 0 || nn->param_offset[L - 1] % 8 != 0)) return 0;   /* W shadow: 16-B rows */
     return phip_out_head_supported(head, nn->layers[L - 1].input_size, nn->layers[L - 1].output_size);
 }
@@ -525,7 +546,9 @@ int nn_value_fold_ok(const NeuralNetwork* nn, int m) {
     const char* e = getenv("PPO_VALUE_FOLD");
     if ((e && e[0] == '0') || phip_gemm_deterministic()) return 0;     /* atomics in the gradient sums */
     const int L = nn->num_layers - 1;
-    if (nn->dtype != 0 || L < 2 || nn->output_size != 1 || nn_is_relu(nn, L - 1) || !nn_is_relu(nn, L - 2)) return 0;
+    if (nn->dtype != 0 || L < 2 || nn->output_size != 1 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE ||
+        !nn_is_relu(nn, L - 2) || nn_has_tanh(nn))       /* its backward reads ReLU masks only */
+        return 0;
     const Layer* hid = &nn->layers[L - 2];
     const int n = hid->input_size, l = hid->output_size;
     return use_x3_layer(m, n, l) && phip_x3_supported(0, m, n, l) && phip_x3_supported(1, m, n, l) &&
@@ -566,7 +589,8 @@ void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, 
  * flat gradient layout (gb after gW), no deterministic-GEMM request (the head's f32 atomics) */
 int nn_policy_wide_ok(const NeuralNetwork* nn, int m) {
     const int L = nn->num_layers - 1;
-    if (nn->dtype != 0 || L < 2 || nn_is_relu(nn, L - 1) || phip_gemm_deterministic()) return 0;
+    if (nn->dtype != 0 || L < 2 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE || phip_gemm_deterministic()) return 0;
+    if (nn_has_tanh(nn)) return 0;          /* the wide head and the fused output layer take relu_in only */
     const Layer* ly = &nn->layers[L - 1];
     if (nn->param_offset[L - 1] % 4 != 0) return 0;                     /* 16-B aligned W / gW */
     return phip_out_bwd_wide_ok(m, ly->input_size, ly->output_size, 1);
@@ -678,6 +702,7 @@ void nn_sync_w16(NeuralNetwork* nn) {
 int nn_set_compute_dtype(void* vnn, int dtype) {
     NeuralNetwork* nn = (NeuralNetwork*)vnn;
     if (!nn || (dtype != 0 && dtype != 1)) return -1;
+    if (dtype == 1 && nn_has_tanh(nn)) return -1;      /* the bf16 kernels know ReLU and identity: setting unchanged */
     if (dtype == 1 && !nn->d_w16) nn->d_w16 = (unsigned short*)phip_malloc(sizeof(unsigned short) * (size_t)nn->num_params);
     nn->dtype = dtype;
     nn->bits_m = -1;

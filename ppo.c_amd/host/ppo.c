@@ -547,6 +547,7 @@ static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
     if (nn->dtype != 0 || L < 1 || L > 8 || !adam->flat || adam->weights[0] != nn->d_params ||
         adam->grad_weights[0] != nn->d_grads)
         return -1;
+    if (nn_has_tanh(nn)) return -1;      /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
     for (int i = 0; i < L; i++)
         if (nn->layers[i].input_size > max_w || nn->layers[i].output_size > max_w) return -1;
     long nw = 0;
@@ -2037,6 +2038,8 @@ PPO* load_ppo(const char* filename, bool use_cuda) {
 int ppo_set_compute_dtype(void* vppo, int dtype) {
     PPO* ppo = (PPO*)vppo;
     if (!ppo) return -1;
+    /* bf16 mode knows ReLU and identity: a tanh layer in either network declines it, both left as they were */
+    if (dtype == 1 && (nn_has_tanh(ppo->V) || nn_has_tanh(ppo->policy->mu))) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;
     return nn_set_compute_dtype(ppo->policy->mu, dtype);
 }

@@ -207,6 +207,10 @@ _SIGS = {
     "ReLU_derivative": (None, [_P, _P, C.c_int, C.c_int]),
     "ReLU_cuda": (None, [_P, C.c_int, C.c_int]),
     "ReLU_derivative_cuda": (None, [_P, _P, C.c_int, C.c_int]),
+    "Tanh": (None, [_P, C.c_int, C.c_int]),
+    "Tanh_derivative": (None, [_P, _P, C.c_int, C.c_int]),
+    "Tanh_cuda": (None, [_P, C.c_int, C.c_int]),
+    "Tanh_derivative_cuda": (None, [_P, _P, C.c_int, C.c_int]),
     "mean_squared_error": (C.c_float, [_P, _P, C.c_int, C.c_int]),
     "mean_squared_error_derivative": (None, [_P, _P, _P, C.c_int, C.c_int]),
     "mean_squared_error_cuda": (C.c_float, [_P, _P, C.c_int, C.c_int]),
