@@ -11,6 +11,7 @@
 // so that, given identical gradients, parameters, m and v match the oracle bit for bit — over the whole
 // fp32 range of g (subnormals, ±inf, NaN up to its payload): tests/test_gpu_adam.py.
 #include "dev.h"
+#include "ppo_math.h"
 
 namespace {
 
@@ -19,10 +20,7 @@ constexpr int TPB = 256;
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
                                           float bc2, float scale) {
     g = g * scale;
-    m = b1 * m + (1 - b1) * g;
-    v = b2 * v + (1 - b2) * (g * g);
-    const float denom = (float)((double)sqrtf(v / bc2) + 1e-8);
-    p -= step * m / denom;
+    ppo::adam_elem(p, g, m, v, step, b1, b2, bc2);
 }
 
 // the step's gradient scale: grad_scale, times the device clip coefficient when clipping is on

@@ -12,32 +12,14 @@
 //                                           [0, limit); no storage, no host work.  Restated
 //                                           bit-exactly in oracle/ref_cpu.c (ref_feistel_index).
 #include "dev.h"
+#include "feistel.h"
 
 namespace {
 
 constexpr int TPB = 256;
 
-struct Feistel { uint32_t k[4]; uint32_t half, mask, n; };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
-__device__ __forceinline__ uint32_t feistel_index(uint32_t i, const Feistel& f) {
-    uint32_t x = i;
-    do {
-        uint32_t L = x >> f.half, R = x & f.mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t nl = R;
-            R = L ^ (mix32(R ^ f.k[r]) & f.mask);
-            L = nl;
-        }
-        x = (L << f.half) | R;
-    } while (x >= f.n);
-    return x;
-}
+using ppo::Feistel;
+using ppo::feistel_index;
 
 __global__ void gather_kernel(const int* __restrict__ perm, Feistel f, int offset, int limit, int batch, int S,
                               int A, const float* __restrict__ state, const float* __restrict__ action,
@@ -120,13 +102,6 @@ __global__ void gather_small_tab_kernel(const PhipStepArgs* __restrict__ tab, co
     }
 }
 
-uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 }  // namespace
 
 extern "C" {
@@ -137,13 +112,9 @@ void phip_gather_rows(const int* perm, uint64_t key, int offset, int limit, int 
                       float* adv_targets, int* rows) {
     if (batch <= 0) return;
     PPO_REQUIRE(limit > 0, "phip_gather: empty buffer");
-    Feistel f{};
-    int bits = 2;
-    while ((1ULL << bits) < (unsigned long long)limit) bits++;
-    f.half = (uint32_t)((bits + 1) / 2);
-    f.mask = (1u << f.half) - 1u;
-    f.n = (uint32_t)limit;
-    for (int r = 0; r < 4; ++r) f.k[r] = (uint32_t)splitmix64(key + (uint64_t)r);
+    uint32_t k[4];
+    for (int r = 0; r < 4; ++r) k[r] = (uint32_t)splitmix64(key + (uint64_t)r);
+    const ppo::Feistel f = ppo::feistel_make(limit, k);
     ppo::ProfScope ps(PPO_K_GATHER, 8.0 * batch * ((states ? S : 0) + (actions ? A : 0) + 3));
     if (!states && (!actions || A <= 32)) {
         hipLaunchKernelGGL(gather_small_kernel, dim3(ppo_divup(batch, TPB)), dim3(TPB), 0, ppo::stream(), perm, f,
@@ -161,11 +132,8 @@ void phip_gather_rows(const int* perm, uint64_t key, int offset, int limit, int 
 }
 
 void phip_step_feistel(PhipStepArgs* s, unsigned long long key, int limit) {
-    int bits = 2;
-    while ((1ULL << bits) < (unsigned long long)limit) bits++;
-    s->fhalf = (unsigned)((bits + 1) / 2);
-    s->fmask = (1u << s->fhalf) - 1u;
-    s->fn = (unsigned)limit;
+    const ppo::Feistel f = ppo::feistel_domain(limit);
+    s->fhalf = f.half; s->fmask = f.mask; s->fn = f.n;
     for (int r = 0; r < 4; ++r) s->fk[r] = (unsigned)splitmix64(key + (uint64_t)r);
 }
 

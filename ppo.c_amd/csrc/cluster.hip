@@ -388,7 +388,7 @@ __global__ __launch_bounds__(TPB) void cluster_phase_kernel(ClArgs a) {
                 if (!a.policy) {
                     atomicAdd(a.stats + 0, part * (1.0f / (float)BB));
                 } else {
-                    float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+                    float ent = ppo::entropy_start(A);
                     for (int j = 0; j < A; ++j) ent += lds[L::ls + j];
                     atomicAdd(a.stats + 1, -part / BB - a.ent_coeff * ent);
                 }
@@ -840,15 +840,8 @@ int phip_cluster_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     a.total_steps = ph->n_epochs * ph->num_batches;
     if (ph->max_steps > 0 && ph->max_steps < a.total_steps) a.total_steps = (int)ph->max_steps;
     a.perms = ph->perms;
-    for (int e = 0; e < ph->n_epochs && !ph->perms; ++e) {
-        Feistel& f = a.fk[e];
-        int bits = 2;
-        while ((1ULL << bits) < (unsigned long long)ph->limit) bits++;
-        f.half = (uint32_t)((bits + 1) / 2);
-        f.mask = (1u << f.half) - 1u;
-        f.n = (uint32_t)ph->limit;
-        for (int r = 0; r < 4; ++r) f.k[r] = ph->feistel_k[4 * e + r];
-    }
+    for (int e = 0; e < ph->n_epochs && !ph->perms; ++e)
+        a.fk[e] = ppo::feistel_make(ph->limit, ph->feistel_k + 4 * e);
     a.steps = ph->steps; a.steps_ls = ph->steps_ls;
     a.b1 = ph->b1; a.b2 = ph->b2; a.eps = ph->eps; a.ent_coeff = ph->ent_coeff;
     a.stats = ph->stats;

@@ -1,9 +1,12 @@
 // cluster_common.h — device primitives shared by the multi-workgroup phase kernels (cluster.hip,
-// cluster_deep.hip): the device Feistel order, the sc1 hand-off primitives and the split barrier
-// (MI355X_MICROARCH.md § inter-workgroup visibility, the first row of the sc1 table), fixed-order
-// column sums, the 16×16×4 fp32 MFMA tile from LDS, and the per-row PPO head / Adam arithmetic.
+// cluster_deep.hip): the sc1 hand-off primitives and the split barrier (MI355X_MICROARCH.md
+// § inter-workgroup visibility, the first row of the sc1 table), fixed-order column sums and the
+// 16×16×4 fp32 MFMA tile from LDS.  The Feistel order (feistel.h) and the per-row PPO head / Adam
+// arithmetic (ppo_math.h) are shared with every other path.
 #pragma once
 #include "dev.h"
+#include "feistel.h"
+#include "ppo_math.h"
 
 #include <cmath>
 #include <cstdint>
@@ -28,27 +31,11 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TPB = 512, NWAVE = TPB / 64;   // eight waves per workgroup
 constexpr int BB = 64;                       // minibatch rows (the reference's B, main.c:34)
 
-struct Feistel { uint32_t k[4]; uint32_t half, mask, n; };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-// identical to buffer.hip's feistel_index (restated in oracle/ref_cpu.c: ref_feistel_index)
-__device__ __forceinline__ uint32_t feistel_index(uint32_t i, const Feistel& f) {
-    uint32_t x = i;
-    do {
-        uint32_t L = x >> f.half, R = x & f.mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t nl = R;
-            R = L ^ (mix32(R ^ f.k[r]) & f.mask);
-            L = nl;
-        }
-        x = (L << f.half) | R;
-    } while (x >= f.n);
-    return x;
-}
+using ppo::Feistel;
+using ppo::feistel_index;
+using ppo::log_prob_row;
+using ppo::surrogate;
+using ppo::adam_elem;
 
 // ---- hand-off primitives (sc1: write-through stores, L1-bypassing loads) ----
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const float* p, long floats) {
@@ -156,35 +143,6 @@ __device__ __forceinline__ f32x4 mm_tile(const float* A, int as_i, int as_k, con
         }
     }
     return acc;
-}
-
-__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
-    const float cst = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = cst;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
-}
-
-__device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, float eps, int m, float* grad) {
-    const float ratio = (float)exp((double)(lp - old_lp));
-    const int adv_pos = adv > 0;
-    const int ratio_pos = ratio > 1 + eps;
-    const int ratio_neg = ratio < 1 - eps;
-    *grad = -(adv_pos * !ratio_pos + !adv_pos * !ratio_neg) * adv * ratio / m;
-    return adv * (adv_pos * (ratio_pos * (1 + eps) + !ratio_pos * ratio) +
-                  !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
-}
-
-// adam.cu:53-74 / tiny.hip adam_elem
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
-                                          float bc2) {
-    m = b1 * m + (1 - b1) * g;
-    v = b2 * v + (1 - b2) * (g * g);
-    const float denom = (float)((double)sqrtf(v / bc2) + 1e-8);
-    p -= step * m / denom;
 }
 
 // stamp buffer layout (PPO_CLUSTER_STAMPS): [64 steps][≤ 32] s_memrealtime | [64] placement words |

@@ -176,19 +176,13 @@ double comm_timeout_s() {
     return v > 0 ? v : 600.0;
 }
 
-// replica check: 64-bit hash of parameter bits, Σ mix(index, bits) mod 2^64 (order-independent, so the
-// grid's atomics give the same value on every rank for the same bits)
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// replica check: 64-bit hash of parameter bits, Σ splitmix64(index ‖ bits) mod 2^64 (order-independent, so
+// the grid's atomics give the same value on every rank for the same bits)
 __global__ void param_hash_kernel(const unsigned* __restrict__ p, long n, unsigned long long base,
                                   unsigned long long* __restrict__ out) {
     unsigned long long acc = 0;
     for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256)
-        acc += mix64(((base + (unsigned long long)i) << 32) ^ p[i]);
+        acc += splitmix64(((base + (unsigned long long)i) << 32) ^ p[i]);
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     __shared__ unsigned long long part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;

@@ -53,6 +53,14 @@ inline long long gemm_key(int op, int engine, long m, long n, long l) {
 // h propagates; tests/tanh_ref.py states the same order in numpy.
 __device__ __forceinline__ float tanh_bwd(float g, float h) { return __fsub_rn(g, __fmul_rn(__fmul_rn(g, h), h)); }
 
+// Wave sum by the __shfl_xor butterfly (xor 32, 16, … 1): every lane gets the sum.  Not interchangeable with
+// wave_sum64 below, which adds in another order and gives other bits.
+__device__ __forceinline__ float wave_sum_xor(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // Cross-lane sums on DPP moves (no LDS round trips; a __shfl_xor tree compiles to ds_bpermute,
 // ≈ 100+ cycles of latency per step): sum over each 16-lane DPP row — the xor-1 / xor-2 / quad-swap /
 // half-swap tree — and over the wave (row sums in row order, read as scalars)

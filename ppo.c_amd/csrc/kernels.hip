@@ -11,6 +11,7 @@
 // Arithmetic mirrors the reference's C promotions (its double exp/pow temporaries) so results
 // match the oracle to a few ulps; reductions use wave shuffles + one f32 atomic per workgroup.
 #include "dev.h"
+#include "ppo_math.h"
 #include "vclip.h"
 
 #include <algorithm>
@@ -21,15 +22,9 @@ namespace {
 
 constexpr int TPB = 256;
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // block-wide sum: every thread gets the result
 __device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
+    v = ppo::wave_sum_xor(v);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
     __syncthreads();
     if (lane == 0) red[w] = v;
@@ -113,7 +108,7 @@ __global__ void mse_kernel(const float* __restrict__ y, const float* __restrict_
         if (d_loss_accum) atomicAdd(d_loss_accum, s * inv);
     }
     if (vc.v_old) {     // per wave (≤ 2^17 rows of a count < 2^31 on ≤ 4096 workgroups: the fp32 sums are exact)
-        const float fc = wave_sum((float)nclip), fr = wave_sum((float)nrow);
+        const float fc = ppo::wave_sum_xor((float)nclip), fr = ppo::wave_sum_xor((float)nrow);
         if ((threadIdx.x & 63) == 0) ppo::value_clip_count(vc, (unsigned long long)fc, (unsigned long long)fr);
     }
 }
@@ -150,26 +145,15 @@ __global__ void value_head_kernel(const float* __restrict__ ypart, int slots, co
         if (d_loss_accum) atomicAdd(d_loss_accum, s * (1.0f / (float)m));
     }
     if (vc.v_old) {     // per wave (< 2^24 rows: the fp32 sums are exact)
-        const float fc = wave_sum((float)nclip), fr = wave_sum((float)nrow);
+        const float fc = ppo::wave_sum_xor((float)nclip), fr = ppo::wave_sum_xor((float)nrow);
         if ((threadIdx.x & 63) == 0) ppo::value_clip_count(vc, (unsigned long long)fc, (unsigned long long)fr);
     }
-}
-
-// policy.cu:67-74 with the reference's double temporaries
-__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
 }
 
 __global__ void log_prob_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
                                 const float* __restrict__ action, float* __restrict__ out, int m, int A) {
     const int i = blockIdx.x * TPB + threadIdx.x;
-    if (i < m) out[i] = log_prob_row(mu + (long)i * A, log_std, action + (long)i * A, A);
+    if (i < m) out[i] = ppo::log_prob_row(mu + (long)i * A, log_std, action + (long)i * A, A);
 }
 
 // policy.cu:101-111 (D2: grad_in per sample).  grad_log_std pre-zeroed; one atomic per (block, j).
@@ -190,7 +174,7 @@ __global__ void log_prob_bwd_kernel(const float* __restrict__ mu, const float* _
             grad_mu[k] = d * e * g;
             c = (-1 + d * d * e) * g;
         }
-        c = wave_sum(c);
+        c = ppo::wave_sum_xor(c);
         if ((threadIdx.x & 63) == 0) atomicAdd(&sacc[j], c);
     }
     __syncthreads();
@@ -199,21 +183,10 @@ __global__ void log_prob_bwd_kernel(const float* __restrict__ mu, const float* _
 
 __global__ void entropy_kernel(const float* __restrict__ log_std, int A, float* out) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        float e = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+        float e = ppo::entropy_start(A);
         for (int j = 0; j < A; ++j) e += log_std[j];
         out[0] = e;
     }
-}
-
-// ppo.cu:82-107, per sample
-__device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, float eps, int m, float* grad) {
-    const float ratio = (float)exp((double)(lp - old_lp));
-    const int adv_pos = adv > 0;
-    const int ratio_pos = ratio > 1 + eps;
-    const int ratio_neg = ratio < 1 - eps;
-    *grad = -(adv_pos * !ratio_pos + !adv_pos * !ratio_neg) * adv * ratio / m;
-    return adv * (adv_pos * (ratio_pos * (1 + eps) + !ratio_pos * ratio) +
-                  !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
 }
 
 __global__ void policy_loss_kernel(const float* __restrict__ adv, const float* __restrict__ lp,
@@ -224,7 +197,7 @@ __global__ void policy_loss_kernel(const float* __restrict__ adv, const float* _
     float s = 0.f;
     for (int i = blockIdx.x * TPB + threadIdx.x; i < m; i += gridDim.x * TPB) {
         float g;
-        s += surrogate(adv[i], lp[i], old_lp[i], eps, m, &g);
+        s += ppo::surrogate(adv[i], lp[i], old_lp[i], eps, m, &g);
         grad_lp[i] = g;
     }
     s = block_sum(s, red);
@@ -256,8 +229,8 @@ __global__ void policy_head_kernel(const float* __restrict__ mu, const float* __
     const float* mr = mu + (long)i * A;
     const float* ar = action + (long)i * A;
     if (i < m) {
-        const float lp = log_prob_row(mr, log_std, ar, A);
-        s = surrogate(adv[i], lp, old_lp[i], eps, m, &g);
+        const float lp = ppo::log_prob_row(mr, log_std, ar, A);
+        s = ppo::surrogate(adv[i], lp, old_lp[i], eps, m, &g);
     }
     for (int j = 0; j < A; ++j) {          // column sums: wave shuffle, then one LDS add per wave
         float c = 0.f;
@@ -266,7 +239,7 @@ __global__ void policy_head_kernel(const float* __restrict__ mu, const float* __
             grad_mu[(long)i * A + j] = d * e2[j] * g;
             c = (-1 + d * d * e2[j]) * g;
         }
-        c = wave_sum(c);
+        c = ppo::wave_sum_xor(c);
         if ((threadIdx.x & 63) == 0) atomicAdd(&gls[j], c);
     }
     s = block_sum(s, red);
@@ -279,7 +252,7 @@ __global__ void policy_head_kernel(const float* __restrict__ mu, const float* __
     if (threadIdx.x == 0 && d_loss_accum) {
         float contrib = -s / m;
         if (blockIdx.x == 0) {
-            float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+            float ent = ppo::entropy_start(A);
             for (int j = 0; j < A; ++j) ent += log_std[j];
             contrib -= ent_coeff * ent;
         }
@@ -289,7 +262,7 @@ __global__ void policy_head_kernel(const float* __restrict__ mu, const float* __
 
 // The same head for A ≤ 32 over ROWS-row tiles: μ and action rows staged through LDS by coalesced
 // loads (the one-thread-per-row form reads them at a 4·A-byte lane stride), the per-row log-prob /
-// surrogate chain unchanged (log_prob_row, surrogate: identical values), grad_μ stored coalesced,
+// surrogate chain unchanged (ppo_math.h: identical values), grad_μ stored coalesced,
 // the log σ column sums from the staged tile (8 partial sums per column, then one f32 atomic per
 // column per workgroup).  Grid: ⌈m / ROWS⌉ (512 workgroups at C4's B = 32768, every CU busy).
 template <int ROWS>
@@ -321,8 +294,8 @@ __global__ __launch_bounds__(TPB) void policy_head_tiled_kernel(
     float s = 0.f;
     if (tid < nr) {
         float g;
-        const float lp = log_prob_row(mt + tid * A, lsd, at + tid * A, A);
-        s = surrogate(adv[r0 + tid], lp, old_lp[r0 + tid], eps, m, &g);
+        const float lp = ppo::log_prob_row(mt + tid * A, lsd, at + tid * A, A);
+        s = ppo::surrogate(adv[r0 + tid], lp, old_lp[r0 + tid], eps, m, &g);
         gr[tid] = g;
     }
     __syncthreads();
@@ -350,7 +323,7 @@ __global__ __launch_bounds__(TPB) void policy_head_tiled_kernel(
     if (tid == 0 && d_loss_accum) {
         float contrib = -s / m;
         if (blockIdx.x == 0) {
-            float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+            float ent = ppo::entropy_start(A);
             for (int j = 0; j < A; ++j) ent += log_std[j];
             contrib -= ent_coeff * ent;
         }

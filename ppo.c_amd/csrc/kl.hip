@@ -2,7 +2,7 @@
 // on the device (no counterpart in the reference).
 //
 // One launch per policy minibatch step, after the step's forward has left μ in HBM and before its Adam:
-//   lp_i  = Gaussian log-prob of action_i under (μ_i, log σ)           (kernels.hip log_prob_row's expression)
+//   lp_i  = Gaussian log-prob of action_i under (μ_i, log σ)           (ppo_math.h log_prob_row, as the loss)
 //   x_i   = (double)lp_i − (double)old_lp_i
 //   kl    = Σ (expm1(x_i) − x_i) / rows          (Schulman's k3 estimator; double: (r − 1) − log r cancels in fp32)
 //   frac  = Σ 1[|(float)exp(x_i) − 1| > ε] / rows
@@ -21,6 +21,7 @@
 // writes the local sums; the caller all-reduces those four floats and kl_decide_kernel decides from the global
 // sums, so every rank takes the same decision from the same bits.
 #include "dev.h"
+#include "ppo_math.h"
 
 namespace {
 
@@ -36,18 +37,6 @@ __device__ __forceinline__ double block_sum(double v, double* s) {
     const double r = s[0];
     __syncthreads();
     return r;
-}
-
-// policy.cu:67-74 with the reference's double temporaries — kernels.hip log_prob_row, so the ratio is the one
-// the loss saw
-__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
 }
 
 // one thread, from rec->sums (local, or all-reduced over the ranks): the step's statistics and the decision
@@ -75,7 +64,7 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
     __shared__ double s[TPB + 1];             // s[TPB]: "this workgroup drew the last ticket"
     double kl = 0.0, cnt = 0.0;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < m; i += (long)gridDim.x * TPB) {
-        const float lp = log_prob_row(mu + i * A, log_std, action + i * A, A);
+        const float lp = ppo::log_prob_row(mu + i * A, log_std, action + i * A, A);
         const double x = (double)lp - (double)old_lp[i];
         kl += expm1(x) - x;
         cnt += fabsf((float)exp(x) - 1.0f) > eps ? 1.0 : 0.0;

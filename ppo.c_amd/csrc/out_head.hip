@@ -25,6 +25,7 @@
 // profiles/r02_out_head_ab.txt).  It takes out_bwd_wide_kernel (head + backward, thread per column)
 // after the forward GEMM, or policy_out_fused_kernel (forward + head + backward) up to 8192 rows.
 #include "dev.h"
+#include "ppo_math.h"
 #include "vclip.h"
 
 #include <algorithm>
@@ -37,30 +38,18 @@ constexpr int NW = NTH / 64;
 
 __device__ __forceinline__ float wsum(float v) { return ppo::wave_sum64(v); }   // DPP rows + scalar reads
 
-// policy.cu:67-74 with the reference's double temporaries (kernels.hip log_prob_row); es[j] =
-// expf(log_std[j]), computed once per wave (the same value the per-element expf gave)
+// ppo::log_prob_row_es on register arrays, unrolled over the compile-time A (passing the arrays to the
+// pointer form compiles out_head_kernel to other code); es[j] = expf(log_std[j]), computed once per wave
 template <int A>
 __device__ __forceinline__ float log_prob_row(const float (&mu)[A], const float (&log_std)[A], const float (&es)[A],
                                               const float (&a)[A]) {
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
+    float lp = ppo::log_prob_start(A);
 #pragma unroll
     for (int j = 0; j < A; ++j) {
         const float z = (a[j] - mu[j]) / es[j];
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
+        lp = ppo::log_prob_sub(lp, ppo::log_prob_term(log_std[j], z));
     }
     return lp;
-}
-
-// ppo.cu:82-107 per sample (kernels.hip surrogate)
-__device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, float eps, int m, float* grad) {
-    const float ratio = (float)exp((double)(lp - old_lp));
-    const int adv_pos = adv > 0;
-    const int ratio_pos = ratio > 1 + eps;
-    const int ratio_neg = ratio < 1 - eps;
-    *grad = -(adv_pos * !ratio_pos + !adv_pos * !ratio_neg) * adv * ratio / m;
-    return adv * (adv_pos * (ratio_pos * (1 + eps) + !ratio_pos * ratio) +
-                  !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
 }
 
 struct OutArgs {
@@ -269,7 +258,7 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
             for (int a = 0; a < A; ++a) act[a] = p.action[(long)row * A + a];
             const float lp = log_prob_row<A>(yv, ls, es, act);
             float glp;
-            const float sv = surrogate(p.adv[row], lp, p.old_lp[row], p.eps, m, &glp);
+            const float sv = ppo::surrogate(p.adv[row], lp, p.old_lp[row], p.eps, m, &glp);
             if (owner) loss += sv;
 #pragma unroll
             for (int a = 0; a < A; ++a) {
@@ -348,7 +337,7 @@ __global__ __launch_bounds__(NTH) void out_head_kernel(OutArgs p) {
         } else {
             float contrib = -s / m;
             if (blockIdx.x == 0) {
-                float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+                float ent = ppo::entropy_start(A);
                 for (int j = 0; j < A; ++j) ent += ls[j];
                 contrib -= p.ent_coeff * ent;
             }
@@ -423,19 +412,6 @@ struct WideArgs {
     float eps, ent_coeff; float* grad_log_std; float* loss_accum;
 };
 
-// kernels.hip log_prob_row (policy.cu:67-74, double temporaries), on LDS rows; es[j] = expf(log_std[j])
-// computed once per workgroup (the same value the per-element expf gave)
-__device__ __forceinline__ float log_prob_row_p(const float* mu, const float* log_std, const float* es, const float* a,
-                                                int A) {
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / es[j];
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
-}
-
 template <int A, int NPT, int U, bool HEAD>
 __global__ __launch_bounds__(256) void out_bwd_wide_kernel(WideArgs p) {
     constexpr int N = 256 * NPT;
@@ -474,9 +450,9 @@ __global__ __launch_bounds__(256) void out_bwd_wide_kernel(WideArgs p) {
         float sv = 0.f;
         for (int row = t; row < nr; row += 256) {
             float glp;
-            const float lp = log_prob_row_p(mus + row * A, lss, ess, acts + row * A, A);
+            const float lp = ppo::log_prob_row_es(mus + row * A, lss, ess, acts + row * A, A);
             const float ad = row == t ? adv0 : p.adv[r0 + row], ol = row == t ? olp0 : p.old_lp[r0 + row];
-            sv += surrogate(ad, lp, ol, p.eps, m, &glp);
+            sv += ppo::surrogate(ad, lp, ol, p.eps, m, &glp);
             grs[row] = glp;
         }
         sv = ppo::wave_sum64(sv);
@@ -506,7 +482,7 @@ __global__ __launch_bounds__(256) void out_bwd_wide_kernel(WideArgs p) {
             const float sl = ((redl[0] + redl[1]) + redl[2]) + redl[3];
             float contrib = -sl / m;
             if (blockIdx.x == 0) {
-                float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+                float ent = ppo::entropy_start(A);
                 for (int j = 0; j < A; ++j) ent += lss[j];
                 contrib -= p.ent_coeff * ent;
             }
@@ -703,15 +679,15 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
         for (int e = t; e < FR * A; e += 256) {
             const int r = e / A, j = e % A;
             const float z = (acts[r * AP + j] - mus[r * AP + j]) / ess[j];
-            dterm[e] = (double)lss[j] + 0.5 * (double)(z * z);     // policy.cu:67-74 (log_prob_row_p)
+            dterm[e] = ppo::log_prob_term(lss[j], z);
         }
         __syncthreads();
         if (t < nr && !(PPO_FUSED_ABL & 2)) {                     // the head, one row per thread (wave 0)
-            float lp = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
+            float lp = ppo::log_prob_start(A);
 #pragma unroll
-            for (int j = 0; j < A; ++j) lp = (float)((double)lp - dterm[t * A + j]);
+            for (int j = 0; j < A; ++j) lp = ppo::log_prob_sub(lp, dterm[t * A + j]);
             float glp;
-            sv += surrogate(advs[t], lp, advs[FR + t], p.eps, p.m, &glp);
+            sv += ppo::surrogate(advs[t], lp, advs[FR + t], p.eps, p.m, &glp);
             grs[t] = glp;
         }
         __syncthreads();
@@ -771,7 +747,7 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
         if (lane == 0 && p.loss_accum) {
             float contrib = -sl / p.m;
             if (blockIdx.x == 0) {
-                float ent = (float)(A * 0.5 * (1 + log(2 * M_PI)));
+                float ent = ppo::entropy_start(A);
                 for (int j = 0; j < A; ++j) ent += lss[j];
                 contrib -= p.ent_coeff * ent;
             }

@@ -12,6 +12,19 @@
 #include <stddef.h>
 #include <stdint.h>
 
+/* splitmix64: libppo's key derivation (Feistel round keys, RNG stream keys) on the host, and the replica
+ * hash's mixer on the device (comm.hip) */
+#define PHIP_GOLDEN64 0x9E3779B97F4A7C15ULL
+#ifdef __HIPCC__
+__host__ __device__
+#endif
+static inline uint64_t splitmix64(uint64_t z) {
+    z += PHIP_GOLDEN64;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif

@@ -1,0 +1,66 @@
+// ppo_math.h — the per-row arithmetic of the PPO update, written once for every kernel that evaluates it:
+// the multi-launch heads (kernels.hip, out_head.hip), the single-workgroup and cluster phases (tiny.hip,
+// cluster.hip, cluster_deep.hip), sampling and rollouts (sample.hip, rollout.hip), the KL monitor (kl.hip)
+// and Adam (adam.hip).  Every path gives the same bits because every path calls these.
+//
+// All arithmetic is in the order written here, with the reference's C promotions (its double temporaries);
+// the kernels are built with -ffp-contract=off.  tests/policy_head_ref.py and oracle/ref_cpu.c restate it
+// independently.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+
+namespace ppo {
+
+// ---- Gaussian log-prob of one row (policy.cu:67-74): lp = start(A), then lp = sub(lp, term(log σ_j, z_j))
+// for j ascending, z_j = (a_j − μ_j) / exp(log σ_j).  A kernel that fuses or splits the loop calls the atoms.
+// sub takes the fp32 lp widened at the call (exact): (float)((double)lp − term), one rounding.
+__device__ __forceinline__ float log_prob_start(int A) { return (float)(-0.5 * A * (double)logf((float)(2 * M_PI))); }
+__device__ __forceinline__ double log_prob_term(float ls, float z) { return (double)ls + 0.5 * (double)(z * z); }
+__device__ __forceinline__ float log_prob_sub(double lp, double term) { return (float)(lp - term); }
+
+__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
+    float lp = log_prob_start(A);
+    for (int j = 0; j < A; ++j) {
+        const float z = (a[j] - mu[j]) / expf(log_std[j]);
+        lp = log_prob_sub(lp, log_prob_term(log_std[j], z));
+    }
+    return lp;
+}
+// es[j] = expf(log_std[j]) computed once by the caller (the same value the per-element expf gives)
+__device__ __forceinline__ float log_prob_row_es(const float* mu, const float* log_std, const float* es,
+                                                 const float* a, int A) {
+    float lp = log_prob_start(A);
+    for (int j = 0; j < A; ++j) {
+        const float z = (a[j] - mu[j]) / es[j];
+        lp = log_prob_sub(lp, log_prob_term(log_std[j], z));
+    }
+    return lp;
+}
+
+// ---- clipped surrogate of one row of a minibatch of m rows (ppo.cu:82-107); *grad = ∂loss/∂lp
+__device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, float eps, int m, float* grad) {
+    const float ratio = (float)exp((double)(lp - old_lp));
+    const int adv_pos = adv > 0;
+    const int ratio_pos = ratio > 1 + eps;
+    const int ratio_neg = ratio < 1 - eps;
+    *grad = -(adv_pos * !ratio_pos + !adv_pos * !ratio_neg) * adv * ratio / m;
+    return adv * (adv_pos * (ratio_pos * (1 + eps) + !ratio_pos * ratio) +
+                  !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
+}
+
+// ---- Gaussian entropy (policy.cu:171-193): this constant, then += log σ_j for j ascending, at the call site
+// (the sum inside a helper compiled to other code than the kernels' own loops)
+__device__ __forceinline__ float entropy_start(int A) { return (float)(A * 0.5 * (1 + log(2 * M_PI))); }
+
+// ---- Adam on one element (adam.cu:53-74): step = lr/bc1, ε added in double
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
+                                          float bc2) {
+    m = b1 * m + (1 - b1) * g;
+    v = b2 * v + (1 - b2) * (g * g);
+    const float denom = (float)((double)sqrtf(v / bc2) + 1e-8);
+    p -= step * m / denom;
+}
+
+}  // namespace ppo

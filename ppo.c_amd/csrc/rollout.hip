@@ -15,6 +15,7 @@
 //            0.05·ε, −1, 1); r = −0.01·mean(a²) + 0.1·ε; terminated ~ Bernoulli(1/500), reset
 //            o ~ U(−1, 1).
 #include "dev.h"
+#include "ppo_math.h"
 #include "rng.h"
 
 #include <cmath>
@@ -29,7 +30,7 @@ constexpr int TPB = 256;
 // ppo_rollout_device call): the position in the policy-noise, env and reset streams of rng.h.  `t`
 // is the step inside this call: row addressing and the segment-end truncation only.
 
-// a = μ + ε·σ written to buffer row rows[e]; log π(a) as policy.cu:67-74 (same as sample.hip)
+// a = μ + ε·σ written to buffer row rows[e]; log π(a) from the atoms of ppo_math.h log_prob_row
 __global__ void sample_rows_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
                                    const int* __restrict__ rows, float* __restrict__ action,
                                    float* __restrict__ logprob, int E, int A, uint64_t seed, uint64_t step) {
@@ -37,13 +38,12 @@ __global__ void sample_rows_kernel(const float* __restrict__ mu, const float* __
     if (e >= E) return;
     const float* mr = mu + (long)e * A;
     float* ar = action + (long)rows[e] * A;
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
+    float lp = ppo::log_prob_start(A);
     for (int j = 0; j < A; ++j) {
         const float a = mr[j] + normal_at((uint64_t)e * A + j, kNoise + step, seed) * expf(log_std[j]);
         ar[j] = a;
         const float z = (a - mr[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
+        lp = ppo::log_prob_sub(lp, ppo::log_prob_term(log_std[j], z));
     }
     logprob[rows[e]] = lp;
 }

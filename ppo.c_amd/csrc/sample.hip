@@ -7,6 +7,7 @@
 //   a = μ + ε·exp(log_std),   log π(a) as in policy.cu:67-74.
 // The synthetic-rollout fills implement SURVEY §8d's generator on the device.
 #include "dev.h"
+#include "ppo_math.h"
 #include "rng.h"
 
 #include <cmath>
@@ -17,16 +18,6 @@ using namespace ppo_rng;
 
 constexpr int TPB = 256;
 
-__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
-    const float c = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = c;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
-}
-
 __global__ void sample_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
                               float* __restrict__ action, float* __restrict__ logprob, int m, int A, uint64_t seed,
                               uint64_t offset) {
@@ -35,7 +26,7 @@ __global__ void sample_kernel(const float* __restrict__ mu, const float* __restr
     const float* mr = mu + (long)i * A;
     float* ar = action + (long)i * A;
     for (int j = 0; j < A; ++j) ar[j] = mr[j] + normal_at((uint64_t)i * A + j, offset, seed) * expf(log_std[j]);
-    if (logprob) logprob[i] = log_prob_row(mr, log_std, ar, A);
+    if (logprob) logprob[i] = ppo::log_prob_row(mr, log_std, ar, A);
 }
 
 __global__ void sample_noise_kernel(const float* __restrict__ mu, const float* __restrict__ log_std,
@@ -46,7 +37,7 @@ __global__ void sample_noise_kernel(const float* __restrict__ mu, const float* _
     const float* mr = mu + (long)i * A;
     float* ar = action + (long)i * A;
     for (int j = 0; j < A; ++j) ar[j] = mr[j] + noise[(long)i * A + j] * expf(log_std[j]);   // policy.cu:84
-    if (logprob) logprob[i] = log_prob_row(mr, log_std, ar, A);
+    if (logprob) logprob[i] = ppo::log_prob_row(mr, log_std, ar, A);
 }
 
 __global__ void fill_uniform_kernel(float* __restrict__ p, long n, uint64_t seed, float lo, float hi) {

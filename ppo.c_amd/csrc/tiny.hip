@@ -24,6 +24,8 @@
 // One CU's fp32 MFMA rate (256 FLOP/clk) bounds a 64-wide step at ≈4 µs; measured ≈26 µs per step
 // (PPO_TINY_STAMPS=1 prints the per-phase split), against ≈65 µs for the multi-launch loop.
 #include "dev.h"
+#include "feistel.h"
+#include "ppo_math.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -39,28 +41,11 @@ constexpr int TPB = PPO_TINY_TPB;
 constexpr int NWAVES = TPB / 64;
 constexpr int MAXL = 8;            // linear layers
 
-struct Feistel { uint32_t k[4]; uint32_t half, mask, n; };
-
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-
-// identical to buffer.hip's feistel_index (restated in oracle/ref_cpu.c: ref_feistel_index)
-__device__ __forceinline__ uint32_t feistel_index(uint32_t i, const Feistel& f) {
-    uint32_t x = i;
-    do {
-        uint32_t L = x >> f.half, R = x & f.mask;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const uint32_t nl = R;
-            R = L ^ (mix32(R ^ f.k[r]) & f.mask);
-            L = nl;
-        }
-        x = (L << f.half) | R;
-    } while (x >= f.n);
-    return x;
-}
+using ppo::Feistel;
+using ppo::feistel_index;
+using ppo::log_prob_row;
+using ppo::surrogate;
+using ppo::adam_elem;
 
 struct TinyArgs {
     int L;                          // linear layers
@@ -91,12 +76,6 @@ struct TinyArgs {
     unsigned long long* stamps;     // diagnostics (PPO_TINY_STAMPS): s_memrealtime at phase boundaries
     int res_off;                    // RESIDENT: LDS offset of [params | grads | m | v | Wᵀ]
 };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // C[M×N] = A(M×K)·B(K×N) on 16×16 tiles, one tile per wave per round; A(i, k) = A[i·a_si + k·a_sk],
 // B(k, j) = B[k·b_sk + j·b_sj] (LDS or global).  Operand lane maps: A lane l holds
@@ -164,34 +143,6 @@ __device__ __forceinline__ void tile_gemm(int M, int N, int K, const float* __re
             }
         }
     }
-}
-
-__device__ __forceinline__ float log_prob_row(const float* mu, const float* log_std, const float* a, int A) {
-    const float cst = (float)(-0.5 * A * (double)logf((float)(2 * M_PI)));
-    float lp = cst;
-    for (int j = 0; j < A; ++j) {
-        const float z = (a[j] - mu[j]) / expf(log_std[j]);
-        lp = (float)((double)lp - ((double)log_std[j] + 0.5 * (double)(z * z)));
-    }
-    return lp;
-}
-
-__device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, float eps, int m, float* grad) {
-    const float ratio = (float)exp((double)(lp - old_lp));
-    const int adv_pos = adv > 0;
-    const int ratio_pos = ratio > 1 + eps;
-    const int ratio_neg = ratio < 1 - eps;
-    *grad = -(adv_pos * !ratio_pos + !adv_pos * !ratio_neg) * adv * ratio / m;
-    return adv * (adv_pos * (ratio_pos * (1 + eps) + !ratio_pos * ratio) +
-                  !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
-}
-
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
-                                          float bc2) {
-    m = b1 * m + (1 - b1) * g;
-    v = b2 * v + (1 - b2) * (g * g);
-    const float denom = (float)((double)sqrtf(v / bc2) + 1e-8);
-    p -= step * m / denom;
 }
 
 #define TINY_STAMP(slot)                                                                         \
@@ -314,7 +265,7 @@ __global__ __launch_bounds__(TPB) void tiny_update_kernel(TinyArgs a) {
                     }
                 }
             }
-            part = wave_sum(part);
+            part = ppo::wave_sum_xor(part);
             if (lane == 0) red[w] = part;
             __syncthreads();
             if (tid == 0) {
@@ -323,7 +274,7 @@ __global__ __launch_bounds__(TPB) void tiny_update_kernel(TinyArgs a) {
                 if (!a.policy) {
                     atomicAdd(a.stats + 0, s * (1.0f / (float)B));
                 } else {
-                    float ent = (float)(a.A * 0.5 * (1 + log(2 * M_PI)));
+                    float ent = ppo::entropy_start(a.A);
                     for (int j = 0; j < a.A; ++j) ent += a.log_std[j];
                     atomicAdd(a.stats + 1, -s / B - a.ent_coeff * ent);
                 }
@@ -703,7 +654,7 @@ __global__ __launch_bounds__(TPB) void tiny_c2_kernel(TinyArgs a) {
                         if (!a.policy) {
                             atomicAdd(a.stats + 0, sl * (1.0f / (float)BB));
                         } else {
-                            const float ent = (float)(0.5 * (1 + log(2 * M_PI))) + s_ls;
+                            const float ent = ppo::entropy_start(1) + s_ls;
                             atomicAdd(a.stats + 1, -sl / BB - a.ent_coeff * ent);
                             s_lsg = gl + -a.ent_coeff;                      // ppo.cu:436-438
                             a.log_std_grad[0] = s_lsg;
@@ -865,15 +816,8 @@ int phip_tiny_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     a.total_steps = ph->n_epochs * ph->num_batches;
     if (ph->max_steps > 0 && ph->max_steps < a.total_steps) a.total_steps = (int)ph->max_steps;
     a.perms = ph->perms;
-    for (int e = 0; e < ph->n_epochs && !ph->perms; ++e) {
-        Feistel& f = a.fk[e];
-        int bits = 2;
-        while ((1ULL << bits) < (unsigned long long)ph->limit) bits++;
-        f.half = (uint32_t)((bits + 1) / 2);
-        f.mask = (1u << f.half) - 1u;
-        f.n = (uint32_t)ph->limit;
-        for (int r = 0; r < 4; ++r) f.k[r] = ph->feistel_k[4 * e + r];
-    }
+    for (int e = 0; e < ph->n_epochs && !ph->perms; ++e)
+        a.fk[e] = ppo::feistel_make(ph->limit, ph->feistel_k + 4 * e);
     a.steps = ph->steps; a.steps_ls = ph->steps_ls;
     a.b1 = ph->b1; a.b2 = ph->b2; a.eps = ph->eps; a.ent_coeff = ph->ent_coeff;
     a.stats = ph->stats;

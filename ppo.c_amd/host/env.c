@@ -57,7 +57,7 @@ Env* create_simple_env(int id, int seed) {
 /* ---------------- Pendulum-v1 ---------------- */
 static double g_th = 0, g_thdot = 0;
 static int g_pstep = 0;
-static uint64_t g_rng = 0x9E3779B97F4A7C15ULL;
+static uint64_t g_rng = PHIP_GOLDEN64;
 
 static double rng_uniform(double lo, double hi) {
     g_rng ^= g_rng << 13; g_rng ^= g_rng >> 7; g_rng ^= g_rng << 17;
@@ -104,7 +104,7 @@ static void free_pendulum(void) {}
 
 Env* create_gym_env(int id, int seed) {
     if (id != 0) die("create_gym_env: only Pendulum-v1 (id 0) is available natively");
-    g_rng = 0x9E3779B97F4A7C15ULL ^ ((uint64_t)(uint32_t)seed * 0xBF58476D1CE4E5B9ULL);
+    g_rng = PHIP_GOLDEN64 ^ ((uint64_t)(uint32_t)seed * 0xBF58476D1CE4E5B9ULL);
     if (!g_rng) g_rng = 1;
     Env* env = (Env*)xmalloc(sizeof(Env));
     env->state_size = 3;

@@ -134,13 +134,6 @@ static float* g_adv_stats = NULL; /* (mean, std) as used for normalisation */
 static long g_gae_own_rows = 0;   /* rows of the last GAE's own V(next_state) forward */
 static long g_gae_n = 0;          /* transitions of the last GAE */
 
-static uint64_t splitmix64(uint64_t z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 static void ensure_gae_ws(long n) {
     if (!g_welford) {
         g_welford = (double*)phip_malloc(4 * sizeof(double));

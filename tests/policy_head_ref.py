@@ -1,5 +1,5 @@
-"""The clipped-surrogate / Gaussian policy head (csrc/kernels.hip log_prob_row + surrogate and their restatements
-in csrc/out_head.hip): the definition in float64, an fp32 model that mirrors the device functions operation for
+"""The clipped-surrogate / Gaussian policy head (csrc/ppo_math.h log_prob_row + surrogate, which every form of the
+head in csrc calls): the definition in float64, an fp32 model that mirrors the device functions operation for
 operation (np.float32 arrays only, the double temporaries of the log-prob sum kept, so it is bit-comparable with
 the kernels, which are built with -ffp-contract=off), the rounding bound the GPU tests hold every form to, and the
 inputs those tests run on.  Pinned on the CPU in test_policy_head_cpu.py."""
@@ -56,7 +56,7 @@ def policy_head_f64(mu, log_std, action, adv, old_lp, eps, ent_coeff):
 
 
 def policy_head_f32(mu, log_std, action, adv, old_lp, eps, ent_coeff=0.0, es=None, e2=None):
-    """kernels.hip log_prob_row + surrogate + the grad_μ / ∂log σ expressions, operation for operation in fp32
+    """ppo_math.h log_prob_row + surrogate + the grad_μ / ∂log σ expressions, operation for operation in fp32
     (the log-prob sum through its double temporaries, 1 + eps formed in fp32, the int × float products as the
     device writes them).  es / e2: expf(log σ) / expf(−2 log σ) per column (default: libm's).  Returns lp, ratio,
     dlp, sur (the row's surrogate), grad_mu, gls_terms — all fp32, no sums (their order is the kernel's own)."""

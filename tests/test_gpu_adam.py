@@ -1,5 +1,5 @@
-"""Adam on its own, bit for bit against the oracle (csrc/adam.hip, host/adam.c, and the copies of the
-arithmetic in csrc/tiny.hip and csrc/cluster_common.h).
+"""Adam on its own, bit for bit against the oracle (csrc/adam.hip, host/adam.c, and the phase
+kernels csrc/tiny.hip and csrc/cluster.hip, all on csrc/ppo_math.h adam_elem).
 
 The reference everywhere is oracle.adam_update (oracle/ref_cpu.c, compiled without FMA contraction) on
 identical fp32 inputs.  Every comparison views the floats as uint32 and uses assert_array_equal: the
@@ -412,9 +412,9 @@ PATHS = {
     "graph": dict(sizes=[17, 256, 256, 6], N=1024, B=64,
                   env={"PPO_NO_CLUSTER": "1", "PPO_GRAPH": "1", "PPO_GRAPH_STEPS": "16"}, dtype=0),
     "eager64": dict(sizes=[17, 256, 256, 6], N=1024, B=64, env={"PPO_NO_CLUSTER": "1"}, dtype=0),
-    # the single-workgroup phases (tiny.hip's copy of the arithmetic)
+    # the single-workgroup phases (tiny.hip, calling ppo_math.h adam_elem)
     "tiny": dict(sizes=[3, 64, 64, 1], N=1024, B=64, env={}, dtype=0),
-    # the multi-workgroup phases at B = 64 (cluster_common.h's copy)
+    # the multi-workgroup phases at B = 64 (cluster.hip, the same adam_elem)
     "cluster": dict(sizes=[17, 256, 256, 6], N=1024, B=64, env={}, dtype=0),
 }
 
