@@ -501,7 +501,7 @@ double ppo_bench_gemm16(int op, int m, int n, int l, int iters, int cfg, int spl
  * queries; returns the previous engine.  Env PPO_F32_GEMM=exact|x3 sets the initial value. */
 int    ppo_gemm_f32_engine(int engine);
 /* bf16 mode's LDS-DMA GEMM kernel (forward / grad_x with bf16 operands, gemm16.hip): on = 1 / 0
- * sets, −1 queries; returns the previous setting (initially PPO_G16_DMA, else on) */
+ * sets, −1 queries; returns the previous setting (initially on) */
 int    ppo_gemm16_dma(int on);
 /* bf16 mode's LDS-DMA grad_W tile width: 128 (256 × 128 tiles, default) or 256 (256 × 256, for
  * n % 256 = 0); other values query; returns the previous width */
@@ -509,12 +509,6 @@ int    ppo_gemm16_tn_width(int bn);
 /* x3 engine tuning: force a tile configuration (−1 = automatic) and the grad_W split-K workgroup
  * target (0 = automatic, < 0 keeps); returns the number of configurations */
 int    ppo_gemm_x3_tune(int force_cfg, int splitk_target);
-/* diagnostic (libppo built with -DPPO_X3_DIAG): 8 slots per workgroup of the last x3 forward
- * launched with PPO_X3_ABLATE=32 — s_memtime at start, after the prologue, after the mainloop, at
- * the end; s_memrealtime (100 MHz, one clock for every XCD) at start and end; returns the slots */
-int    ppo_x3_stamps(unsigned long long* out, int n);
-/* diagnostic: the same for the double-buffered bf16 GEMM (gemm16.hip, -DPPO_G16_ABLATE=32 builds; else 0) */
-int    ppo_g16_stamps(unsigned long long* out, int n);
 /* average device µs of one x3 launch (fp32 operands; op as ppo_bench_gemm) */
 double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int splitk_target);
 

@@ -424,11 +424,7 @@ __global__ __launch_bounds__(TPB) void cluster_phase_kernel(ClArgs a) {
                     // slice-major partials [slice][cw][b][HC] (each workgroup's later read of its own slice
                     // is one contiguous block; the row-major [cw][b][H] form read HC columns of every 1-KB row)
                     const int k = 16 * tk + 4 * q;
-#ifdef CLU_G1ROWS
-                    st16_sc1(rG1, (cw * BB + 16 * tb + c) * H + k, acc);
-#else
                     st16_sc1(rG1, (((k / HC) * NWG + cw) * BB + 16 * tb + c) * HC + k % HC, acc);
-#endif
                 }
             }
             // bias gradient of layer 1 (fixed order)
@@ -464,11 +460,7 @@ __global__ __launch_bounds__(TPB) void cluster_phase_kernel(ClArgs a) {
                 f32x4 v[NWG / 2];
 #pragma unroll
                 for (int cc = 0; cc < NWG / 2; ++cc)
-#ifdef CLU_G1ROWS
-                    v[cc] = ld16_sc1(rG1, ((half * (NWG / 2) + cc) * BB + b) * H + c0 + jq);
-#else
                     v[cc] = ld16_sc1(rG1, (((c0 / HC) * NWG + half * (NWG / 2) + cc) * BB + b) * HC + jq);
-#endif
                 f32x4 s = v[0];
 #pragma unroll
                 for (int cc = 1; cc < NWG / 2; ++cc) s += v[cc];
@@ -813,13 +805,9 @@ int phip_cluster_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     static_assert(bytes <= 160 * 1024, "cluster: LDS");
     // one workgroup in every `active_stride`: blocks b and b + 8 are dealt to one XCD (observed,
     // MI355X_MICROARCH.md § Workgroup dispatch), so stride 8 puts the phase on one XCD, 4 on two, 1 on
-    // all eight; correctness never depends on it (PPO_CLUSTER_STRIDE overrides; 1, 2, 4 or 8)
+    // all eight; correctness never depends on it
     // (value phase — the longer — on one XCD, policy on two: 16 + 8 ≤ 32 CUs wherever they land)
-    int stride = ph->policy ? 4 : 8;
-    if (const char* st = getenv("PPO_CLUSTER_STRIDE")) {
-        const int v = atoi(st);
-        if (v == 1 || v == 2 || v == 4 || v == 8) stride = v;
-    }
+    const int stride = ph->policy ? 4 : 8;
     auto kfn = cluster_phase_kernel<256, HC>;
     static bool attr = false;
     if (!attr) {
@@ -861,9 +849,7 @@ int phip_cluster_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     a.X1 = ws.X1; a.Y = ws.Y; a.G1 = ws.G1; a.ctr = ws.ctr; a.err = d_err;
     a.timeout = host_timeout_ticks();
     a.active_stride = stride;
-    // stride 8 puts a phase on one XCD (blocks b, b + 8 share one); the policy phase then takes XCD 4
-    // so the two concurrent phases never share CUs
-    a.active_offset = stride == 8 && ph->policy ? 4 : 0;
+    a.active_offset = 0;
     static const char* names[12] = {"gather", "L0", "barrier A", "h1 load", "L1+Y", "barrier B", "head+bwd",
                                     "G1+gW1 adam", "barrier C", "g1+gW0", "adam", "step->next"};
     if (getenv("PPO_CLUSTER_STAMPS")) a.stamps = host_stamps(12, "cluster", names, ph->policy, a.total_steps, NWG);

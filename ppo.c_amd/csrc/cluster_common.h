@@ -11,17 +11,11 @@
 #include <cmath>
 #include <cstdint>
 
-#ifndef CLU_REPL
-#define CLU_REPL 8                                   // barrier counter replicas (128-B lines; ≤ 64)
-#endif
-#ifndef CLU_RSTRIDE
-#define CLU_RSTRIDE 32                               // words between replicas (32: adjacent 128-B lines)
-#endif
+constexpr int CLU_REPL = 8;                          // barrier counter replicas (128-B lines; ≤ 64)
+constexpr int CLU_RSTRIDE = 32;                      // words between replicas (32: adjacent 128-B lines)
 constexpr int CLU_CTR_BYTES = 4 * CLU_RSTRIDE * CLU_REPL;
-#ifndef CLU_SLEEP
-#define CLU_SLEEP 4                                  // s_sleep between barrier polls (× 64 clocks): 32 pollers
+constexpr int CLU_SLEEP = 4;                         // s_sleep between barrier polls (× 64 clocks): 32 pollers
                                                      // at 1 slowed every barrier (C4 value step 75 → 69 µs at 4)
-#endif
 
 namespace clu {
 

@@ -41,34 +41,21 @@ constexpr int T12 = (H / 16) / NWAVE;                // gW1 / gW2 tiles per wave
 constexpr int T0 = (SPMAX + 15) / 16 / NWAVE;        // gW0 tiles per wave (3)
 constexpr int RPW = BB / NWG;                        // head rows per workgroup (2)
 constexpr int NSTAMP = 18;
-#ifndef CLU_PPAD
-#define CLU_PPAD 0                                   // floats of padding per row of the Pa / Pb partial slabs
-#endif
-constexpr int PH = H + CLU_PPAD;                     // Pa / Pb row pitch
-#ifndef CLU_PSLICE
-#define CLU_PSLICE 1                                 // Pa / Pb slice-major ([slice][p][b][HC]); 0: row-major [p][b][H]
-#endif
-// Slice-major: a workgroup's reduction of its own 16 columns over the 32 partials is one contiguous
+constexpr int PH = H;                                // Pa / Pb floats per (partial, row): no padding
+// Pa / Pb are slice-major ([slice][p][b][HC]), not row-major ([p][b][H]): a workgroup's reduction of its
+// own 16 columns over the 32 partials is one contiguous
 // 128 KB block. Row-major, it read 64 B from every 2-KB row (2,048 loads at one address offset mod 2 KB),
 // and the four slices at offsets 384-511 mod 1024 B (6, 7, 22, 23) were 1.5-1.8 µs slower at barriers A
-// and F in every placement (PPO_CLUSTER_ROT moved the slow workgroups with their slices): the step
-// waits for them. Slice-major: every slice 13.1 / 5.9 µs (was 14.0 / 7.5, slow 15.5 / 9.3); C4 B = 64
+// and F in every placement (rotating the slices over the workgroups moved the slow workgroups with their
+// slices): the step waits for them. Slice-major: every slice 13.1 / 5.9 µs (was 14.0 / 7.5, slow 15.5 / 9.3); C4 B = 64
 // 9.51-9.69 s per update vs 10.44-10.51 row-major, same box (profiles/r06_c4b64_partial_layout.txt).
 // float offset of partial p's row b, hidden unit slice·HC + j, in a Pa / Pb slab
 __device__ __forceinline__ int pidx(int slice, int p, int b, int j) {
-#if CLU_PSLICE
     return ((slice * NWG + p) * BB + b) * HC + j;
-#else
-    return (p * BB + b) * PH + slice * HC + j;
-#endif
 }
-#ifndef CLU_GW_PRE
-#define CLU_GW_PRE 1                                 // weight-gradient tiles whose operands load under the P partial
-#endif
-#ifndef CLU_FWD_NG
-#define CLU_FWD_NG 4                                 // forward k-groups of 16 in flight per lane (16 — a whole
+constexpr int CLU_GW_PRE = 1;                        // weight-gradient tiles whose operands load under the P partial
+constexpr int CLU_FWD_NG = 4;                        // forward k-groups of 16 in flight per lane (16 — a whole
                                                      // K half — measured slower: 5.7 vs 4.9 µs per layer)
-#endif
 static_assert(T12 * NWAVE * 16 == H && T0 * NWAVE * 16 >= SPMAX && RPW * NWG == BB, "tile counts");
 
 struct DArgs {
@@ -88,8 +75,6 @@ struct DArgs {
     unsigned *ctr, *err;
     unsigned long long timeout;                      // barrier wait bound (realtime ticks)
     int active_stride, active_offset;                // workgroup b works iff b % stride == offset
-    int rot;                                         // PPO_CLUSTER_ROT (diagnostic): workgroup cw owns hidden
-                                                     // slice (cw + rot) mod NWG — separates slice from placement
     unsigned long long* stamps;                      // PPO_CLUSTER_STAMPS: workgroup 0, steps 0..63
     unsigned long long* arr;                         // PPO_CLUSTER_STAMPS=2: every workgroup's arrival and exit
                                                      // time at every barrier, steps 0..63 [64][6][2][NWG]
@@ -358,7 +343,7 @@ __global__ __launch_bounds__(TPB) void cluster_deep_kernel(DArgs a) {
     if (a.stamps && threadIdx.x == 0)
         a.stamps[64 * 32 + cw] = ((unsigned long long)__builtin_amdgcn_s_getreg((20) | (0 << 6) | (15 << 11)) << 32) |
                                  __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));
-    const int c0 = ((cw + a.rot) % NWG) * HC;
+    const int c0 = cw * HC;
     extern __shared__ float lds[];
     int* flag = reinterpret_cast<int*>(lds + L::flag);
     const int tid = threadIdx.x;
@@ -405,9 +390,7 @@ __global__ __launch_bounds__(TPB) void cluster_deep_kernel(DArgs a) {
             asm volatile("" : "+v"(tid));
             const int lane = tid & 63, w = tid >> 6, c = lane & 15, q = lane >> 4;
             CD_STAMP(0);
-#ifndef CLU_NO_PREFETCH
             asm volatile("" ::"v"(pf));                                  // (the prefetch has landed)
-#endif
             const int cur = step & 1;
             const int* rows = reinterpret_cast<const int*>(lds + L::rows) + cur * BB;
             const int tc = L::tgt + cur * BB, oc = L::olp + cur * BB, acb = L::act + cur * BB * OP;
@@ -465,7 +448,6 @@ __global__ __launch_bounds__(TPB) void cluster_deep_kernel(DArgs a) {
             cluster_arrive(a.ctr);
             CD_BAR_STAMP(1, 0);
             if (has_next) gather_act(a, lds, cur ^ 1);                   // the next minibatch, part 2
-#ifndef CLU_NO_PREFETCH
             // rows 2cw, 2cw + 1 of the next minibatch from HBM into the caches (each workgroup two, so
             // every row is fetched once before the 32 workgroups read all of them at the next layer 0)
             if (has_next && tid < 2 * (S / 4)) {
@@ -473,7 +455,6 @@ __global__ __launch_bounds__(TPB) void cluster_deep_kernel(DArgs a) {
                 const int r = tid / (S / 4), k = 4 * (tid % (S / 4));
                 pf = *reinterpret_cast<const f32x4*>(a.state + (long)rn[RPW * cw + r] * S + k);
             }
-#endif
             ok = cluster_wait(a.ctr, a.err, nbar++, NWG, flag, cw, a.timeout);          // B: h2 published
             if (!ok) break;
             CD_BAR_STAMP(1, 1);
@@ -559,6 +540,8 @@ __global__ __launch_bounds__(TPB) void cluster_deep_kernel(DArgs a) {
                     float* yr = lds + L::hrow + tid * GP;                 // y, then ∂L/∂y in place
                     float* gl = yr + OP;                                   // log σ row terms
                     float part;
+                    // (the two `!a.policy` arms below are dead inside this `else`; deleting them reorders
+                    // six instructions of the kernel, so they stay until the kernel is next retimed)
                     if (!a.policy) {                                       // loss.cu:5-23
                         const float y = yr[0], t = lds[tc + i];
                         const float d = t - y;
@@ -765,11 +748,7 @@ int phip_cluster_deep_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     static_assert(bytes <= 160 * 1024, "cluster_deep: LDS");
     // one workgroup in every `active_stride` (cluster.hip): 2 spreads each phase over four XCDs, so the
     // value and policy phases (64 workgroups, one per CU) fit wherever they land
-    int stride = 2;
-    if (const char* st = getenv("PPO_CLUSTER_STRIDE")) {
-        const int v = atoi(st);
-        if (v == 1 || v == 2 || v == 4 || v == 8) stride = v;
-    }
+    constexpr int stride = 2;
     static bool attr = false;
     if (!attr) {
         PPO_CHECK(hipFuncSetAttribute((const void*)cluster_deep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -810,10 +789,7 @@ int phip_cluster_deep_update(const PhipTinyNet* net, const PhipTinyPhase* ph) {
     a.ctr = ws.ctr; a.err = d_err;
     a.timeout = host_timeout_ticks();
     a.active_stride = stride;
-    // stride 8 puts a phase on one XCD (blocks b, b + 8 share one); the policy phase then takes XCD 4
-    // so the two concurrent phases never share CUs
-    a.active_offset = stride == 8 && ph->policy ? 4 : 0;
-    if (const char* r = getenv("PPO_CLUSTER_ROT")) a.rot = ((atoi(r) % NWG) + NWG) % NWG;
+    a.active_offset = 0;
     static const char* names[NSTAMP] = {"L0", "bar A", "L1", "bar B", "L2+Y", "bar C", "head", "bar D",
                                         "g3+P2", "gW2 adam", "bar E", "g2+P1", "gW1 adam", "bar F",
                                         "g1 reduce", "gW0 adam", "gb0+b0", "step->next"};

@@ -37,16 +37,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int NT_ = 256;
 
-#ifndef PPO_G16_ABLATE
-#define PPO_G16_ABLATE 0          // diagnostic builds only (tools/build_variant.sh): 1 no MFMA, 2 no epilogue
-#endif                            // stores, 4 no steady-state global loads, 8 no steady-state LDS stores,
-                                  // 16 no fragment reads, 32 stamps, 64 no bias / mask loads, 128 grad_W plain stores
-#if PPO_G16_ABLATE & 32
-// s_memtime of wave 0 of each workgroup: start, after the mainloop, epilogue issued, stores drained;
-// s_memrealtime (100 MHz) at start and drained
-__device__ unsigned long long g_g16_stamps[8192 * 8];
-#endif
-
 enum Op { OP_NT = 0, OP_NN = 1, OP_TN = 2 };
 
 struct Args {
@@ -438,9 +428,7 @@ __global__ __launch_bounds__(NT_, 2) void gemm_bf16_kernel(Args a) {
                     }
                 } else if (ok) {
                     float* dst = static_cast<float*>(a.C) + off;
-                    if (PPO_G16_ABLATE & 128) {                 // diagnostic: plain stores
-                        *dst = v;
-                    } else if (a.splits > 1) {
+                    if (a.splits > 1) {
                         atomicAdd(dst, v);
                     } else {
                         *dst = v;
@@ -459,7 +447,6 @@ __global__ __launch_bounds__(NT_, 2) void gemm_bf16_kernel(Args a) {
 // forward's ReLU′ bits are applied on this row-major read-back, 8 columns per lane
 template <int OP, int BM, int BN, int NTH>
 __device__ __forceinline__ void c_image_out(const Args& a, const unsigned short* cimg, int m0, int n0, int tid) {
-    constexpr int AB = PPO_G16_ABLATE;
     constexpr int CP = BN + 32;
     __syncthreads();
     constexpr int CH = BN / 8;                        // 16-B chunks per tile row (4 per 32-bit word)
@@ -471,8 +458,7 @@ __device__ __forceinline__ void c_image_out(const Args& a, const unsigned short*
         for (int it = 0; it < IT; ++it) {
             const int idx = tid + it * NTH;
             const int grow = min(m0 + idx / CH, a.M - 1), gcol = n0 + (idx % CH) * 8;
-            mword[it] = (a.bits_in && !(AB & 64)) ? a.bits_in[(long)grow * a.wpr + (min(gcol, a.N - 1) >> 5)]
-                                                   : ~0u;
+            mword[it] = a.bits_in ? a.bits_in[(long)grow * a.wpr + (min(gcol, a.N - 1) >> 5)] : ~0u;
         }
     }
 #pragma unroll
@@ -512,13 +498,11 @@ __device__ __forceinline__ void c_image_out(const Args& a, const unsigned short*
 
 // Epilogue of the 256×256 kernels (8 waves of (TM·32)×(TN·32), 32×32 accumulator blocks: lane (r, h)
 // holds column r, rows 4h + (e&3) + 8(e>>2)).  LDS (BM × (BN + 32) bf16) must be free on entry.
-template <int OP, int BM, int BN, int TM, int TN, int NTH, typename TC, typename S>
+template <int OP, int BM, int BN, int TM, int TN, int NTH, typename TC>
 __device__ __forceinline__ void epilogue256(const Args& a, f32x16 (&acc)[TM][TN], unsigned short* lds, int m0,
-                                            int n0, int wm, int wn, int tid, S&& stamp) {
+                                            int n0, int wm, int wn, int tid) {
     constexpr int WM = TM * 32, WN = TN * 32;
-    constexpr int AB = PPO_G16_ABLATE;
     const int lane = tid & 63, r = lane & 31, h = lane >> 5;
-    (void)stamp;
     // bf16 output: the tile goes through LDS (free after the last barrier) as packed column pairs,
     // then out as 16-B stores, 32 lanes per 512-B row segment; the ReLU′ bits (forward) and the
     // incoming mask (grad_x) are applied on that row-major read-back, 8 columns per lane, so the
@@ -533,7 +517,7 @@ __device__ __forceinline__ void epilogue256(const Args& a, f32x16 (&acc)[TM][TN]
 #pragma unroll
             for (int jj = 0; jj < TN; ++jj) {
                 const int col = n0 + wn * WN + jj * 32 + r;
-                bcol[jj] = (OP == OP_NT && a.bias && !(AB & 64)) ? a.bias[col < a.N ? col : a.N - 1] : 0.f;
+                bcol[jj] = (OP == OP_NT && a.bias) ? a.bias[col < a.N ? col : a.N - 1] : 0.f;
             }
 #pragma unroll
             for (int i = 0; i < TM; ++i)
@@ -562,11 +546,6 @@ __device__ __forceinline__ void epilogue256(const Args& a, f32x16 (&acc)[TM][TN]
                     }
                 }
             c_image_out<OP, BM, BN, NTH>(a, cimg, m0, n0, tid);
-            if constexpr ((AB & 32) != 0) {
-                stamp(2);
-                __builtin_amdgcn_s_waitcnt(0);
-                stamp(3);
-            }
             return;
         }
     }
@@ -687,40 +666,17 @@ __global__ __launch_bounds__(NTH, 1) void gemm_bf16_db_kernel(Args a) {
         sa.load(PA, a.lda, m0, a.M, j * BK, K, vec, tid);
         sb.load(PB, a.ldb, n0, a.N, j * BK, K, vec, tid);
     };
-    constexpr int AB = PPO_G16_ABLATE;
-    auto stamp = [&](int slot) {
-#if PPO_G16_ABLATE & 32
-        if (tid == 0 && b < 8192) {
-            g_g16_stamps[b * 8 + slot] = __builtin_amdgcn_s_memtime();
-            if (slot == 0 || slot == 3) g_g16_stamps[b * 8 + 4 + slot / 3] = __builtin_amdgcn_s_memrealtime();
-        }
-#endif
-        (void)slot;
-    };
-    stamp(0);
     auto kstep = [&](const unsigned short* img, int ks) {
         bf16x8 fa[TM], fb[TN];
-        if constexpr (AB & 16) {
 #pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)ks, 1u, 2u, 3u});
+        for (int i = 0; i < TM; ++i) fa[i] = SA::frag(img, wm * WM + i * 32 + r, ks, lane);
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = __builtin_bit_cast(bf16x8, u32x4{(unsigned)lane, 1u, 2u, 3u});
-        } else {
-#pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = SA::frag(img, wm * WM + i * 32 + r, ks, lane);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = SB::frag(img + SA::IMG, wn * WN + j * 32 + r, ks, lane);
-        }
+        for (int j = 0; j < TN; ++j) fb[j] = SB::frag(img + SA::IMG, wn * WN + j * 32 + r, ks, lane);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if constexpr (AB & 1) {
-                    acc[i][j][0] += __builtin_bit_cast(u32x4, fa[i])[0] ^ __builtin_bit_cast(u32x4, fb[j])[1];
-                } else {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                }
-            }
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
     };
 
     const int nk = (K + BK - 1) / BK;
@@ -740,12 +696,12 @@ __global__ __launch_bounds__(NTH, 1) void gemm_bf16_db_kernel(Args a) {
         kstep(cur, 0);
         __builtin_amdgcn_sched_barrier(0);
         kstep(cur, 1);
-        if constexpr (!(AB & 8)) sa.store(nxt, tid);
+        sa.store(nxt, tid);
         __builtin_amdgcn_sched_barrier(0);
         kstep(cur, 2);
-        if constexpr (!(AB & 8)) sb.store(nxt + SA::IMG, tid);
+        sb.store(nxt + SA::IMG, tid);
         __builtin_amdgcn_sched_barrier(0);
-        if constexpr (!(AB & 4)) load(j + 2);
+        load(j + 2);
         kstep(cur, 3);
         __syncthreads();
     }
@@ -761,20 +717,8 @@ __global__ __launch_bounds__(NTH, 1) void gemm_bf16_db_kernel(Args a) {
         __syncthreads();
     }
 
-    stamp(1);
-    if constexpr (AB & 2) {                                   // keep the accumulators live
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int jj = 0; jj < TN; ++jj)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) t += acc[i][jj][e];
-        if (t == 1234.5f) static_cast<float*>(a.C)[tid] = t;
-        return;
-    }
     static_assert((size_t)BM * (BN + 32) <= 2 * (size_t)BUF, "gemm16 (db): C image exceeds LDS");
-    epilogue256<OP, BM, BN, TM, TN, NTH, TC>(a, acc, lds, m0, n0, wm, wn, tid, stamp);
+    epilogue256<OP, BM, BN, TM, TN, NTH, TC>(a, acc, lds, m0, n0, wm, wn, tid);
 }
 
 // s_waitcnt vmcnt(N) with N a compile-time count of this wave's outstanding vector-memory operations
@@ -793,16 +737,11 @@ __device__ __forceinline__ void wait_vmcnt() {
 // to land before tile j+1's first fragment read, exposing the whole DMA latency once per k-tile.
 // Hidden from that pass, each image is published only by the loops' own `s_waitcnt vmcnt` +
 // barrier (the "memory" clobber keeps the compiler's LDS accesses in program order around it).
-// PPO_G16_BUILTIN_DMA=1 restores the builtin (A/B).
 typedef __attribute__((address_space(3))) void* lds_vptr;
 typedef __attribute__((address_space(1))) void* glb_vptr;
 __device__ __forceinline__ void dma16(glb_vptr g, lds_vptr l) {
-#if defined(PPO_G16_BUILTIN_DMA) && PPO_G16_BUILTIN_DMA
-    __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
-#else
     const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)l);
     asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(g), "{m0}"(base) : "memory");
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -845,17 +784,6 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma_kernel(Args a) {
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int wm = w / WARPS_N, wn = w % WARPS_N;
     const int r = lane & 31, h = lane >> 5;
-    constexpr int AB = PPO_G16_ABLATE;
-    auto stamp = [&](int slot) {
-#if PPO_G16_ABLATE & 32
-        if (tid == 0 && b < 8192) {
-            g_g16_stamps[b * 8 + slot] = __builtin_amdgcn_s_memtime();
-            if (slot == 0 || slot == 3) g_g16_stamps[b * 8 + 4 + slot / 3] = __builtin_amdgcn_s_memrealtime();
-        }
-#endif
-        (void)slot;
-    };
-    stamp(0);
 
     // DMA sources: wave w fills the images' 1-KiB pieces 4w..4w+3 (piece q: rows 8q..8q+7 of a
     // k-contiguous image, k-rows 2q, 2q+1 of the n-contiguous one); element offsets without k0
@@ -927,13 +855,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma_kernel(Args a) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if constexpr (AB & 1) {
-                    acc[i][j][0] += __builtin_bit_cast(u32x4, f.a[i])[0] ^ __builtin_bit_cast(u32x4, f.b[j])[1];
-                } else {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i], f.b[j], acc[i][j], 0, 0, 0);
-                }
-            }
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[i], f.b[j], acc[i][j], 0, 0, 0);
     };
 
     unsigned short* const buf0 = lds;
@@ -960,10 +883,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma_kernel(Args a) {
         // every wave is done reading `cur`, and tile j+1 has landed: refill `cur` with tile j+2
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (j + 2 < nk && !(AB & 4)) dma(j + 2, cur);
+        if (j + 2 < nk) dma(j + 2, cur);
     }
-    stamp(1);
-    epilogue256<OP, BM, BN, TM, TN, NTH, TC>(a, acc, lds, m0, n0, wm, wn, tid, stamp);
+    epilogue256<OP, BM, BN, TM, TN, NTH, TC>(a, acc, lds, m0, n0, wm, wn, tid);
 }
 
 // ---------------------------------------------------------------------------
@@ -1225,12 +1147,8 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma_tn_kernel(Args a, float*
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                if constexpr (PPO_G16_ABLATE & 1)
-                    acc[i][j][0] += __builtin_bit_cast(u32x4, fa[i])[0] ^ __builtin_bit_cast(u32x4, fb[j])[1];
-                else
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-            }
+            for (int j = 0; j < TN; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
     };
 
     const bool do_bias = a.gbias != nullptr && tn == 0;
@@ -1268,18 +1186,7 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_dma_tn_kernel(Args a, float*
         step(cur, 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (j + 2 < nk && !(PPO_G16_ABLATE & 4)) dma(j + 2, cur);
-    }
-    if constexpr (PPO_G16_ABLATE & 2) {                       // keep the accumulators live
-        float t = 0.f;
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int jj = 0; jj < TN; ++jj)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) t += acc[i][jj][e];
-        if (t == 1234.5f) static_cast<float*>(a.C)[tid] = t;
-        return;
+        if (j + 2 < nk) dma(j + 2, cur);
     }
 
     // a.cvec (split-K with gb = gW + l·n, the flat gradient layout): each split's bias partial goes
@@ -1361,23 +1268,15 @@ void launch_db(Args a) {
     PPO_LAUNCH_CHECK();
 }
 
-int g_dma16 = -1;           // LDS-DMA 256×256 kernel: -1 = read PPO_G16_DMA (default 1 = on), 0 off
+int g_dma16 = 1;            // LDS-DMA 256×256 kernel: 1 = on, 0 = off (ppo_gemm16_dma)
 
-int dma16_setting() {
-    if (g_dma16 < 0) {
-        const char* e = getenv("PPO_G16_DMA");
-        g_dma16 = e ? atoi(e) : 1;
-    }
-    return g_dma16;
-}
-// the 16×16×32 MFMA form for bf16-output DMA products and for grad_W (the round-2 PPO_G16_MF16 switch
-// is gone: the 32×32×16 form remains only where this one does not apply).  Measured at C5 16384×1024×1024: forward 41.5 -> 37.3 µs,
+// the 16×16×32 MFMA form for bf16-output DMA products and for grad_W (the 32×32×16 form remains only
+// where this one does not apply).  Measured at C5 16384×1024×1024: forward 41.5 -> 37.3 µs,
 // grad_x 42.1 -> 40.7 µs (C5 update 276.4 -> 271.9 ms); grad_W 82.6 -> 80.3 µs (273.7 -> 271.8 ms)
 constexpr int g_mf16 = 1;
 
 template <int OP, typename TC>
 bool launch_dma(Args a) {
-    dma16_setting();
     const bool ok = g_dma16 >= 1 && a.vec && a.acopy == nullptr && a.K % 64 == 0 && a.lda % 8 == 0 &&
                     a.ldb % 8 == 0 && (OP == OP_NT || a.N % 256 == 0) &&
                     (long)a.M * a.lda < (1L << 31) && (long)(OP == OP_NT ? a.N : a.K) * a.ldb < (1L << 31) &&
@@ -1473,8 +1372,7 @@ inline bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 inline int epl(int t) { return t ? 8 : 4; }
 
 // grad_W on the LDS-DMA TN tile (bf16 g and x): l a multiple of 256, n of 128, the batch of 64;
-// PPO_G16_TN=0 keeps the register-staged kernel, PPO_G16_TN_BN=128|256 (or ppo_gemm16_tn_width)
-// sets the tile width — 256 × 128 by default: at C5 (1024-wide layers, 16384 rows) its 32 tiles × 8
+// ppo_gemm16_tn_width sets the tile width — 256 × 128 by default: at C5 (1024-wide layers, 16384 rows) its 32 tiles × 8
 // splits beat 16 tiles of 256 × 256 × 16 splits in the update, 235.5 vs 244.0 ms
 // (profiles/r04_c5_gradw_tile_ab.txt): half the split-partial bytes for the slab reduce
 // (C5's hidden layers, 16384 × 1024 × 1024, are the only production bf16 × bf16 grad_W shape: the
@@ -1484,7 +1382,7 @@ int g_tn_bn = 128;                                 // ppo_gemm16_tn_width change
 constexpr int g_tn_target = 256;                   // workgroup target of the DMA TN split-K grid: one per CU
 
 bool launch_dma_tn(float* gW, float* gb, const void* g, const void* x, int m, int n, int l, int zeroed) {
-    if (g_tn_dma == 0 || dma16_setting() == 0 || g_force16 >= 0) return false;
+    if (g_tn_dma == 0 || g_dma16 == 0 || g_force16 >= 0) return false;
     if (l % 256 != 0 || n % 128 != 0 || m % 64 != 0 || !al16(g) || !al16(x) || !al16(gW)) return false;
     if ((long)m * l >= (1L << 31) || (long)m * n >= (1L << 31)) return false;
     const int BN = g_tn_bn == 256 && n % 256 == 0 ? 256 : 128;
@@ -1665,19 +1563,8 @@ double ppo_bench_gemm16(int op, int m, int n, int l, int iters, int cfg, int spl
     return 1000.0 * ms / (iters > 0 ? iters : 1);
 }
 
-int ppo_g16_stamps(unsigned long long* out, int n) {
-#if PPO_G16_ABLATE & 32
-    phip_sync();
-    PPO_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_g16_stamps), sizeof(unsigned long long) * (size_t)std::min(n, 8192 * 8)));
-    return 8192 * 8;
-#else
-    (void)out; (void)n;
-    return 0;
-#endif
-}
-
 int ppo_gemm16_dma(int on) {
-    const int old = dma16_setting();
+    const int old = g_dma16;
     if (on == 0 || on == 1) g_dma16 = on;
     return old;
 }

@@ -50,10 +50,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 constexpr int BK = 16;
 enum { OP_NT = 0, OP_NN = 1, OP_TN = 2 };
 
-// diagnostic stamps (ABL & 32): s_memtime of wave 0 of each workgroup at kernel start, after the
-// prologue, after the mainloop, at the end
-__device__ unsigned long long g_x3_stamps[8192 * 8];
-
 struct X3Args {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
@@ -258,7 +254,7 @@ struct StageX3 {
         return MN ? k0 + k + q * KSTEP < kend : k0 + k + 4 * q < kend;
     }
     // ONE: the values are exact in one bf16 plane (0/1 masks): plane 0 only, planes 1 and 2 never read
-    template <bool FULL, bool NOSPLIT = false, bool ONE = false>
+    template <bool FULL, bool ONE = false>
     __device__ __forceinline__ void store(unsigned short* img, int k0, int kend) {
         f32x4* vv = v;
         if (!FULL) {
@@ -266,10 +262,8 @@ struct StageX3 {
             for (int q = 0; q < NV; ++q)
                 if (!kvalid(q, k0, kend)) vv[q] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
-        // NOSPLIT (timing ablation only): raw bits into the planes, no split VALU
         auto split = [](f32x4 f, u32x2& p0, u32x2& p1, u32x2& p2) {
-            if (NOSPLIT) { p0 = p1 = p2 = u32x2{__builtin_bit_cast(unsigned, f[0]), __builtin_bit_cast(unsigned, f[3])}; }
-            else if (ONE) { p0 = u32x2{pack2(f[0], f[1]), pack2(f[2], f[3])}; p1 = p2 = p0; }
+            if (ONE) { p0 = u32x2{pack2(f[0], f[1]), pack2(f[2], f[3])}; p1 = p2 = p0; }
             else split4(f, p0, p1, p2);
         };
         if (MN) {
@@ -345,10 +339,6 @@ struct StageX3 {
 // (grad_W: fewer split-K workgroups per output tile, so fewer f32 atomics — they execute at the
 // memory side at ≈1.3 TB/s chip-wide, MI355X_MICROARCH.md § Global float atomics).
 // ---------------------------------------------------------------------------------------------
-// ABL (timing ablations, results wrong; PPO_X3_ABLATE, -DPPO_X3_DIAG builds, cfgs 0 and 3): 1 = no
-// MFMAs, 2 = no split / LDS stores, 4 = no epilogue stores, 8 = no global loads after the prologue,
-// 32 = stamps, 64 = no split (raw bits stored to the planes), 128 = every other k-tile barrier skipped,
-// 256 / 512 = no B / A fragment reads after the prologue (stale fragments: the LDS read cost)
 // forward / grad_x epilogue: 32×32 accumulator block (i, j): lane (r, h) holds column r, rows
 // 4h + (e&3) + 8(e>>2).  Branch-free per element: the bias loads hoisted, the ReLU′-bit ballots in a
 // loop version of their own, grad_x's mask words brought into LDS (BM·BN/32 words, free on entry) by
@@ -449,16 +439,13 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                     const int row = r0 + dr;
                     const bool ok = col_ok && row < a.M;
                     float v = acc[i][j][e];
+                    // (plain stores: non-temporal ones measured neutral, profiles/r03nt_x3_ntstore_ab.txt)
                     float* dst = a.C + (long)row * a.ldc + col;
                     if (OP == OP_NT) {
                         v += bcol[j];
                         if constexpr (TH) v = tanhf(v);
                         else if (a.relu) v = v > 0.f ? v : 0.f;
-#ifdef PPO_X3_NTSTORE
-                        if (ok) __builtin_nontemporal_store(v, dst);
-#else
                         if (ok) *dst = v;
-#endif
                         if constexpr (YD) yp[e] += v * wcol[j];
                         if constexpr (BITS) {
                             const unsigned long long bb = __ballot(ok && v > 0.f);
@@ -469,11 +456,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                         if (FG) v *= gsh[lr0 + dr];
                         if (masked && !((mk[(lr0 + dr) * WPT + ((c0 - n0) >> 5)] >> r) & 1u)) v = 0.f;
                         if constexpr (TH) v = ppo::tanh_bwd(v, hv[e]);
-#ifdef PPO_X3_NTSTORE
-                        if (ok) __builtin_nontemporal_store(v, dst);
-#else
                         if (ok) *dst = v;
-#endif
                     }
                 }
                 if (BITS && r < 16) {
@@ -491,8 +474,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
 // FOLD: the value-head fold variant (forward: ydot / ypart; grad_x / grad_W: A synthesised from h).
 // The body of one workgroup (block b of a grid of `grid` blocks), a device function so that one launch
 // could run several products' tiles (a grad_W + grad_x pair was measured and not kept, see phip_x3_bwd_w)
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
-          bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
 __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     constexpr int NTG = NTH / KG;                                  // threads per k-group
     constexpr int NW = NTG / 64, WARPS_N = NW / WARPS_M;
@@ -537,13 +519,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     const int lt = KG > 1 ? tid % NTG : tid;
     const int w = lt >> 6;
     const int wm = w / WARPS_N, wn = w % WARPS_N;
-    auto stamp = [&](int slot) {
-        if (tid == 0 && b < 8192) {
-            g_x3_stamps[b * 8 + slot] = __builtin_amdgcn_s_memtime();
-            if (slot == 0 || slot == 3) g_x3_stamps[b * 8 + 4 + slot / 3] = __builtin_amdgcn_s_memrealtime();
-        }
-    };
-    if (ABL & 32) stamp(0);
     const int r = lane & 31, h = lane >> 5;
 
     f32x16 acc[TM][TN];
@@ -620,17 +595,14 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     // fragment registers: plane p of the A (fa) and B (fb) operand tiles of the current k-tile
     bf16x8 fa[3][TM][KH], fb[3][TN][KH];
     // (fold: A is a 0/1 mask in plane 0 only — its planes 1, 2 and their three products are skipped)
-    bool first_rd = true;                                          // (ABL 256 / 512: the prologue's reads only)
     auto rd_a = [&](const unsigned short* img, int p) {
         if (syn && p != 0) return;
-        if ((ABL & 512) && !first_rd) return;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int kh = 0; kh < KH; ++kh) fa[p][i][kh] = SA::frag(img + p * SA::PLANE, wm * WM + i * 32 + r, lane, kh);
     };
     auto rd_b = [&](const unsigned short* img, int p) {
-        if ((ABL & 256) && !first_rd) return;
 #pragma unroll
         for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -640,13 +612,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     // plane product A_pa·B_pb of the current k-tile (the six with pa + pb ≤ 2)
     auto mm = [&](int pa, int pb) {
         if (syn && pa != 0) return;
-        if (ABL & 1) {               // keep the fragment reads live
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j][0] += (float)fa[pa][i][0][0] + (float)fb[pb][j][0][1];
-            return;
-        }
 #pragma unroll
         for (int kh = 0; kh < KH; ++kh)
 #pragma unroll
@@ -672,7 +637,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         constexpr bool FULL = decltype(FULLc)::value, COPY = OP == OP_NT && decltype(COPYc)::value;
         constexpr bool BSUM = OP == OP_TN && decltype(COPYc)::value;
         constexpr bool SYN = OP != OP_NT && decltype(SYNc)::value;
-        if ((ABL & 2) && k0 != kbeg) return;
         if constexpr (COPY) {
             if (((k0 - kbeg) / KB) % a.tiles_n == tn) sa.copy_out(a.acopy, a.K, m0, a.M, k0, kend);
         }
@@ -695,7 +659,7 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 }
             }
         }
-        sa.template store<FULL, (ABL & 64) != 0, SYN>(img, k0, kend);
+        sa.template store<FULL, SYN>(img, k0, kend);
         if constexpr (BSUM && !SYN) {
 #pragma unroll
             for (int q = 0; q < SA::NV; ++q) bs[q] += sa.v[q];
@@ -703,17 +667,15 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     };
     auto stage_b = [&](auto FULLc, unsigned short* img, int k0) {
         constexpr bool FULL = decltype(FULLc)::value;
-        if ((ABL & 2) && k0 != kbeg) return;
         if constexpr (FMB_ == 1) {                       // fold: x rows scaled by g (grad_W), W rows by w (grad_x)
 #pragma unroll
             for (int q = 0; q < SB::NV; ++q) sb.v[q] *= sb.gq[q];
         }
-        sb.template store<FULL, (ABL & 64) != 0>(img + SA::SIZE, k0, kend);
+        sb.template store<FULL>(img + SA::SIZE, k0, kend);
     };
     auto load = [&](auto FULLc, auto SYNc, int k0) {
         constexpr bool FULL = decltype(FULLc)::value;
         constexpr bool SYN = OP != OP_NT && decltype(SYNc)::value;
-        if ((ABL & 8) && k0 != kbeg) return;
         sa.template load<FULL, SYN ? FMA_ : 0>(k0, kend);
         sb.template load<FULL, SYN ? FMB_ : 0>(k0, kend);
     };
@@ -743,15 +705,11 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     // — each of the region's MFMAs followed by NV VALU, one DS and one VMEM instruction.  Without it
     // the compiler front-loads a region's split VALU (≈30 in a row) ahead of its MFMAs, and the two
     // lock-stepped waves of a SIMD leave the matrix pipe idle together: 3761 → 3400 cycles per k-tile
-    // at C4 (profiles/r03_x3_stamps.txt).  grad_W measured no gain (PPO_X3_SGB=0/1 builds).
+    // at C4 (profiles/r03_x3_stamps.txt).  grad_W measured no gain with the request.  (s_setprio around
+    // the MFMAs, and a static priority for the second-dispatched half of the waves: no gain either.)
     auto region_end = [&](auto NVc) {
-#if defined(PPO_X3_SGB) || !defined(PPO_X3_NO_SGB)
         constexpr int NVV = decltype(NVc)::value;
-#ifdef PPO_X3_SGB
-        constexpr bool SGB = true;
-#else
         constexpr bool SGB = OP != OP_TN;
-#endif
         if constexpr (SGB) {
 #pragma unroll
             for (int q = 0; q < TM * TN * KH; ++q) {
@@ -761,7 +719,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
             }
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
     };
     using I0 = std::integral_constant<int, 0>;
@@ -773,9 +730,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         const bool has1 = STEADY || j + 1 < NK, has2 = STEADY || j + 2 < NK, has3 = STEADY || j + 3 < NK;
         rd_a(cur, 1);
         rd_b(cur, 1);
-#ifdef PPO_X3_PRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
         mm(2, 0);
         if (has1) rd_a(n1, 2);
         region_end(I0{});
@@ -797,10 +751,7 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         if (has1) rd_a(n1, 0);
         region_end(I0{});
         mm(1, 1);
-#ifdef PPO_X3_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-        if (!((ABL & 128) && (j & 1))) __syncthreads();      // (ABL 128, timing only: every other barrier)
+        __syncthreads();
     };
     auto mainloop = [&](auto COPYc, auto SYNc) {
         unsigned short* cur = ring;
@@ -811,9 +762,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         if (NK > 2) load_t(SYNc, 2);
         __syncthreads();
         if (NK > 0) { rd_a(cur, 2); rd_b(cur, 0); rd_b(cur, 2); rd_a(cur, 0); }
-        if ((ABL & 768) && NK > 0) { rd_a(cur, 1); rd_b(cur, 1); }
-        first_rd = false;
-        if (ABL & 32) stamp(1);
         // steady state: tiles j+2 and j+3 exist and are full.  grad_W's loop is unrolled by the ring
         // length, so every ring slot's fragment / staging addresses are loop-invariant registers (no
         // per-iteration slot arithmetic: 130 → 92 VALU per k-tile); the 256×256 kernels have no
@@ -839,9 +787,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
             unsigned short* t = cur; cur = n1; n1 = n2; n2 = t;
         }
     };
-#ifdef PPO_X3_PRIO2
-    if ((tid >> 6) >= NTH / 128) __builtin_amdgcn_s_setprio(1);   // the second-dispatched half wins VALU arbitration
-#endif
     // (COPYc: the gather copy / Σ g; SYNc: the folded value head's synthesised A)
     auto run = [&](auto COPYc) {
         if constexpr (syn) mainloop(COPYc, T{});
@@ -849,9 +794,6 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     };
     if (do_copy || do_bsum) run(T{});
     else run(F{});
-#ifdef PPO_X3_PRIO2
-    __builtin_amdgcn_s_setprio(0);
-#endif
 
     // LDS scratch after the mainloop (the images are no longer read): bias-gradient partial sums,
     // then the k-groups' accumulator exchange
@@ -923,23 +865,10 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
             }
     }
 
-    if (ABL & 32) stamp(2);
-    if (ABL & 4) {
-        float t = 0.f;                                          // keep every accumulator live
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) t += acc[i][j][e];
-        if (t == 12345.678f) a.C[tid] = 1.f;
-        return;
-    }
     if constexpr (OP != OP_TN) {
         static_assert(BM * (BN / 32 + 1) * 4 <= KG * NS * BUF * 2, "x3 epilogue: mask words exceed LDS");
         x3_epilogue_out<OP, BM, BN, TM, TN, NTH, OP == OP_NT && FOLD != 0, OP == OP_NN && FOLD != 0, TH>(
             a, acc, lds, m0, n0, wm, wn, tid);
-        if (ABL & 32) stamp(3);
         return;
     }
     // grad_W epilogue: every load a block needs is issued before its stores
@@ -982,21 +911,13 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 if (OP == OP_NT) {
                     v += bcol;
                     if (a.relu) v = v > 0.f ? v : 0.f;
-#ifdef PPO_X3_NTSTORE
-                    if (ok) __builtin_nontemporal_store(v, dst);
-#else
                     if (ok) *dst = v;
-#endif
                     if (a.bits_out) {
                         const unsigned long long bb = __ballot(ok && v > 0.f);
                         if (r == e) word = h ? (unsigned)(bb >> 32) : (unsigned)bb;
                     }
                 } else if (OP == OP_NN) {
-#ifdef PPO_X3_NTSTORE
-                    if (ok) __builtin_nontemporal_store(keep[e] ? v : 0.f, dst);
-#else
                     if (ok) *dst = keep[e] ? v : 0.f;
-#endif
                 } else if (ok) {
                     if (a.slab) a.slab[(long)(kbeg / a.kchunk) * a.M * a.N + (long)row * a.N + col] = v;
                     else if (a.splits > 1) atomicAdd(dst, v);
@@ -1008,29 +929,22 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 if (row < a.M && c0 < a.N) a.bits_out[(long)row * a.wpr + (c0 >> 5)] = word;
             }
         }
-    if (ABL & 32) stamp(3);
 }
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
-          bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
 __global__ __launch_bounds__(NTH, OCC) void gemm_x3_kernel(X3Args a) {
-    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, TH>(a, (int)blockIdx.x, (int)gridDim.x);
+    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,TH>(a, (int)blockIdx.x, (int)gridDim.x);
 }
-
-#ifdef PPO_X3_DIAG
-int g_x3_ablate = -1;
-#endif
 
 int g_x3_last_slots = 0;                 // the last launch's ypart slots (tiles_n × waves along N)
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int ABL = 0, int FOLD = 0, int KB = BK,
-          bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
 void launch_x3(X3Args a) {
     // a tanh launch (forward: a.tanh; grad_x: a.hpost) runs the TH kernels — the tanh epilogue compiled apart, so
     // the ReLU / identity kernels keep the registers they had (x3_epilogue_out)
-    if constexpr (!TH && OP != OP_TN && FOLD == 0 && ABL == 0) {
+    if constexpr (!TH && OP != OP_TN && FOLD == 0) {
         if (OP == OP_NT ? a.tanh != 0 : a.hpost != nullptr) {
-            launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, true>(a);
+            launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,true>(a);
             return;
         }
     }
@@ -1062,7 +976,7 @@ void launch_x3(X3Args a) {
             a.vh_ypart = nullptr;
         }
     }
-    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, ABL, FOLD, KB, TH>;
+    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,TH>;
     if (lds > 64 * 1024) {
         static bool attr = false;                      // once per instantiation (the whole LDS)
         if (!attr) {
@@ -1127,59 +1041,25 @@ constexpr CfgX3 kCfgX3[] = {{256, 256, 1, 1, 16}, {128, 128, 1, 2, 16}, {128, 12
 int g_force_x3 = -1;
 int g_split_x3 = 0;
 
+template <int OP, int FOLD>
+void launch_tile_x3(int c, const X3Args& a) {
+    switch (c) {
+        case 0: launch_x3<OP, 256, 256, 4, 512, 2, 1, FOLD>(a); break;
+        case 2: launch_x3<OP, 128, 128, 4, 512, 2, 1, FOLD>(a); break;
+        case 4: launch_x3<OP, 64, 64, 2, 256, 4, 1, FOLD>(a); break;
+        case 5: launch_x3<OP, 256, 128, 4, 512, 2, 1, FOLD>(a); break;
+        case 6: launch_x3<OP, 64, 64, 2, 256, 2, 1, FOLD, 32>(a); break;
+        case 3:
+            if constexpr (OP == OP_TN) { launch_x3<OP, 128, 128, 2, 512, 2, 2, FOLD>(a); break; }
+            [[fallthrough]];
+        default: launch_x3<OP, 128, 128, 2, 256, 2, 1, FOLD>(a); break;
+    }
+}
+
 template <int OP>
 void launch_cfg_x3(int c, const X3Args& a) {
-    if (a.ydot || a.fold_g) {                      // the value-head fold variants
-        switch (c) {
-            case 0: launch_x3<OP, 256, 256, 4, 512, 2, 1, 0, 1>(a); return;
-            case 2: launch_x3<OP, 128, 128, 4, 512, 2, 1, 0, 1>(a); return;
-            case 4: launch_x3<OP, 64, 64, 2, 256, 4, 1, 0, 1>(a); return;
-            case 5: launch_x3<OP, 256, 128, 4, 512, 2, 1, 0, 1>(a); return;
-            case 6: launch_x3<OP, 64, 64, 2, 256, 2, 1, 0, 1, 32>(a); return;
-            case 3:
-                if constexpr (OP == OP_TN) { launch_x3<OP, 128, 128, 2, 512, 2, 2, 0, 1>(a); return; }
-                [[fallthrough]];
-            default: launch_x3<OP, 128, 128, 2, 256, 2, 1, 0, 1>(a); return;
-        }
-    }
-#ifdef PPO_X3_DIAG
-    if (g_x3_ablate < 0) {
-        const char* e = getenv("PPO_X3_ABLATE");
-        g_x3_ablate = e ? atoi(e) : 0;
-    }
-    if (g_x3_ablate && (c == 0 || c == 4 || (c == 3 && OP == OP_TN))) {
-        auto run = [&](auto ABLc) {
-            constexpr int A = decltype(ABLc)::value;
-            if (c == 4) launch_x3<OP, 64, 64, 2, 256, 4, 1, A>(a);
-            else if constexpr (OP == OP_TN) launch_x3<OP, 128, 128, 2, 512, 2, 2, A>(a);
-            else launch_x3<OP, 256, 256, 4, 512, 2, 1, A>(a);
-        };
-        switch (g_x3_ablate) {
-            case 1: run(std::integral_constant<int, 1>{}); return;
-            case 2: run(std::integral_constant<int, 2>{}); return;
-            case 4: run(std::integral_constant<int, 4>{}); return;
-            case 8: run(std::integral_constant<int, 8>{}); return;
-            case 32: run(std::integral_constant<int, 32>{}); return;
-            case 64: run(std::integral_constant<int, 64>{}); return;
-            case 128: run(std::integral_constant<int, 128>{}); return;
-            case 256: run(std::integral_constant<int, 256>{}); return;
-            case 512: run(std::integral_constant<int, 512>{}); return;
-            case 768: run(std::integral_constant<int, 768>{}); return;
-            default: break;
-        }
-    }
-#endif
-    switch (c) {
-        case 0: launch_x3<OP, 256, 256, 4, 512, 2, 1>(a); break;
-        case 2: launch_x3<OP, 128, 128, 4, 512, 2, 1>(a); break;
-        case 4: launch_x3<OP, 64, 64, 2, 256, 4, 1>(a); break;
-        case 5: launch_x3<OP, 256, 128, 4, 512, 2, 1>(a); break;
-        case 6: launch_x3<OP, 64, 64, 2, 256, 2, 1, 0, 0, 32>(a); break;
-        case 3:
-            if constexpr (OP == OP_TN) { launch_x3<OP, 128, 128, 2, 512, 2, 2>(a); break; }
-            [[fallthrough]];
-        default: launch_x3<OP, 128, 128, 2, 256, 2, 1>(a); break;
-    }
+    if (a.ydot || a.fold_g) launch_tile_x3<OP, 1>(c, a);      // the value-head fold variants
+    else launch_tile_x3<OP, 0>(c, a);
 }
 
 // forward / grad_x: the largest tile whose grid still gives every CU a workgroup (one round of
@@ -1200,10 +1080,7 @@ int pick_x3(int M, int N, int op) {
     // 32-k small tiles (cfg 6): each launch alone is faster (shard forward 21.1 -> 20.0 µs, C3 14.4 -> 13.5),
     // but at 72 KiB of LDS per workgroup the other loop's kernels and the carried reduces no longer fit
     // beside them — the shard update 71.6 -> 73.1 ms, C3 26.8 -> 27.2 with every small product on it
-    // (profiles/r06_x3_bk32_ab.txt); PPO_X3_BK32 = 1 (every small product) / nt (forwards only) / 0 (default)
-    const char* e = getenv("PPO_X3_BK32");
-    if (e && e[0] == '1') return 6;
-    if (e && e[0] == 'n' && op == OP_NT) return 6;
+    // (profiles/r06_x3_bk32_ab.txt)
     return 4;
 }
 
@@ -1490,14 +1367,6 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
     phip_free(x); phip_free(W); phip_free(y); phip_free(b); phip_free(gw); phip_free(bits); phip_free(fold);
     phip_free(hp);
     return 1000.0 * ms / (iters > 0 ? iters : 1);
-}
-
-// diagnostic: the stamps of the last PPO_X3_ABLATE=32 launch (4 per workgroup; libppo built with
-// -DPPO_X3_DIAG, tools/build_variant.sh)
-int ppo_x3_stamps(unsigned long long* out, int n) {
-    phip_sync();
-    PPO_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_x3_stamps), sizeof(unsigned long long) * (size_t)std::min(n, 8192 * 8)));
-    return 8192 * 8;
 }
 
 }  // extern "C"

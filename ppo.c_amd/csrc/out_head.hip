@@ -150,9 +150,7 @@ __device__ __forceinline__ void store_cols(float* __restrict__ p, const float (&
 // T: storage of x, W and gx — float (fp32 mode) or unsigned short (bf16 mode: x and gx bf16, W the
 // bf16 parameter shadow, and the head gradient rounded to bf16 before its products, as the separate
 // bf16 GEMMs round the fp32 operand they stage)
-#ifndef OUTHEAD_PF
-#define OUTHEAD_PF 4                                 // rows in flight per wave (one wave per row)
-#endif
+constexpr int OUTHEAD_PF = 4;                        // rows in flight per wave (one wave per row)
 
 // VC: the value head with loss clipping (vclip.h) — its own instantiation, so that with clipping off the
 // kernel is the one compiled without it (the clip branch costs the width-256 kernels a wave of occupancy)
@@ -560,9 +558,6 @@ struct FusedArgs {
 };
 
 constexpr int FR = 16;                                             // rows per block
-#ifndef PPO_FUSED_ABL
-#define PPO_FUSED_ABL 0        // diagnostic builds only: 1 no μ MFMA, 2 no head, 4 no gx / gW3 rows, 8 no h loads
-#endif
 
 template <int NPT>
 constexpr size_t fused_lds_floats() {
@@ -633,7 +628,7 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
 #pragma unroll
         for (int v = 0; v < NPF; ++v) {
             const int e = t + 256 * v, r = e / (N / 4), cq = e % (N / 4);
-            if (!(PPO_FUSED_ABL & 8)) *reinterpret_cast<f32x4v*>(hs + r * HPs + 4 * cq) = hpf[v];
+            *reinterpret_cast<f32x4v*>(hs + r * HPs + 4 * cq) = hpf[v];
         }
 #pragma unroll
         for (int v = 0; v < 2; ++v) {
@@ -651,7 +646,7 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
             const float* B0 = ws + c * HPs + w * KW + q;
             const float* B1 = ws + 16 * HPs + w * KW + q;
 #pragma unroll 4
-            for (int kk = 0; kk < KW && !(PPO_FUSED_ABL & 1); kk += 8) {
+            for (int kk = 0; kk < KW; kk += 8) {
                 const float av = Ar[kk], bv = Ar[kk + 4];
                 a0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, B0[kk], a0, 0, 0, 0);
                 b0 = __builtin_amdgcn_mfma_f32_16x16x4f32(bv, B0[kk + 4], b0, 0, 0, 0);
@@ -682,7 +677,7 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
             dterm[e] = ppo::log_prob_term(lss[j], z);
         }
         __syncthreads();
-        if (t < nr && !(PPO_FUSED_ABL & 2)) {                     // the head, one row per thread (wave 0)
+        if (t < nr) {                   // the head, one row per thread (wave 0)
             float lp = ppo::log_prob_start(A);
 #pragma unroll
             for (int j = 0; j < A; ++j) lp = ppo::log_prob_sub(lp, dterm[t * A + j]);
@@ -698,12 +693,12 @@ __global__ __launch_bounds__(256, 2) void policy_out_fused_kernel(FusedArgs p) {
             mus[r * AP + j] = d * e2s[j] * gr;
         }
         __syncthreads();
-        if (t < A && !(PPO_FUSED_ABL & 2)) {                      // ordered sums over the block's rows
+        if (t < A) {                    // ordered sums over the block's rows
             for (int r = 0; r < nr; ++r) gls += lst[r * AP + t];
         } else if (t >= 32 && t < 32 + A) {
             for (int r = 0; r < nr; ++r) gbs += mus[r * AP + t - 32];
         }
-        for (int r = 0; r < nr && !(PPO_FUSED_ABL & 4); r += 2) {  // two rows at a time (independent chains)
+        for (int r = 0; r < nr; r += 2) {// two rows at a time (independent chains)
             const bool two = r + 1 < nr;
             float gv0[A], gv1[A], xv0[NPT], xv1[NPT];
 #pragma unroll

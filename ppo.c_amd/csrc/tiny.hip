@@ -34,10 +34,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-#ifndef PPO_TINY_TPB
-#define PPO_TINY_TPB 1024
-#endif
-constexpr int TPB = PPO_TINY_TPB;
+constexpr int TPB = 1024;
 constexpr int NWAVES = TPB / 64;
 constexpr int MAXL = 8;            // linear layers
 
@@ -443,12 +440,7 @@ __device__ __forceinline__ f32x4 c2_tile(const float* __restrict__ A, int i0, co
     return acc;
 }
 
-#ifndef PPO_C2_ADAM_U
-#define PPO_C2_ADAM_U 2   // Adam rounds interleaved per batch
-#endif
-#ifndef PPO_C2_AB
-#define PPO_C2_AB 0       // diagnostic builds only: 1 no Adam arithmetic, 2 no next-minibatch gather,
-#endif                    // 4 no layer-0 gradient phase work, 8 no hidden-layer MFMA tiles
+constexpr int C2_ADAM_U = 2;   // Adam rounds interleaved per batch
 using ppo::row_sum16;
 __device__ __forceinline__ float sum16(float v) { return ppo::row_sum16(v); }
 __device__ __forceinline__ float sum64(float v) { return ppo::wave_sum64(v); }
@@ -617,11 +609,8 @@ __global__ __launch_bounds__(TPB) void tiny_c2_kernel(TinyArgs a) {
             // G1 = (G2·W1) ⊙ 1[Y1 > 0] tiles; columns 4w .. 4w+3 of gb1 = Σ_b G2 and gW2 = Σ_b g·Y2
             // (16 row slices of 4 per column, lanes 16s + col); gb2 and the loss sums by wave 15 ----
             {
-                f32x4 aw = {0.f, 0.f, 0.f, 0.f}, ax = aw;
-                if constexpr (!(PPO_C2_AB & 8)) {
-                    aw = c2_tile<BB, false, P, false, P>(G2, ti0, Y1, tj0, lane);
-                    ax = c2_tile<H, true, P, false, P>(G2, ti0, Pp + Ly::oW1, tj0, lane);
-                }
+                const f32x4 aw = c2_tile<BB, false, P, false, P>(G2, ti0, Y1, tj0, lane);
+                const f32x4 ax = c2_tile<H, true, P, false, P>(G2, ti0, Pp + Ly::oW1, tj0, lane);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int r = ti0 + 4 * q + e, k = tj0 + c;
@@ -671,11 +660,11 @@ __global__ __launch_bounds__(TPB) void tiny_c2_kernel(TinyArgs a) {
             // its Adam step at once; every other parameter's gradient is complete since the barrier ----
             int nep = ep, nkb = kb + 1;
             if (nkb >= a.num_batches) { nep = ep + 1; nkb = 0; }
-            const bool next = !(PPO_C2_AB & 2) && step + 1 < a.total_steps && nep < a.n_epochs && gt >= 0;
+            const bool next = step + 1 < a.total_steps && nep < a.n_epochs && gt >= 0;
             Row nr{};
             if (next) nr = fetch(nep, nkb);
             const float st = a.steps[2 * step], bc2 = a.steps[2 * step + 1];
-            if (!(PPO_C2_AB & 4)) {
+            {
                 const int j = tid >> 4, rs = tid & 15;
                 float s4[SP] = {};
 #pragma unroll
@@ -708,7 +697,7 @@ __global__ __launch_bounds__(TPB) void tiny_c2_kernel(TinyArgs a) {
             // the rest of the image (W1, b1, W2, b2 and their pads), one element per thread per round,
             // the rounds unrolled so their dependent Adam chains interleave
             {
-                constexpr int NR = (Ly::NPAR - Ly::oW1 + TPB - 1) / TPB, U = PPO_C2_ADAM_U;
+                constexpr int NR = (Ly::NPAR - Ly::oW1 + TPB - 1) / TPB, U = C2_ADAM_U;
 #pragma unroll
                 for (int r0 = 0; r0 < NR; r0 += U) {
                     float pu[U], gu[U], mu[U], vu[U];
@@ -718,10 +707,7 @@ __global__ __launch_bounds__(TPB) void tiny_c2_kernel(TinyArgs a) {
                         pu[r] = Pp[e]; gu[r] = Gd[e]; mu[r] = Mv[e]; vu[r] = Vv[e];
                     }
 #pragma unroll
-                    for (int r = 0; r < U; ++r) {
-                        if constexpr (PPO_C2_AB & 1) pu[r] += gu[r] * st;
-                        else adam_elem(pu[r], gu[r], mu[r], vu[r], st, a.b1, a.b2, bc2);
-                    }
+                    for (int r = 0; r < U; ++r) adam_elem(pu[r], gu[r], mu[r], vu[r], st, a.b1, a.b2, bc2);
 #pragma unroll
                     for (int r = 0; r < U; ++r) {
                         const int e = Ly::oW1 + tid + (r0 + r) * TPB;

@@ -112,8 +112,6 @@ _SIGS = {
     "ppo_gemm16_tn_width": (C.c_int, [C.c_int]),
     "ppo_gemm_x3_tune": (C.c_int, [C.c_int, C.c_int]),
     "ppo_bench_gemm_x3": (C.c_double, [C.c_int] * 7),
-    "ppo_x3_stamps": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
-    "ppo_g16_stamps": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_int]),
     "ppo_set_compute_dtype": (C.c_int, [_P, C.c_int]),
     "ppo_rollout_device": (None, [_P, C.c_int, C.c_int, C.c_int, C.c_ulonglong]),
     "nn_set_compute_dtype": (C.c_int, [_P, C.c_int]),
@@ -280,7 +278,7 @@ _lib = None
 
 
 def load(path=None):
-    """Load libppo.so (PPO_LIB overrides the path: diagnostic variants built by tools/build_variant.sh).
+    """Load libppo.so (PPO_LIB overrides the path: another build of the library, tools/ab_bench.sh).
 
     In a process that also uses torch, `import torch` BEFORE calling load(): libppo then binds to the
     HIP runtime torch already mapped (same soname, libamdhip64.so.7) and the process holds one runtime.

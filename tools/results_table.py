@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """BASELINE.md §3 rows from one box's bench lines: tools/results_table.py DIR_A DIR_B prints the markdown
-rows (DIR_A: r04_final_a.sh's bench.json = C4; DIR_B: r04_final_b.sh's per-config lines)."""
+rows (DIR_A: bench.json of the default C4 run; DIR_B: one bench line per config)."""
 import json
 import os
 import sys
