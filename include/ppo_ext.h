@@ -124,7 +124,10 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[22]=the reward normaliser's running count, out[23]=rewards clamped by the last update's scaling (an exact
  * integer: integer atomics only; under data parallelism THIS RANK's rows), out[24]=rewards it scaled (limit)
  * (reward normalisation, ppo_set_reward_norm: all three 0 while it is off; callers passing n <= 22 see no
- * change). */
+ * change).
+ * With the categorical policy (ppo_set_action_dist 1) out[4] is the mean row entropy of the last policy step's
+ * minibatch (Σ H / rows as the head accumulated it; 0 before the first policy step; under data parallelism THIS
+ * RANK's rows), not the Gaussian entropy of log σ. */
 void ppo_read_stats(void* ppo, double* out, int n);
 void ppo_reset_stats(void* ppo);
 
@@ -232,6 +235,50 @@ int    ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float 
                               const float* d_old_lp, float* d_mu, const float* d_x, const float* d_W, const float* d_b,
                               float* d_lp, float* d_grad_mu, float* d_gx, float* d_gW, float* d_grad_log_std,
                               double* loss);
+/* The action distribution (default 0; not in the reference).  dist 0 is the diagonal Gaussian — today's behaviour,
+ * every path bit for bit.  dist 1 is a categorical policy over A = action_size choices: μ's A outputs are the logits
+ * z, log σ is unused.  The per-row arithmetic is written once (csrc/ppo_math.h cat_*), fp32, in this order:
+ *     M = max_k z_k;  e_k = expf(z_k − M);  s = Σ_k e_k;  lp = (z_a − M) − logf(s);  p_k = e_k / s
+ *     H = logf(s) − (Σ_k e_k·(z_k − M)) / s
+ *     g = ∂loss/∂lp of the clipped surrogate (the Gaussian head's own function)
+ *     ∂loss/∂z_k = g·([k == a] − p_k) + (ent_coeff / m)·p_k·((z_k − M) − logf(s) + H)
+ *     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+ * ACTIONS keep their storage: a row's action stays A floats in the trajectory buffer, column 0 the chosen index as
+ * an exact float, columns 1 … A−1 written as 0; no buffer layout, gather or struct changes.  SAMPLING is inverse-CDF
+ * from one uniform per row: u = u01(philox(counter, offset, key).x) ∈ (0, 1], c_k = Σ_{j<=k} e_j (fp32, k ascending),
+ * a = min{k : u·c_{A−1} <= c_k} (csrc/rng.h lists the streams).  ppo_rollout_device, ppo_eval_device and
+ * ppo_fill_synthetic sample this way; ppo_eval_device with deterministic != 0 takes argmax_k z_k, the lowest index
+ * on ties.
+ * THE UPDATE.  While it is on, a policy step is forward → the categorical head (one launch, csrc/categorical.hip) →
+ * backward, and ppo_update runs the multi-launch loop (no single-workgroup / cluster phases, no graph replay, no
+ * fused output-layer kernels: those embed the Gaussian head), as with gradient clipping.  It works together with
+ * gradient clipping, value-loss clipping, target-KL early stopping (x = lp − old log-prob with the categorical lp),
+ * both normalisers, tanh networks, both fp32 GEMM engines and data parallelism: no collective is added and the order
+ * of collectives does not depend on the setting.  The head writes no gradient to log σ; the entropy Adam still runs
+ * each step, on a zero gradient, which leaves log σ bit-identical.
+ * The reference-API entry points that have only a policy or only host data stay Gaussian: sample_action,
+ * compute_log_prob*, ppo_sample_action_device, policy_loss_and_grad*, and ppo_policy_kl_device.  The host rollout
+ * has no discrete form: train_ppo_epoch / eval_ppo END THE PROCESS with a message while it is on.
+ * The setting lives with the PPO, not in GaussianPolicy (whose layout is the reference's).  Not part of a
+ * checkpoint: set it again after load_ppo.
+ * Returns 0, or −1 with the setting unchanged for an unknown dist, and for dist 1 with A < 2, A > 4096 or bf16
+ * compute mode (ppo_set_compute_dtype(ppo, 1) in turn returns −1 while dist is 1).  nn_set_compute_dtype called on
+ * the policy network itself has no handle to the PPO and is not declined: ppo_update ENDS THE PROCESS with a message
+ * when it finds a categorical policy whose μ is in bf16 mode. */
+int    ppo_set_action_dist(void* ppo, int dist);
+int    ppo_get_action_dist(void* ppo);                    /* 0 for a NULL ppo */
+/* The categorical head on caller-supplied device arrays (a test entry: the update calls the same launcher):
+ * logits [m, A], action [m, A] (column 0 the index), adv [m], old log-prob [m] → d_grad [m, A] = ∂loss/∂logits,
+ * d_lp [m], d_ent [m] = the row entropies, *loss.  2 <= A <= 4096.  Synchronises.  Returns 0, or −1 for bad
+ * arguments (a NULL array, m <= 0, A out of range, NaN eps) with nothing recorded for ppo_last_error. */
+int    ppo_categorical_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                   const float* d_old_lp, int m, int A, float eps, float ent_coeff, float* d_grad,
+                                   float* d_lp, float* d_ent, double* loss);
+/* The categorical sampler on caller-supplied device arrays: logits [m, A], row i's uniform from
+ * philox(i, offset, key).x → d_action [m, A] (index, 0, …, 0) and d_log_prob [m].  Synchronises.  Returns 0, or −1
+ * for bad arguments, as above. */
+int    ppo_categorical_sample_device(const float* d_logits, int m, int A, unsigned long long key,
+                                     unsigned long long offset, float* d_action, float* d_log_prob);
 /* Running observation normalisation (off by default; not in the reference; Stable-Baselines3 VecNormalize,
  * CleanRL NormalizeObservation).  Per observation column j the running state is, in double, a shared count n,
  * mean[j] and M2[j] (the sum of squared deviations; population variance M2/n, as SB3's RunningMeanStd).  The
@@ -412,7 +459,8 @@ int    ppo_episode_scan_device(const float* d_reward, const unsigned char* d_ter
  * the environments are reset exactly as a fresh PPO's first ppo_rollout_device(…, seed) resets them, the Philox
  * keys are derived from `seed` as there, and the step counter is local and starts at 0 — so with deterministic
  * == 0 a fresh PPO's evaluation sees, bit for bit, the trajectory of that PPO's first training rollout.
- * deterministic != 0: the action is μ's output bit for bit (no noise drawn, no log-prob).  Rewards and flags go
+ * deterministic != 0: the action is μ's output bit for bit (no noise drawn, no log-prob) — with the categorical
+ * policy, argmax over the logits, the lowest index on ties.  Rewards and flags go
  * to an n_envs × horizon scratch (written as the rollout writes the buffer's, the segment-end truncation and
  * cont[] included) and are scanned once at the end by the scan above with `gamma`, from fresh states:
  * out[0..7] has the layout of ppo_episode_stats over the episodes completed within the horizon, out[8] is the
@@ -424,7 +472,8 @@ int    ppo_episode_scan_device(const float* d_reward, const unsigned char* d_ter
  * Adam state are left bit-identical; only μ's forward workspaces (its activations of the last forward) change.
  * Scratch is O(n_envs·(S + A) + n_envs·horizon·6 B), kept for the next call and freed by free_ppo.
  * Returns the values written (9), synchronising once to fill out; or −1 — no die, nothing run — for a NULL ppo or
- * out, n_envs <= 0, horizon <= 0, env_kind not 0 or 1, Pendulum with S != 3 or A != 1, a NaN gamma or n < 9. */
+ * out, n_envs <= 0, horizon <= 0, env_kind not 0, 1 or 2, Pendulum with S != 3 or A != 1, CartPole with S != 4,
+ * A != 2 or the Gaussian policy, a NaN gamma or n < 9. */
 int    ppo_eval_device(void* ppo, int n_envs, int horizon, int env_kind, unsigned long long seed, int deterministic,
                        float gamma, double* out, int n);
 /* the last GAE's state (compute_gae_cuda / ppo_update; synchronises): welford (may be NULL) ← the
@@ -452,7 +501,10 @@ void ppo_fill_synthetic(void* ppo, int n_envs, int horizon, unsigned long long s
  * over the E current observations, Gaussian sampling (Philox), one environment step — written
  * env-major into the device buffer (transition (e, t) at row e·horizon + t; each segment ends
  * truncated), ready for ppo_update.  env_kind 0 = Pendulum-v1 (S = 3, A = 1; gymnasium dynamics),
- * 1 = synthetic (any S, A).  Episodes continue across calls; the first call (or a change of
+ * 1 = synthetic (any S, A; with the categorical policy the chosen index i acts as 2·i/(A − 1) − 1),
+ * 2 = CartPole-v1 (S = 4, A = 2, the categorical policy only — ppo_set_action_dist; gymnasium's constants, explicit
+ * Euler, reward 1 per step, terminated at |x| > 2.4 or |θ| > 12°, truncated at 500 steps; index 1 pushes right);
+ * any other combination ends the process with a message.  Episodes continue across calls; the first call (or a change of
  * n_envs / env_kind) resets every environment from `seed`.  `seed` keys the Philox streams of the
  * policy noise, the environment's noise and its resets; the position in them advances with every
  * step of every call (a counter that starts at 0 with the PPO), so passing the same seed to every
@@ -470,7 +522,8 @@ int ppo_nn_input_rows(void* nn, float* out, int m);
  * master parameters / Adam / heads / GAE, bf16 storage of hidden activations and their gradients
  * (BASELINE config C5).  Returns 0, or −1 for an invalid dtype.  The bf16 kernels know ReLU and identity
  * layers only: dtype 1 on a network with a "tanh" layer (for ppo_set_compute_dtype: in either network)
- * returns −1 and leaves the setting unchanged; tanh networks run in fp32 mode, on both fp32 GEMM engines. */
+ * returns −1 and leaves the setting unchanged; tanh networks run in fp32 mode, on both fp32 GEMM engines.
+ * ppo_set_compute_dtype(ppo, 1) also returns −1 while the categorical policy is on (ppo_set_action_dist). */
 int ppo_set_compute_dtype(void* ppo, int dtype);
 int nn_set_compute_dtype(void* nn, int dtype);          /* NeuralNetwork* */
 

@@ -136,7 +136,10 @@ void phip_gather_rows_bf16(unsigned short* dst, const float* src, const int* row
 void phip_f32_to_bf16(unsigned short* dst, const float* src, long count);
 
 /* ---------------- batched device rollout (rollout.hip) ---------------- */
-/* env kinds: 0 = Pendulum-v1 (S = 3, A = 1), 1 = synthetic (any S, A) */
+/* env kinds: 0 = Pendulum-v1 (S = 3, A = 1), 1 = synthetic (any S, A), 2 = CartPole-v1 (S = 4, A = 2, categorical
+ * actions).  env_state holds PHIP_ENV_STATE(S) floats per environment.  cat != 0 (the step functions): column 0
+ * of an action row is a categorical index (kind 1 reads it as 2·index/(A − 1) − 1; kind 2 requires it) */
+#define PHIP_ENV_STATE(S) ((S) > 5 ? (S) : 5)
 void phip_rollout_rows(int* rows, int E, int T);             /* rows[t·E + e] = e·T + t */
 void phip_env_reset(int kind, float* env_state, float* state, int E, int T, int S, uint64_t seed);
 void phip_env_first_obs(int kind, const float* env_state, float* state, int E, int T, int S);
@@ -147,13 +150,13 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
  * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h) */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed);
+                   uint64_t seed, int cat);
 /* the evaluation's step (ppo_eval_device): the same dynamics (shared __device__ functions) over compact arrays —
  * obs [E, S] is the current observation, read and replaced in place, action [E, A]; reward / term / trunc are
  * written at row e·T + t and cont as phip_env_step writes them; nothing else is kept */
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed);
+                        uint64_t seed, int cat);
 
 /* ---------------- episode statistics (episode.hip) ---------------- */
 /* The scan of ppo_ext.h ppo_episode_scan_device plus its fold, two launches: E segments of T rows, cont (may be
@@ -261,6 +264,25 @@ void phip_policy_head(const float* mu, const float* log_std, const float* action
                       const float* old_lp, int m, int A, float epsilon, float ent_coeff,
                       float* grad_mu, float* grad_log_std, float* d_loss_accum,
                       int ls_zeroed);
+
+/* ---------------- categorical policy (categorical.hip) ---------------- */
+#define PHIP_CAT_MAX_A 4096
+/* the clipped-surrogate head over logits [m, A] (2 <= A <= PHIP_CAT_MAX_A), the chosen index in column 0 of
+ * action [m, A]: grad [m, A] = ∂loss/∂logits written, lp_out / ent_out (may be NULL) [m] = the row's log-prob /
+ * entropy written, d_loss_accum (may be NULL) += −Σ surrogate/m − ent_coeff·Σ H/m, d_ent_accum (may be NULL)
+ * += Σ H (both one floating-point atomic per workgroup).  One launch; log σ is not involved. */
+void phip_cat_head(const float* logits, const float* action, const float* adv, const float* old_lp, int m, int A,
+                   float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out, float* d_loss_accum,
+                   float* d_ent_accum);
+/* inverse-CDF sample of row e from u01(philox(e, offset, key).x); the action row (index, 0, …, 0) and the
+ * log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
+void phip_cat_sample(const float* logits, const int* rows, float* action, float* logprob, int m, int A, uint64_t key,
+                     uint64_t offset);
+/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
+void phip_cat_sample_rows(const float* logits, const int* rows, float* action, float* logprob, int E, int A,
+                          uint64_t key, uint64_t step);
+/* action[e] ← (argmax_k logits[e, k], 0, …, 0), the lowest index on ties */
+void phip_cat_argmax(const float* logits, float* action, int m, int A);
 
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
@@ -387,8 +409,9 @@ typedef struct {
 /* Σ (expm1(x) − x) and the clipped-row count of one policy minibatch (x = log-prob − old log-prob, rows of
  * μ [m, A]) into rec->sums; one launch, deterministic (no floating-point atomics, grid a function of m), no
  * host read.  decide_here != 0: the same launch also decides (below) from the local sums */
+/* dist: 0 = Gaussian; 1 = categorical — μ holds the logits, column 0 of the action the index, log σ is unread */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
-                    float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec);
+                    int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec);
 /* kl = sums[0] / rows_global, clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
  * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the
  * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so

@@ -50,6 +50,57 @@ __device__ __forceinline__ float surrogate(float adv, float lp, float old_lp, fl
                   !adv_pos * (ratio_neg * (1 - eps) + !ratio_neg * ratio));
 }
 
+// ---- Categorical policy over A choices (ppo_set_action_dist; no counterpart in the reference): the atoms of
+// one row, z its A logits and a the chosen index, all fp32:
+//     M   = max_k z_k
+//     e_k = expf(z_k − M)                                   cat_exp
+//     s   = Σ_k e_k        t = Σ_k e_k·(z_k − M)            k ascending inside each part the kernel sums: one lane
+//                                                           sums its own k, parts combine by the kernel's fixed tree
+//     ls  = logf(s)
+//     lp  = (z_a − M) − ls                                  cat_log_prob
+//     p_k = e_k / s
+//     H   = ls − t / s                                      cat_entropy
+//     g   = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)
+//     ∂loss/∂z_k = g·([k == a] − p_k) + (ent_coeff / m)·p_k·(((z_k − M) − ls) + H)          cat_grad
+//     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+// The signs are the Gaussian head's: loss = −mean surrogate − ent_coeff·entropy, once; the second gradient term
+// is ∂(−ent_coeff·H/m)/∂z_k = (ent_coeff/m)·p_k·(log p_k + H).  tests/categorical_ref.py restates it.
+__device__ __forceinline__ float cat_exp(float z, float M) { return expf(z - M); }
+__device__ __forceinline__ float cat_log_prob(float za, float M, float ls) { return (za - M) - ls; }
+__device__ __forceinline__ float cat_entropy(float ls, float t, float s) { return ls - t / s; }
+// cm = ent_coeff / m, formed once per launch by the caller
+__device__ __forceinline__ float cat_grad(float g, bool chosen, float z, float M, float s, float ls, float H,
+                                          float cm) {
+    const float p = cat_exp(z, M) / s;
+    return g * ((chosen ? 1.f : 0.f) - p) + cm * p * (((z - M) - ls) + H);
+}
+// one thread walks a whole row in index order (the sampler, the KL monitor, evaluation): M, s and — when t is
+// not NULL — t
+__device__ __forceinline__ float cat_row_max(const float* z, int A) {
+    float M = z[0];
+    for (int k = 1; k < A; ++k) M = fmaxf(M, z[k]);
+    return M;
+}
+__device__ __forceinline__ float cat_row_sum(const float* z, int A, float M, float* t) {
+    float s = 0.f, tt = 0.f;
+    for (int k = 0; k < A; ++k) {
+        const float e = cat_exp(z[k], M);
+        s += e;
+        tt += e * (z[k] - M);
+    }
+    if (t) *t = tt;
+    return s;
+}
+// the stored action row: column 0 holds the index as an exact float; anything outside [0, A) is clamped
+__device__ __forceinline__ int cat_index(float a0, int A) {
+    const int a = (int)a0;
+    return a < 0 ? 0 : (a >= A ? A - 1 : a);
+}
+__device__ __forceinline__ float cat_log_prob_row(const float* z, int A, int a) {
+    const float M = cat_row_max(z, A);
+    return cat_log_prob(z[a], M, logf(cat_row_sum(z, A, M, nullptr)));
+}
+
 // ---- Gaussian entropy (policy.cu:171-193): this constant, then += log σ_j for j ascending, at the call site
 // (the sum inside a helper compiled to other code than the kernels' own loops)
 __device__ __forceinline__ float entropy_start(int A) { return (float)(A * 0.5 * (1 + log(2 * M_PI))); }

@@ -20,6 +20,12 @@
 //     env decision   same key                           counter e         offset kEnv + 2g         .x .y reward noise, .z done
 //     env ε          same key                           counter e·S + j   offset kEnv + 2g + 1     .x .y   N(0, 1)
 //     reset          same key                           counter e (Pendulum: .x θ, .y θ̇) or e·S + j (.x)   offset kReset + g
+//   CartPole-v1 (env_kind 2): first reset and reset at counter e, .x .y .z .w → x, ẋ, θ, θ̇ ~ U(−0.05, 0.05)
+//   categorical policy (ppo_set_action_dist 1; categorical.hip; tests/categorical_ref.py restates these rows):
+//     ppo_fill_synthetic      action noise   key s0 ^ 5   counter i (row)   offset 0          .x   u01, inverse CDF
+//     ppo_rollout_device / ppo_eval_device
+//                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e   offset kNoise + g   .x   u01, inverse CDF
+//     ppo_categorical_sample_device(key, offset)          counter i (row)   offset `offset`   .x   u01, inverse CDF
 #pragma once
 
 #include <cmath>

@@ -13,7 +13,15 @@
 //            reset θ ~ U(−π, π), θ̇ ~ U(−1, 1) from Philox.
 //   kind 1 — synthetic (any S, A): o' = clip(0.95·o + 0.05·tanh(a[j mod A]) +
 //            0.05·ε, −1, 1); r = −0.01·mean(a²) + 0.1·ε; terminated ~ Bernoulli(1/500), reset
-//            o ~ U(−1, 1).
+//            o ~ U(−1, 1).  With a categorical policy (ppo_set_action_dist 1) the action row holds an index
+//            in column 0: every element reads tanh's argument as c = 2·index/(A − 1) − 1, whatever j, and
+//            the reward's action term becomes −0.01·c²; the noise, the done draw and the reset are unchanged.
+//   kind 2 — CartPole-v1 (S = 4, A = 2, categorical policy only): gymnasium's constants (g = 9.8, cart 1.0, pole
+//            0.1, half-length 0.5, force 10, τ = 0.02) and explicit Euler, in fp32 in the order of
+//            cartpole_advance below; action index 1 pushes right.  Terminated when |x| > 2.4 or |θ| > 12·2π/360
+//            after the step; reward 1 on every step, the terminating one included; TimeLimit at 500 steps sets
+//            truncated.  Per-env state (x, ẋ, θ, θ̇, steps); a reset draws the four U(−0.05, 0.05) from
+//            .x .y .z .w of one Philox draw at counter e.
 #include "dev.h"
 #include "ppo_math.h"
 #include "rng.h"
@@ -143,19 +151,22 @@ __global__ void pendulum_eval_kernel(float* __restrict__ es, float* __restrict__
 struct SynthStep { float o2, nxt, reward; bool done; };
 
 __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restrict__ ar, long k, int e, int j, int A,
-                                                   uint64_t step, uint64_t seed) {
+                                                   uint64_t step, uint64_t seed, int cat) {
     SynthStep s;
     const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
     s.done = u01(d.z) < 1.f / 500.f;
     const float eps = normal_at((uint64_t)k, kEnv + 2 * step + 1, seed);
-    float o2 = 0.95f * o + 0.05f * tanhf(ar[j % A]) + 0.05f * eps;
+    // categorical: the index of column 0 mapped onto [−1, 1]
+    const float c = cat ? 2.f * (float)ppo::cat_index(ar[0], A) / (float)(A - 1) - 1.f : 0.f;
+    float o2 = 0.95f * o + 0.05f * tanhf(cat ? c : ar[j % A]) + 0.05f * eps;
     o2 = fminf(fmaxf(o2, -1.f), 1.f);
     s.o2 = o2;
     s.reward = 0.f;
     if (j == 0) {
         float ss = 0.f;
         for (int q = 0; q < A; ++q) ss += ar[q] * ar[q];
-        s.reward = -0.01f * ss / (float)A + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
+        const float act_term = cat ? -0.01f * (c * c) : -0.01f * ss / (float)A;
+        s.reward = act_term + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
     }
     s.nxt = s.done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + step, seed).x) : o2;
     return s;
@@ -166,12 +177,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed) {
+                                  uint64_t seed, int cat) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed);
+    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed, cat);
     next_state[row * S + j] = s.o2;
     if (j == 0) {
         reward[row] = s.reward;
@@ -187,12 +198,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
 __global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                   float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed) {
+                                  uint64_t seed, int cat) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat);
     if (j == 0) {
         reward[row] = s.reward;
         term[row] = s.done ? 1 : 0;
@@ -201,6 +212,86 @@ __global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ ob
     }
     es[k] = s.nxt;
     obs[k] = s.nxt;
+}
+
+// One CartPole-v1 step of environment e from (x, ẋ, θ, θ̇, steps) under the action index a (1 pushes right), fp32
+// in exactly this order (tests/categorical_ref.py mirrors it): the transition's next observation and flags; on
+// return the state is what the next step starts from — the reset drawn where the episode ended.  The training
+// and the evaluation kernels both step through this, so the two cannot drift.
+struct CartPoleStep { float next[4]; bool term, limit; };
+
+__device__ __forceinline__ void cartpole_reset(float* st, uint64_t e, uint64_t offset, uint64_t seed) {
+    const u32x4 r = philox(e, offset, seed);
+    st[0] = -0.05f + 0.1f * u01(r.x);
+    st[1] = -0.05f + 0.1f * u01(r.y);
+    st[2] = -0.05f + 0.1f * u01(r.z);
+    st[3] = -0.05f + 0.1f * u01(r.w);
+    st[4] = 0.f;
+}
+
+__device__ __forceinline__ CartPoleStep cartpole_advance(float* st, int a, uint64_t e, uint64_t step, uint64_t seed) {
+    CartPoleStep o;
+    const float x = st[0], xd = st[1], th = st[2], thd = st[3];
+    const float force = a == 1 ? 10.f : -10.f;
+    const float ct = cosf(th), sn = sinf(th);
+    const float temp = (force + 0.05f * (thd * thd) * sn) / 1.1f;                  // polemass_length 0.05, total mass 1.1
+    const float thacc = (9.8f * sn - ct * temp) / (0.5f * (4.f / 3.f - 0.1f * (ct * ct) / 1.1f));
+    const float xacc = temp - 0.05f * thacc * ct / 1.1f;
+    o.next[0] = x + 0.02f * xd;
+    o.next[1] = xd + 0.02f * xacc;
+    o.next[2] = th + 0.02f * thd;
+    o.next[3] = thd + 0.02f * thacc;
+    const float steps = st[4] + 1.f;
+    o.term = fabsf(o.next[0]) > 2.4f || fabsf(o.next[2]) > 12.f * 2.f * (float)M_PI / 360.f;
+    o.limit = steps >= 500.f;
+    if (o.term || o.limit) {
+        cartpole_reset(st, e, kReset + step, seed);
+    } else {
+        for (int q = 0; q < 4; ++q) st[q] = o.next[q];
+        st[4] = steps;
+    }
+    return o;
+}
+
+// CartPole-v1: env state (x, ẋ, θ, θ̇, steps) in es[5e .. 5e+4]
+__global__ void cartpole_step_kernel(float* __restrict__ es, float* __restrict__ state,
+                                     const float* __restrict__ action, float* __restrict__ next_state,
+                                     float* __restrict__ reward, uint8_t* __restrict__ term,
+                                     uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
+                                     uint64_t step, uint64_t seed) {
+    const int e = blockIdx.x * TPB + threadIdx.x;
+    if (e >= E) return;
+    const long row = (long)e * T + t;
+    float st[5];
+    for (int q = 0; q < 5; ++q) st[q] = es[5 * e + q];
+    const CartPoleStep o = cartpole_advance(st, ppo::cat_index(action[2 * row], 2), (uint64_t)e, step, seed);
+    for (int q = 0; q < 4; ++q) next_state[4 * row + q] = o.next[q];
+    reward[row] = 1.f;
+    term[row] = o.term ? 1 : 0;
+    trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
+    if (cont && t == T - 1) cont[e] = (o.term || o.limit) ? 0 : 1;
+    for (int q = 0; q < 5; ++q) es[5 * e + q] = st[q];
+    if (t + 1 < T)
+        for (int q = 0; q < 4; ++q) state[4 * (row + 1) + q] = st[q];
+}
+
+// the evaluation's form: obs [E, 4] is the current observation, replaced in place; action [E, 2]
+__global__ void cartpole_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
+                                     float* __restrict__ reward, uint8_t* __restrict__ term,
+                                     uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
+                                     uint64_t step, uint64_t seed) {
+    const int e = blockIdx.x * TPB + threadIdx.x;
+    if (e >= E) return;
+    const long row = (long)e * T + t;
+    float st[5];
+    for (int q = 0; q < 5; ++q) st[q] = es[5 * e + q];
+    const CartPoleStep o = cartpole_advance(st, ppo::cat_index(action[2 * e], 2), (uint64_t)e, step, seed);
+    reward[row] = 1.f;
+    term[row] = o.term ? 1 : 0;
+    trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
+    if (t == T - 1) cont[e] = (o.term || o.limit) ? 0 : 1;
+    for (int q = 0; q < 5; ++q) es[5 * e + q] = st[q];
+    for (int q = 0; q < 4; ++q) obs[4 * e + q] = st[q];
 }
 
 // reset every env; write row e·T (t = 0) of the buffer
@@ -212,6 +303,13 @@ __global__ void env_reset_kernel(int kind, float* __restrict__ es, float* __rest
         const u32x4 r = philox((uint64_t)k, kReset - 1, seed);
         const float th = -(float)M_PI + 2.f * (float)M_PI * u01(r.x), thdot = -1.f + 2.f * u01(r.y);
         es[3 * k] = th; es[3 * k + 1] = thdot; es[3 * k + 2] = 0.f;
+        return;
+    }
+    if (kind == 2) {
+        if (k >= E) return;
+        float st[5];
+        cartpole_reset(st, (uint64_t)k, kReset - 1, seed);
+        for (int q = 0; q < 5; ++q) es[5 * k + q] = st[q];
         return;
     }
     if (k >= (long)E * S) return;
@@ -226,6 +324,7 @@ __global__ void env_obs_kernel(int kind, const float* __restrict__ es, float* __
     const int e = (int)(k / S), j = (int)(k % S);
     float v;
     if (kind == 0) v = j == 0 ? cosf(es[3 * e]) : (j == 1 ? sinf(es[3 * e]) : es[3 * e + 1]);
+    else if (kind == 2) v = es[5 * e + j];
     else v = es[k];
     state[(long)e * T * S + j] = v;
 }
@@ -248,7 +347,8 @@ void phip_rollout_rows(int* rows, int E, int T) {
 }
 
 void phip_env_reset(int kind, float* env_state, float* state, int E, int T, int S, uint64_t seed) {
-    const long n = kind == 0 ? E : (long)E * S;
+    const long n = (kind == 0 || kind == 2) ? E : (long)E * S;
+    PPO_REQUIRE(kind != 2 || S == 4, "phip_env_reset: CartPole-v1 needs S = 4");
     hipLaunchKernelGGL(env_reset_kernel, dim3(ppo_divup(n, TPB)), dim3(TPB), 0, ppo::stream(), kind, env_state, state,
                        E, T, S, seed);
     PPO_LAUNCH_CHECK();
@@ -256,6 +356,7 @@ void phip_env_reset(int kind, float* env_state, float* state, int E, int T, int 
 
 void phip_env_first_obs(int kind, const float* env_state, float* state, int E, int T, int S) {
     const long n = (long)E * S;
+    PPO_REQUIRE(kind != 2 || S == 4, "phip_env_first_obs: CartPole-v1 needs S = 4");
     hipLaunchKernelGGL(env_obs_kernel, dim3(ppo_divup(n, TPB)), dim3(TPB), 0, ppo::stream(), kind, env_state, state,
                        E, T, S);
     PPO_LAUNCH_CHECK();
@@ -271,23 +372,27 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed) {
+                   uint64_t seed, int cat) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && A == 1, "phip_env_step: Pendulum-v1 needs S = 3, A = 1");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
                            state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed);
+    } else if (kind == 2) {
+        PPO_REQUIRE(S == 4 && A == 2 && cat, "phip_env_step: CartPole-v1 needs S = 4, A = 2 and categorical actions");
+        hipLaunchKernelGGL(cartpole_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
+                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed);
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
-                           seed);
+                           seed, cat);
     }
     PPO_LAUNCH_CHECK();
 }
 
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed) {
+                        uint64_t seed, int cat) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * S + A + 2));
     PPO_REQUIRE(env_state && obs && action && reward && term && trunc && cont && E > 0 && t >= 0 && t < T,
                 "phip_env_step_eval: operands");
@@ -295,9 +400,14 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
         PPO_REQUIRE(S == 3 && A == 1, "phip_env_step_eval: Pendulum-v1 needs S = 3, A = 1");
         hipLaunchKernelGGL(pendulum_eval_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state, obs,
                            action, reward, term, trunc, cont, E, T, t, step, seed);
+    } else if (kind == 2) {
+        PPO_REQUIRE(S == 4 && A == 2 && cat,
+                    "phip_env_step_eval: CartPole-v1 needs S = 4, A = 2 and categorical actions");
+        hipLaunchKernelGGL(cartpole_eval_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state, obs,
+                           action, reward, term, trunc, cont, E, T, t, step, seed);
     } else {
         hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
-                           env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed);
+                           env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat);
     }
     PPO_LAUNCH_CHECK();
 }

@@ -121,6 +121,12 @@ typedef struct {
     int* ev_rows;
     unsigned char *ev_term, *ev_trunc, *ev_cont;
     double* ev_agg;
+    /* the action distribution (ppo_set_action_dist; 0 = diagonal Gaussian, 1 = categorical over A choices, μ's
+     * outputs the logits; csrc/categorical.hip) and the categorical head's entropy word: Σ of the row entropies
+     * of the last policy step's minibatch and that minibatch's rows (ppo_read_stats out[4]) */
+    int action_dist;
+    float* cat_ent;
+    int cat_rows;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -168,6 +174,7 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->kl = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
         d->vclip_counts = (unsigned long long*)phip_malloc(2 * sizeof(unsigned long long));
+        d->cat_ent = (float*)phip_malloc(4 * sizeof(float));
         ppo->dev = d;
     }
     if (B > d->cap_B) {
@@ -205,6 +212,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->clip[0]); phip_free(d->clip[1]);
     phip_free(d->kl);
     phip_free(d->vclip_counts);
+    phip_free(d->cat_ent);
     phip_free(d->obs_run); phip_free(d->obs_m); phip_free(d->obs_shadow); phip_free(d->obs_next);
     phip_free(d->obs_batch); phip_free(d->obs_all); phip_free(d->obs_counts);
     phip_free(d->rew_run); phip_free(d->rew_scale); phip_free(d->rew_shadow); phip_free(d->rew_batch);
@@ -298,6 +306,7 @@ static int gae_full_forwards(void) {
 /* running observation normalisation (ppo_ext.h ppo_set_obs_norm)      */
 /* ------------------------------------------------------------------ */
 static int obs_on(const PPODev* d) { return d && d->obs_clip > 0.f; }
+static int cat_on(const PPODev* d) { return d && d->action_dist == 1; }
 
 /* the running triple and its affine pair (the identity until something is folded or set) */
 static void obs_ws(PPO* ppo, PPODev* d) {
@@ -655,6 +664,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
     if (d->target_kl > 0.f) return -1;
     /* … and their value heads are plain MSE: value-loss clipping takes that loop as well */
     if (d->value_clip > 0.f) return -1;
+    /* … and their policy heads are Gaussian: a categorical policy takes that loop too */
+    if (cat_on(d)) return -1;
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -856,7 +867,22 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
                          NULL, d->rows_p);
     }
     /* μ grads + (top bucket) the log σ gradient behind them */
-    if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
+    const int cat = !tab && cat_on(d);
+    if (cat) {             /* categorical policy: the plain branch with its own head (categorical.hip) */
+        /* log σ is unused: the head writes no gradient to it, and the entropy Adam below steps on the zeros
+         * kept here, which leaves log σ bit-identical */
+        /* ppo_set_action_dist and ppo_set_compute_dtype decline the pair; nn_set_compute_dtype on μ itself does not
+         * know the PPO, so the combination is caught where it would run: the head reads fp32 logits */
+        if (mu->dtype != 0) die("ppo_update: the categorical policy needs fp32 compute mode (μ is in bf16 mode)");
+        if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
+        *ls_zero = 1;
+        phip_memset(d->cat_ent, 0, sizeof(float));
+        d->cat_rows = B;
+        nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
+        phip_cat_head(mu->d_output, act, adv, olp, B, A, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
+                      d->stats + 1, d->cat_ent);
+        nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
+    } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         nn_out_head_step(mu, 1, c->state, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
                          pol->d_log_std, act, adv, olp, ppo->epsilon, ppo->ent_coeff,
@@ -882,7 +908,8 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const int kl_on = !tab && d->target_kl > 0.f;
     const long kl_rows = (long)B * phip_comm_world();
     if (kl_on && c->comm) {
-        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, ppo->epsilon, d->target_kl, kl_rows, 0, d->kl);
+        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, cat, ppo->epsilon, d->target_kl, kl_rows, 0,
+                       d->kl);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -902,7 +929,9 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     if (kl_on) {
         if (!ap->flat || !ppo->adam_entropy->flat) die("ppo_update: target-KL early stopping needs flat Adam spans");
         if (c->comm) phip_kl_decide(d->kl, d->target_kl, kl_rows);
-        else phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, ppo->epsilon, d->target_kl, kl_rows, 1, d->kl);
+        else
+            phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, cat, ppo->epsilon, d->target_kl, kl_rows, 1,
+                           d->kl);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -947,6 +976,7 @@ static int step_graphs_ok(const StepCtx* c) {
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
     if (c->d->target_kl > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
+    if (cat_on(c->d)) return 0;                   /* … and a captured policy step's head is the Gaussian one */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
     for (int i = 0; i < 3; i++) {
@@ -1207,9 +1237,10 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const int* perms_p = phase_perms(ppo, d, shuffle_mode, n_epochs_policy, limit, 1, keys_p);
     const char* serial_env = getenv("PPO_SERIAL");
     const int concurrent = nv > 0 && np > 0 && !(serial_env && *serial_env && *serial_env != '0');
-    const int fuse_p = nn_out_head_ok(mu, 1);
+    /* the fused and the wide output-layer kernels embed the Gaussian head: a categorical policy takes neither */
+    const int fuse_p = !cat_on(d) && nn_out_head_ok(mu, 1);
     StepCtx c = {ppo, d, B, S, A, limit, num_batches, comm, nn_out_head_ok(V, 0), fuse_p,
-                 !fuse_p && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
+                 !fuse_p && !cat_on(d) && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
                  NULL, NULL, NULL, NULL, 16, 1, 1, 0, state};
     {
         const char* ge = getenv("PPO_GRAPH_STEPS");
@@ -1355,6 +1386,11 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         v[23] = (double)cnt[0];
         v[24] = (double)cnt[1];
     }
+    if (cat_on(d)) {                            /* categorical: the mean row entropy of the last policy step */
+        float h = 0.f;
+        phip_d2h(&h, d->cat_ent, sizeof(float));
+        v[4] = d->cat_rows > 0 ? (double)h / d->cat_rows : 0.0;
+    }
     for (int i = 0; i < n && i < 25; i++) out[i] = v[i];
 }
 
@@ -1478,7 +1514,7 @@ static void eval_ws(PPODev* d, int E, long N, int S, int A) {
     if (E > d->ev_E) {
         phip_free(d->ev_env); phip_free(d->ev_obs); phip_free(d->ev_obsn); phip_free(d->ev_act);
         phip_free(d->ev_lp); phip_free(d->ev_rows); phip_free(d->ev_cont);
-        d->ev_env = (float*)phip_malloc(sizeof(float) * (size_t)E * (S > 3 ? S : 3));
+        d->ev_env = (float*)phip_malloc(sizeof(float) * (size_t)E * PHIP_ENV_STATE(S));
         d->ev_obs = (float*)phip_malloc(sizeof(float) * (size_t)E * S);
         d->ev_obsn = (float*)phip_malloc(sizeof(float) * (size_t)E * S);
         d->ev_act = (float*)phip_malloc(sizeof(float) * (size_t)E * A);
@@ -1502,11 +1538,13 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
                     float gamma, double* out, int n) {
     PPO* ppo = (PPO*)vppo;
     if (!ppo || !out || n < 9 || n_envs <= 0 || horizon <= 0 || isnan(gamma)) return -1;
-    if (env_kind != 0 && env_kind != 1) return -1;
+    if (env_kind < 0 || env_kind > 2) return -1;
     const int E = n_envs, T = horizon;
     const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
     if (env_kind == 0 && (S != 3 || A != 1)) return -1;
     PPODev* d = dev_ws(ppo, 1);
+    const int cat = cat_on(d);
+    if (env_kind == 2 && (S != 4 || A != 2 || !cat)) return -1;
     eval_ws(d, E, (long)E * T, S, A);
     /* the first reset and the key of every later draw, as ppo_rollout_device derives them; the step counter is
      * local: the training rollout's position in the streams does not move */
@@ -1524,10 +1562,12 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         /* through the row list, as the rollout forwards: the same kernels over the same E rows */
         nn_forward_dev_rows(pol->mu, norm ? d->ev_obsn : d->ev_obs, d->ev_rows, NULL, E);
         const uint64_t step = (uint64_t)t;
-        if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
+        if (cat && deterministic) phip_cat_argmax(pol->mu->d_output, d->ev_act, E, A);
+        else if (cat) phip_cat_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
+        else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
-                           d->ev_cont, E, T, t, step, S, A, key);
+                           d->ev_cont, E, T, t, step, S, A, key, cat);
     }
     phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
                       d->ev_agg, NULL);
@@ -1713,7 +1753,7 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
     if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
     phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
-    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, eps, INFINITY, m, 1, rec);
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec);
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
     out2[0] = (double)sums[0] / m;
@@ -1787,6 +1827,51 @@ int ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float eps
     return 0;
 }
 
+/* ppo_ext.h: the action distribution */
+int ppo_set_action_dist(void* vppo, int dist) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || (dist != 0 && dist != 1)) return -1;
+    if (dist == 1) {
+        const int A = ppo->buffer->action_size;
+        if (A < 2 || A > PHIP_CAT_MAX_A) return -1;
+        if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;       /* bf16 compute mode */
+    }
+    dev_ws(ppo, 1)->action_dist = dist;
+    return 0;
+}
+
+int ppo_get_action_dist(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo && ppo->dev ? ((PPODev*)ppo->dev)->action_dist : 0;
+}
+
+/* the categorical head and sampler on caller-supplied device arrays (test entries: bad arguments return −1 ahead of
+ * any device call, so nothing is recorded for ppo_last_error) */
+int ppo_categorical_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                const float* d_old_lp, int m, int A, float eps, float ent_coeff, float* d_grad,
+                                float* d_lp, float* d_ent, double* loss) {
+    static float* word = NULL;
+    if (!d_logits || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || m <= 0 || A < 2 ||
+        A > PHIP_CAT_MAX_A || isnan(eps))
+        return -1;
+    if (!word) word = (float*)phip_malloc(4 * sizeof(float));
+    phip_memset(word, 0, 4 * sizeof(float));
+    phip_cat_head(d_logits, d_action, d_adv, d_old_lp, m, A, eps, ent_coeff, d_grad, d_lp, d_ent, word, NULL);
+    phip_sync();
+    float l = 0.f;
+    phip_d2h(&l, word, sizeof(float));
+    *loss = (double)l;
+    return 0;
+}
+
+int ppo_categorical_sample_device(const float* d_logits, int m, int A, unsigned long long key,
+                                  unsigned long long offset, float* d_action, float* d_log_prob) {
+    if (!d_logits || !d_action || !d_log_prob || m <= 0 || A < 2 || A > PHIP_CAT_MAX_A) return -1;
+    phip_cat_sample(d_logits, NULL, d_action, d_log_prob, m, A, key, offset);
+    phip_sync();
+    return 0;
+}
+
 /* ppo_ext.h: global gradient-norm clipping */
 int ppo_set_max_grad_norm(void* vppo, float max_norm) {
     if (isnan(max_norm)) return -1;
@@ -1816,6 +1901,9 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
 void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, int n_epochs_policy,
                      int n_epochs_value) {
     /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
+    if (cat_on((PPODev*)ppo->dev))
+        die("train_ppo_epoch: the categorical policy (ppo_set_action_dist) is not supported by the host rollout; "
+            "use ppo_rollout_device + ppo_update");
     if (obs_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout; "
             "use ppo_rollout_device + ppo_update");
@@ -1834,6 +1922,9 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
+    if (cat_on((PPODev*)ppo->dev))
+        die("eval_ppo: the categorical policy (ppo_set_action_dist) is not supported by the host rollout; use "
+            "ppo_eval_device");
     if (obs_on((PPODev*)ppo->dev))
         die("eval_ppo: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout");
     reset_buffer(ppo->buffer);
@@ -1872,10 +1963,15 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     const int E = n_envs, T = horizon;
     const long N = (long)E * T;
     if (E <= 0 || T <= 0 || N > b->capacity) die("ppo_rollout_device: n_envs*horizon must be in [1, capacity]");
-    if (env_kind != 0 && env_kind != 1) die("ppo_rollout_device: env_kind must be 0 (Pendulum-v1) or 1 (synthetic)");
+    if (env_kind < 0 || env_kind > 2)
+        die("ppo_rollout_device: env_kind must be 0 (Pendulum-v1), 1 (synthetic) or 2 (CartPole-v1)");
     const int S = b->state_size, A = b->action_size;
     if (env_kind == 0 && (S != 3 || A != 1)) die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1");
     PPODev* d = dev_ws(ppo, 1);
+    const int cat = cat_on(d);
+    if (env_kind == 2 && (S != 4 || A != 2 || !cat))
+        die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
+            "(ppo_set_action_dist)");
     if (d->ro_E != E || d->ro_T != T) {
         phip_free(d->ro_rows);
         d->ro_rows = (int*)phip_malloc(sizeof(int) * (size_t)N);
@@ -1884,7 +1980,7 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     }
     if (d->ro_E != E || d->ro_kind != env_kind || d->ro_S != S || !d->env_state) {
         phip_free(d->env_state);
-        d->env_state = (float*)phip_malloc(sizeof(float) * (size_t)E * (S > 3 ? S : 3));
+        d->env_state = (float*)phip_malloc(sizeof(float) * (size_t)E * PHIP_ENV_STATE(S));
         phip_env_reset(env_kind, d->env_state, b->d_state_p, E, T, S, splitmix64(seed));
         /* fresh episodes: nothing continues, nothing is carried (phip_malloc zeroes) */
         phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
@@ -1927,9 +2023,11 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         /* one position in the Philox streams per step of every call: the policy noise and the environment's
          * draws never repeat under a constant seed */
         const uint64_t step = d->ro_step++;
-        phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
+        if (cat) phip_cat_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
+        else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
-                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key);
+                      (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
+                      cat);
     }
     /* episode statistics: one scan of the rows just laid (two launches, no host read) — the batch becomes the
      * last rollout's aggregate and is folded into the window */
@@ -1965,7 +2063,12 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
         obs = obs_shadow(ppo, d);
         phip_obs_normalize(b->d_state_p, obs, N, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run, NULL);
     }
-    ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
+    if (cat_on((PPODev*)ppo->dev)) {     /* categorical: one uniform per row from the "action noise" key */
+        nn_forward_dev(ppo->policy->mu, obs, (int)N);
+        phip_cat_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, s0 ^ 0x5, 0);
+    } else {
+        ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
+    }
     phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
     phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
     b->idx = (int)(N % b->capacity);
@@ -1973,7 +2076,6 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     buffer_point_device(b);
     /* not laid by a device rollout: scanned as one stream, and the next rollout starts from a zero carry */
     if (ppo->dev) ((PPODev*)ppo->dev)->ro_laid = ((PPODev*)ppo->dev)->rew_scanned = 0;
-    (void)A;
 }
 
 /* ------------------------------------------------------------------ */
@@ -2033,6 +2135,8 @@ int ppo_set_compute_dtype(void* vppo, int dtype) {
     if (!ppo) return -1;
     /* bf16 mode knows ReLU and identity: a tanh layer in either network declines it, both left as they were */
     if (dtype == 1 && (nn_has_tanh(ppo->V) || nn_has_tanh(ppo->policy->mu))) return -1;
+    /* … and the categorical head reads fp32 logits: bf16 mode is declined while it is on */
+    if (dtype == 1 && cat_on((PPODev*)ppo->dev)) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;
     return nn_set_compute_dtype(ppo->policy->mu, dtype);
 }

@@ -156,6 +156,11 @@ _SIGS = {
     "ppo_kl_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "ppo_policy_kl_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double)]),
     "ppo_policy_head_device": (C.c_int, [C.c_int] * 5 + [C.c_float] * 2 + [_P] * 13 + [C.POINTER(C.c_double)]),
+    "ppo_set_action_dist": (C.c_int, [_P, C.c_int]),
+    "ppo_get_action_dist": (C.c_int, [_P]),
+    "ppo_categorical_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
+                                              C.POINTER(C.c_double)]),
+    "ppo_categorical_sample_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _P, _P]),
     "ppo_set_value_clip": (C.c_int, [_P, C.c_float]),
     "ppo_get_value_clip": (C.c_float, [_P]),
     "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
