@@ -257,7 +257,9 @@ int    ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float 
  * of collectives does not depend on the setting.  The head writes no gradient to log σ; the entropy Adam still runs
  * each step, on a zero gradient, which leaves log σ bit-identical.
  * The reference-API entry points that have only a policy or only host data stay Gaussian: sample_action,
- * compute_log_prob*, ppo_sample_action_device, policy_loss_and_grad*, and ppo_policy_kl_device.  The host rollout
+ * compute_log_prob*, ppo_sample_action_device, policy_loss_and_grad*, and ppo_policy_kl_device — to act on
+ * caller-supplied observations under the PPO's distribution (and its observation normaliser) use ppo_act_device, and
+ * to train against a caller-stepped environment the open rollout (ppo_rollout_begin … _end).  The host rollout
  * has no discrete form: train_ppo_epoch / eval_ppo END THE PROCESS with a message while it is on.
  * The setting lives with the PPO, not in GaussianPolicy (whose layout is the reference's).  Not part of a
  * checkpoint: set it again after load_ppo.
@@ -370,7 +372,8 @@ int    ppo_obs_stats_device(const float* d_x, long n, int S, double* out);
  * carry_in is zeroed; an environment reset (a change of n_envs or env_kind) zeroes it.  Repeated updates over
  * one rollout read the same carry_in: idempotent apart from the fold.  ppo_fill_synthetic, train_ppo_epoch and
  * a limit that is not E·T mean "not rollout-laid": one stream, no carry.  (A buffer the caller refills through
- * the device pointers after a rollout keeps the rollout's layout and carry.)  Carries are per rank, not hashed.
+ * the device pointers after a rollout keeps the rollout's layout and carry; the open rollout, ppo_rollout_begin …
+ * _end below, is the supported way to lay a caller-stepped environment with all of it.)  Carries are per rank, not hashed.
  * Under data parallelism each rank's 3-double batch triple (the zero triple for an empty shard) is all-gathered
  * at one fixed point ahead of GAE's forwards — every rank reaches it, empty shard or not — combined in rank
  * order and folded, so every rank holds bit-identical state: EVERY RANK MUST HOLD THE SAME on/off AND frozen
@@ -510,6 +513,90 @@ void ppo_fill_synthetic(void* ppo, int n_envs, int horizon, unsigned long long s
  * step of every call (a counter that starts at 0 with the PPO), so passing the same seed to every
  * call is the intended use and a fresh PPO with that seed reproduces the same rollouts. */
 void ppo_rollout_device(void* ppo, int n_envs, int horizon, int env_kind, unsigned long long seed);
+
+/* THE OPEN ROLLOUT: ppo_rollout_device with the environment step handed to the caller (DESIGN.md §4 "External
+ * environments").  The caller owns a vectorised simulator on the device; libppo owns everything else — the row map,
+ * observation normalisation, μ's forward, the sampler and its Philox position, the segment-end truncation, cont[],
+ * the return carry, the episode tracker — with the same launches and the same streams as ppo_rollout_device.
+ *     ppo_rollout_begin(ppo, E, T, d_obs0 | NULL, seed)
+ *     T × { step = ppo_rollout_act(ppo, d_action);   the caller steps its E environments under d_action;
+ *           ppo_rollout_store(ppo, d_reward, d_next_obs, d_term, d_trunc, d_obs_after | NULL) }
+ *     ppo_rollout_end(ppo);   ppo_update(…)
+ * Arrays are dense and device-resident: d_obs0, d_next_obs, d_obs_after [E, S] floats, d_action [E, A] floats,
+ * d_reward [E] floats, d_term, d_trunc [E] bytes.  Everything is stream-ordered on libppo's stream and nothing is
+ * read back: a simulator on another stream synchronises with libppo's itself (ppo_synchronize, or keep its work on
+ * the null stream).  All four return −1 — nothing launched, nothing recorded for ppo_last_error, the state of the
+ * rollout unchanged — for a NULL ppo or array (d_obs0 and d_obs_after excepted) or a call out of sequence; none
+ * ends the process.
+ * begin: 1 <= E·T <= capacity.  d_obs0 != NULL: FRESH EPISODES from these observations, as ppo_rollout_device on a
+ * change of n_envs or env_kind — cont[], both return carries and the tracker's per-environment state are
+ * reallocated fresh, the statistics window stays; the environment kind becomes "external", so going from a
+ * built-in environment to an external one or back is a change of environment in both directions.  d_obs0 == NULL:
+ * the environments CONTINUE from the d_obs_after of the last stored step — legal only after an external rollout of
+ * the same E and state size that reached its end (T may differ), else −1.  The return-carry swap happens here, as
+ * at the start of ppo_rollout_device.  The current observations go to rows e·T of `state`.  `seed` keys the policy
+ * noise exactly as ppo_rollout_device's does (splitmix64(seed ^ 0x524F4C4C)) for every act of this rollout.  begin
+ * leaves the buffer's limit (idx / full) and its rollout-laid mark alone: A ppo_update ISSUED WHILE A ROLLOUT IS OPEN
+ * sees the previous limit over partly new rows — the caller's error.  A begin while one is open abandons it (with
+ * d_obs0; with NULL it is out of sequence); ppo_rollout_device, ppo_fill_synthetic and train_ppo_epoch called while
+ * one is open simply close it, and nothing can continue from it.
+ * act (after begin or store): step t's E rows e·T + t are normalised into the shadow while observation
+ * normalisation is on, μ is forwarded over them and the Gaussian or categorical row sampler writes action and
+ * log-prob into the buffer rows at the rollout step counter's next position — the counter ppo_rollout_device
+ * advances, so internal and external rollouts of one PPO never reuse a position; one more launch copies the E
+ * action rows out to d_action.  Returns that position (>= 0), so that the caller can address the same position in
+ * streams of its own (ppo_env_step_device takes it).
+ * store (once after each act), for row = e·T + t:
+ *     next_state[row] = d_next_obs[e]          the transition's own next observation: the terminal one where the
+ *                                              episode ended
+ *     reward[row]     = d_reward[e]
+ *     terminated[row] = d_term[e] != 0
+ *     truncated[row]  = d_trunc[e] != 0 || (t == T−1 && !terminated[row])
+ *     t == T−1:  cont[e] = !(d_term[e] || d_trunc[e])     the environment's own flags alone decide it
+ *     t + 1 < T: state[row + 1] = d_obs_after[e]          what the next step starts from: the reset observation
+ *     always:    the PPO's current observations [E, S] ← d_obs_after[e]     where the episode ended
+ * d_obs_after == NULL means d_next_obs: an environment that never resets, or that resets on its next step.  (A
+ * terminated row at a segment end gets truncated = 0 here; CartPole's built-in kernel writes 1.  Nothing downstream
+ * tells the two apart: GAE and both scans read terminated || truncated, and terminated alone masks the bootstrap.)
+ * end: legal only after the T-th store (else −1, the rollout stays open).  The tail of ppo_rollout_device: the
+ * episode scan with cont[], the advantages zeroed, idx / full, the buffer pointed at the device, rollout-laid.
+ * Composes with every option of ppo_update (both normalisers, the categorical policy, clipping, target KL, tanh
+ * networks, data parallelism: per rank, no collective added).  The open rollout's own state (step t, the current
+ * observations) is not part of a checkpoint. */
+int       ppo_rollout_begin(void* ppo, int n_envs, int horizon, const float* d_obs0, unsigned long long seed);
+long long ppo_rollout_act(void* ppo, float* d_action);
+int       ppo_rollout_store(void* ppo, const float* d_reward, const float* d_next_obs, const unsigned char* d_term,
+                            const unsigned char* d_trunc, const float* d_obs_after);
+int       ppo_rollout_end(void* ppo);
+/* A STATELESS ACT, for evaluation and serving against a caller's environment (what ppo_eval_device does for the
+ * built-ins): d_obs [m, S] raw → d_action [m, A] (and d_log_prob [m]).  Observations are normalised under the pair
+ * as it stands, as if frozen — nothing folded, the clamp counters untouched — into a scratch kept with the PPO; μ is
+ * forwarded.  deterministic != 0: the action is μ's output bit for bit — categorical: the lowest argmax index in
+ * column 0, zeros after; d_log_prob is not written and may be NULL.  Otherwise row i draws exactly what the rollout's
+ * sampler draws for environment i at position `step` under `seed`: on the same observations ppo_rollout_act (begun
+ * with that seed, returning that step) and ppo_act_device agree bit for bit; d_log_prob may be NULL.  Leaves
+ * bit-identical everything ppo_eval_device leaves so (the rollout's step counter and an open rollout included):
+ * only μ's forward workspaces change.  Stream-ordered, no host read.  Returns 0, or −1 — nothing launched — for a
+ * NULL ppo, d_obs or d_action or m <= 0. */
+int ppo_act_device(void* ppo, const float* d_obs, int m, int deterministic, unsigned long long seed,
+                   unsigned long long step, float* d_action, float* d_log_prob);
+/* THE BUILT-IN ENVIRONMENTS ON DENSE ARRAYS: ppo_rollout_device's three environments as a caller-stepped simulator
+ * — a third form of each step kernel through the same device functions as the training and the evaluation forms, so
+ * the three cannot drift.  Driven through the open rollout with the seed begin took and the step act returned, they
+ * reproduce ppo_rollout_device bit for bit.  d_env_state holds E · ppo_env_state_floats(env_kind, S) floats (−1 for
+ * an unknown kind or an S the kind does not take).  reset: every environment from splitmix64(seed) at the reset
+ * stream's first offset, as ppo_rollout_device's first call; d_obs [E, S] ← the first observations.  step: d_action
+ * [E, A] in (categorical != 0: column 0 holds an index); d_next_obs [E, S] ← the transition's next observation,
+ * d_obs_after [E, S] ← what the next step starts from, d_reward [E], d_term [E] as the training kernels write it,
+ * d_trunc [E] ← the environment's own TimeLimit alone (Pendulum 200 steps, CartPole 500, synthetic never): the
+ * segment end belongs to ppo_rollout_store.  The key is splitmix64(seed ^ 0x524F4C4C), `step` the position in the
+ * environment and reset streams.  Stream-ordered, no host read.  Both return 0, or −1 — nothing launched — for a NULL
+ * array, E <= 0 or a shape the kind does not take (Pendulum S = 3, A = 1; CartPole S = 4, A = 2, categorical). */
+int ppo_env_state_floats(int env_kind, int S);
+int ppo_env_reset_device(int env_kind, float* d_env_state, float* d_obs, int E, int S, unsigned long long seed);
+int ppo_env_step_device(int env_kind, float* d_env_state, const float* d_action, float* d_next_obs, float* d_obs_after,
+                        float* d_reward, unsigned char* d_term, unsigned char* d_trunc, int E, int S, int A,
+                        int categorical, unsigned long long seed, unsigned long long step);
 
 /* layer 0's input of the last device forward of a NeuralNetwork*, m rows × input_size fp32, to the
  * host: the gathered minibatch rows the GEMMs read (NeuralNetwork.d_x0) — for parity tests;

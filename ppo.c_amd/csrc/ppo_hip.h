@@ -157,6 +157,20 @@ void phip_env_step(int kind, float* env_state, float* state, const float* action
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
                         uint64_t seed, int cat);
+/* the dense step (ppo_env_step_device): the same dynamics again over [E, ·] arrays the caller owns — action in;
+ * the transition's next observation, the observation the next step starts from (the reset one where the episode
+ * ended), reward, terminated and the environment's own TimeLimit out.  No segment end, no cont */
+void phip_env_step_dense(int kind, float* env_state, const float* action, float* next_obs, float* obs_after,
+                         float* reward, uint8_t* term, uint8_t* trunc, int E, uint64_t step, int S, int A,
+                         uint64_t seed, int cat);
+/* the open rollout (ppo_rollout_begin … _end): ro_kind of a rollout whose environment the caller steps */
+#define PHIP_ENV_EXTERNAL 3
+void phip_action_rows_out(const float* action, const int* rows, float* dense, int E, int A);  /* dense[e] = action[rows[e]] */
+/* one external step into buffer row e·T + t by the store rule of ppo_ext.h; obs_after may be NULL (= next_obs);
+ * cur [E, S] ← the observation the next step starts from; cont [E] written at t = T − 1 */
+void phip_ext_store(const float* next_obs, const float* obs_after, const float* reward_in, const uint8_t* term_in,
+                    const uint8_t* trunc_in, float* state, float* next_state, float* reward, uint8_t* term,
+                    uint8_t* trunc, uint8_t* cont, float* cur, int E, int T, int t, int S);
 
 /* ---------------- episode statistics (episode.hip) ---------------- */
 /* The scan of ppo_ext.h ppo_episode_scan_device plus its fold, two launches: E segments of T rows, cont (may be

@@ -336,6 +336,103 @@ __global__ void rows_kernel(int* __restrict__ rows, int E, int T) {
     rows[k] = e * T + t;
 }
 
+// The dense forms (ppo_ext.h ppo_env_step_device): the same advance functions over caller-owned arrays — action
+// [E, A] in, the transition's next observation, the observation the next step starts from, reward and the
+// environment's own flags out, each [E, ·].  trunc is the TimeLimit alone: a segment end belongs to the store.
+__global__ void pendulum_dense_kernel(float* __restrict__ es, const float* __restrict__ action,
+                                      float* __restrict__ next_obs, float* __restrict__ obs_after,
+                                      float* __restrict__ reward, uint8_t* __restrict__ term,
+                                      uint8_t* __restrict__ trunc, int E, uint64_t step, uint64_t seed) {
+    const int e = blockIdx.x * TPB + threadIdx.x;
+    if (e >= E) return;
+    float th = es[3 * e], thdot = es[3 * e + 1];
+    float steps = es[3 * e + 2];
+    const PendulumStep o = pendulum_advance(th, thdot, steps, action[e], (uint64_t)e, step, seed);
+    next_obs[3 * e] = o.next[0];
+    next_obs[3 * e + 1] = o.next[1];
+    next_obs[3 * e + 2] = o.next[2];
+    reward[e] = o.reward;
+    term[e] = 0;
+    trunc[e] = o.limit ? 1 : 0;
+    es[3 * e] = th;
+    es[3 * e + 1] = thdot;
+    es[3 * e + 2] = steps;
+    obs_after[3 * e] = cosf(th);
+    obs_after[3 * e + 1] = sinf(th);
+    obs_after[3 * e + 2] = thdot;
+}
+
+__global__ void synth_dense_kernel(float* __restrict__ es, const float* __restrict__ action,
+                                   float* __restrict__ next_obs, float* __restrict__ obs_after,
+                                   float* __restrict__ reward, uint8_t* __restrict__ term,
+                                   uint8_t* __restrict__ trunc, int E, uint64_t step, int S, int A, uint64_t seed,
+                                   int cat) {
+    const long k = (long)blockIdx.x * TPB + threadIdx.x;
+    if (k >= (long)E * S) return;
+    const int e = (int)(k / S), j = (int)(k % S);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat);
+    next_obs[k] = s.o2;
+    if (j == 0) {
+        reward[e] = s.reward;
+        term[e] = s.done ? 1 : 0;
+        trunc[e] = 0;
+    }
+    es[k] = s.nxt;
+    obs_after[k] = s.nxt;
+}
+
+__global__ void cartpole_dense_kernel(float* __restrict__ es, const float* __restrict__ action,
+                                      float* __restrict__ next_obs, float* __restrict__ obs_after,
+                                      float* __restrict__ reward, uint8_t* __restrict__ term,
+                                      uint8_t* __restrict__ trunc, int E, uint64_t step, uint64_t seed) {
+    const int e = blockIdx.x * TPB + threadIdx.x;
+    if (e >= E) return;
+    float st[5];
+    for (int q = 0; q < 5; ++q) st[q] = es[5 * e + q];
+    const CartPoleStep o = cartpole_advance(st, ppo::cat_index(action[2 * e], 2), (uint64_t)e, step, seed);
+    for (int q = 0; q < 4; ++q) next_obs[4 * e + q] = o.next[q];
+    reward[e] = 1.f;
+    term[e] = o.term ? 1 : 0;
+    trunc[e] = o.limit ? 1 : 0;
+    for (int q = 0; q < 5; ++q) es[5 * e + q] = st[q];
+    for (int q = 0; q < 4; ++q) obs_after[4 * e + q] = st[q];
+}
+
+// The open rollout (ppo_ext.h ppo_rollout_act / ppo_rollout_store).  One thread per (e, j), j along the row.
+// dense[e, :] = action[rows[e], :]
+__global__ void action_rows_out_kernel(const float* __restrict__ action, const int* __restrict__ rows,
+                                       float* __restrict__ dense, int E, int A) {
+    const long k = (long)blockIdx.x * TPB + threadIdx.x;
+    if (k >= (long)E * A) return;
+    const int e = (int)(k / A), j = (int)(k % A);
+    dense[k] = action[(long)rows[e] * A + j];
+}
+
+// One external step into row e·T + t: the store rule of ppo_ext.h.  obs_after (NULL: next_obs) is what the next
+// step starts from: it goes to state[row + 1] and to cur, the PPO's current observations.  The flags, the reward
+// and cont[e] are thread j == 0's; no thread reads what another writes.  next_obs and obs_after may be one array.
+__global__ void ext_store_kernel(const float* next_obs, const float* obs_after, const float* __restrict__ reward_in,
+                                 const uint8_t* __restrict__ term_in, const uint8_t* __restrict__ trunc_in,
+                                 float* __restrict__ state, float* __restrict__ next_state,
+                                 float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
+                                 uint8_t* __restrict__ cont, float* __restrict__ cur, int E, int T, int t, int S) {
+    const long k = (long)blockIdx.x * TPB + threadIdx.x;
+    if (k >= (long)E * S) return;
+    const int e = (int)(k / S), j = (int)(k % S);
+    const long row = (long)e * T + t;
+    next_state[row * S + j] = next_obs[k];
+    const float after = obs_after ? obs_after[k] : next_obs[k];
+    if (t + 1 < T) state[(row + 1) * S + j] = after;
+    cur[k] = after;
+    if (j == 0) {
+        const bool tm = term_in[e] != 0, tr = trunc_in[e] != 0;
+        reward[row] = reward_in[e];
+        term[row] = tm ? 1 : 0;
+        trunc[row] = (tr || (t == T - 1 && !tm)) ? 1 : 0;
+        if (t == T - 1) cont[e] = (tm || tr) ? 0 : 1;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -409,6 +506,47 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
         hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat);
     }
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_env_step_dense(int kind, float* env_state, const float* action, float* next_obs, float* obs_after,
+                         float* reward, uint8_t* term, uint8_t* trunc, int E, uint64_t step, int S, int A,
+                         uint64_t seed, int cat) {
+    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
+    PPO_REQUIRE(env_state && action && next_obs && obs_after && reward && term && trunc && E > 0,
+                "phip_env_step_dense: operands");
+    if (kind == 0) {
+        PPO_REQUIRE(S == 3 && A == 1, "phip_env_step_dense: Pendulum-v1 needs S = 3, A = 1");
+        hipLaunchKernelGGL(pendulum_dense_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
+                           action, next_obs, obs_after, reward, term, trunc, E, step, seed);
+    } else if (kind == 2) {
+        PPO_REQUIRE(S == 4 && A == 2 && cat,
+                    "phip_env_step_dense: CartPole-v1 needs S = 4, A = 2 and categorical actions");
+        hipLaunchKernelGGL(cartpole_dense_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
+                           action, next_obs, obs_after, reward, term, trunc, E, step, seed);
+    } else {
+        hipLaunchKernelGGL(synth_dense_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
+                           env_state, action, next_obs, obs_after, reward, term, trunc, E, step, S, A, seed, cat);
+    }
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_action_rows_out(const float* action, const int* rows, float* dense, int E, int A) {
+    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * A + 1));
+    hipLaunchKernelGGL(action_rows_out_kernel, dim3(ppo_divup((long)E * A, TPB)), dim3(TPB), 0, ppo::stream(), action,
+                       rows, dense, E, A);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_ext_store(const float* next_obs, const float* obs_after, const float* reward_in, const uint8_t* term_in,
+                    const uint8_t* trunc_in, float* state, float* next_state, float* reward, uint8_t* term,
+                    uint8_t* trunc, uint8_t* cont, float* cur, int E, int T, int t, int S) {
+    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (4 * S + 3));
+    PPO_REQUIRE(next_obs && reward_in && term_in && trunc_in && cont && cur && E > 0 && t >= 0 && t < T,
+                "phip_ext_store: operands");
+    hipLaunchKernelGGL(ext_store_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(), next_obs,
+                       obs_after, reward_in, term_in, trunc_in, state, next_state, reward, term, trunc, cont, cur, E,
+                       T, t, S);
     PPO_LAUNCH_CHECK();
 }
 

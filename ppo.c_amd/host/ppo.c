@@ -127,6 +127,18 @@ typedef struct {
     int action_dist;
     float* cat_ent;
     int cat_rows;
+    /* the open rollout (ppo_rollout_begin / _act / _store / _end; ro_kind == PHIP_ENV_EXTERNAL): ext_open while
+     * one is open, ext_t the step the next act takes, ext_acted between an act and its store, ext_done once a
+     * rollout has ended and ext_obs [ro_E, ro_S] — the observations the next step starts from, as the stores left
+     * them — may continue into begin(NULL); ext_key the policy-noise key of begin's seed */
+    int ext_open, ext_t, ext_acted, ext_done;
+    uint64_t ext_key;
+    float* ext_obs;
+    long ext_obs_cap;
+    /* ppo_act_device's scratch for act_m rows: the normalised observations, the identity row list, log-probs */
+    int act_m;
+    float *act_obsn, *act_lp;
+    int* act_rows;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -222,6 +234,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ev_env); phip_free(d->ev_obs); phip_free(d->ev_obsn); phip_free(d->ev_act); phip_free(d->ev_lp);
     phip_free(d->ev_reward); phip_free(d->ev_rows); phip_free(d->ev_term); phip_free(d->ev_trunc);
     phip_free(d->ev_cont); phip_free(d->ev_agg);
+    phip_free(d->ext_obs); phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -1910,6 +1923,7 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
     /* the host rollout resets the environment at each call: its buffer is scanned with no carry (reward
      * normalisation), and a device rollout after it starts from a zero carry */
     if (ppo->dev) ((PPODev*)ppo->dev)->ro_laid = ((PPODev*)ppo->dev)->rew_scanned = 0;
+    if (ppo->dev && ((PPODev*)ppo->dev)->ext_open) ((PPODev*)ppo->dev)->ext_open = ((PPODev*)ppo->dev)->ext_done = 0;
     for (int i = 0; i < steps_per_epoch / ppo->buffer->capacity; i++) {
         collect_trajectories(ppo->buffer, env, ppo->policy, ppo->buffer->capacity);
         buffer_to_device(ppo->buffer);
@@ -1957,6 +1971,65 @@ void ppo_sample_action_device(void* vpolicy, float* d_state, float* d_action, fl
     phip_sample(p->mu->d_output, p->d_log_std, d_action, d_log_prob, m, p->action_size, seed, offset);
 }
 
+/* The pieces ppo_rollout_device and the open rollout (ppo_rollout_begin … _end) share, so that the two cannot
+ * drift.  The row map rows[t·E + e] = e·T + t for E × T (called before ro_E changes): */
+static void ro_rows_ws(PPODev* d, int E, int T) {
+    if (d->ro_E == E && d->ro_T == T && d->ro_rows) return;
+    phip_free(d->ro_rows);
+    d->ro_rows = (int*)phip_malloc(sizeof(int) * (size_t)E * (size_t)T);
+    phip_rollout_rows(d->ro_rows, E, T);
+    d->ro_T = T;
+}
+
+/* fresh episodes in E environments of `kind`: nothing continues, nothing is carried (phip_malloc zeroes) */
+static void ro_fresh(PPODev* d, int E, int kind, int S) {
+    phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
+    d->ro_cont = (unsigned char*)phip_malloc((size_t)E);
+    d->rew_carry_in = (double*)phip_malloc(sizeof(double) * (size_t)E);
+    d->rew_carry_out = (double*)phip_malloc(sizeof(double) * (size_t)E);
+    d->rew_scanned = 0;
+    /* episode statistics: the episodes in progress are dropped with the environments, the window stays */
+    phip_free(d->ep_state);
+    d->ep_state = (double*)phip_malloc(4 * sizeof(double) * (size_t)E);
+    d->ep_fresh = 1;
+    d->ro_E = E;
+    d->ro_kind = kind;
+    d->ro_S = S;
+}
+
+/* the returns' carry (reward normalisation; kept with the feature off too, so that it may be turned on
+ * between a rollout and its update): what an update's scan of the rollout just before this one left
+ * becomes this one's carry_in; with no such scan every return restarts from 0 */
+static void ro_carry_swap(PPODev* d, int E) {
+    if (d->rew_scanned) {
+        double* t = d->rew_carry_in;
+        d->rew_carry_in = d->rew_carry_out;
+        d->rew_carry_out = t;
+    } else {
+        phip_memset(d->rew_carry_in, 0, sizeof(double) * (size_t)E);
+    }
+    d->rew_scanned = 0;
+}
+
+/* behind the last step of a rollout of E × T rows: the buffer becomes rollout-laid and ready for ppo_update */
+static void ro_finish(PPO* ppo, PPODev* d, int E, int T) {
+    TrajectoryBuffer* b = ppo->buffer;
+    const long N = (long)E * T;
+    /* episode statistics: one scan of the rows just laid (two launches, no host read) — the batch becomes the
+     * last rollout's aggregate and is folded into the window */
+    if (!d->ep_agg) d->ep_agg = (double*)phip_malloc(16 * sizeof(double));
+    phip_episode_scan(b->d_reward_p, (const uint8_t*)b->d_terminated_p, (const uint8_t*)b->d_truncated_p, d->ro_cont,
+                      E, T, d->ep_gamma, d->ep_fresh ? NULL : d->ep_state, d->ep_state, NULL, NULL, d->ep_agg + 8,
+                      d->ep_agg);
+    d->ep_fresh = 0;
+    phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
+    phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
+    b->idx = (int)(N % b->capacity);
+    b->full = N == b->capacity;
+    buffer_point_device(b);
+    d->ro_laid = 1;
+}
+
 void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned long long seed) {
     PPO* ppo = (PPO*)vppo;
     TrajectoryBuffer* b = ppo->buffer;
@@ -1972,42 +2045,15 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     if (env_kind == 2 && (S != 4 || A != 2 || !cat))
         die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
             "(ppo_set_action_dist)");
-    if (d->ro_E != E || d->ro_T != T) {
-        phip_free(d->ro_rows);
-        d->ro_rows = (int*)phip_malloc(sizeof(int) * (size_t)N);
-        phip_rollout_rows(d->ro_rows, E, T);
-        d->ro_T = T;
-    }
+    d->ext_open = d->ext_done = 0;                               /* an open rollout is simply closed */
+    ro_rows_ws(d, E, T);
     if (d->ro_E != E || d->ro_kind != env_kind || d->ro_S != S || !d->env_state) {
         phip_free(d->env_state);
         d->env_state = (float*)phip_malloc(sizeof(float) * (size_t)E * PHIP_ENV_STATE(S));
         phip_env_reset(env_kind, d->env_state, b->d_state_p, E, T, S, splitmix64(seed));
-        /* fresh episodes: nothing continues, nothing is carried (phip_malloc zeroes) */
-        phip_free(d->ro_cont); phip_free(d->rew_carry_in); phip_free(d->rew_carry_out);
-        d->ro_cont = (unsigned char*)phip_malloc((size_t)E);
-        d->rew_carry_in = (double*)phip_malloc(sizeof(double) * (size_t)E);
-        d->rew_carry_out = (double*)phip_malloc(sizeof(double) * (size_t)E);
-        d->rew_scanned = 0;
-        /* episode statistics: the episodes in progress are dropped with the environments, the window stays */
-        phip_free(d->ep_state);
-        d->ep_state = (double*)phip_malloc(4 * sizeof(double) * (size_t)E);
-        d->ep_fresh = 1;
-        d->ro_E = E;
-        d->ro_kind = env_kind;
-        d->ro_S = S;
+        ro_fresh(d, E, env_kind, S);
     }
-    /* the returns' carry (reward normalisation; kept with the feature off too, so that it may be turned on
-     * between a rollout and its update): what an update's scan of the rollout just before this one left
-     * becomes this one's carry_in; with no such scan every return restarts from 0 */
-    if (d->rew_scanned) {
-        double* t = d->rew_carry_in;
-        d->rew_carry_in = d->rew_carry_out;
-        d->rew_carry_out = t;
-    } else {
-        phip_memset(d->rew_carry_in, 0, sizeof(double) * (size_t)E);
-    }
-    d->rew_scanned = 0;
-    d->ro_laid = 1;
+    ro_carry_swap(d, E);
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     GaussianPolicy* pol = ppo->policy;
     phip_env_first_obs(env_kind, d->env_state, b->d_state_p, E, T, S);
@@ -2029,18 +2075,7 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
                       cat);
     }
-    /* episode statistics: one scan of the rows just laid (two launches, no host read) — the batch becomes the
-     * last rollout's aggregate and is folded into the window */
-    if (!d->ep_agg) d->ep_agg = (double*)phip_malloc(16 * sizeof(double));
-    phip_episode_scan(b->d_reward_p, (const uint8_t*)b->d_terminated_p, (const uint8_t*)b->d_truncated_p, d->ro_cont,
-                      E, T, d->ep_gamma, d->ep_fresh ? NULL : d->ep_state, d->ep_state, NULL, NULL, d->ep_agg + 8,
-                      d->ep_agg);
-    d->ep_fresh = 0;
-    phip_memset(b->d_advantage_p, 0, sizeof(float) * (size_t)N);
-    phip_memset(b->d_adv_target_p, 0, sizeof(float) * (size_t)N);
-    b->idx = (int)(N % b->capacity);
-    b->full = N == b->capacity;
-    buffer_point_device(b);
+    ro_finish(ppo, d, E, T);
 }
 
 void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long seed, float p_terminate) {
@@ -2076,6 +2111,151 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     buffer_point_device(b);
     /* not laid by a device rollout: scanned as one stream, and the next rollout starts from a zero carry */
     if (ppo->dev) ((PPODev*)ppo->dev)->ro_laid = ((PPODev*)ppo->dev)->rew_scanned = 0;
+    /* an open rollout is simply closed: its rows are gone, so nothing continues from it */
+    if (ppo->dev && ((PPODev*)ppo->dev)->ext_open) ((PPODev*)ppo->dev)->ext_open = ((PPODev*)ppo->dev)->ext_done = 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* the open rollout: the caller steps the environment (ppo_ext.h)      */
+/* ------------------------------------------------------------------ */
+int ppo_rollout_begin(void* vppo, int n_envs, int horizon, const float* d_obs0, unsigned long long seed) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || n_envs <= 0 || horizon <= 0) return -1;
+    TrajectoryBuffer* b = ppo->buffer;
+    const int E = n_envs, T = horizon, S = b->state_size;
+    if ((long)E * T > b->capacity) return -1;
+    PPODev* d = dev_ws(ppo, 1);
+    if (!d_obs0 && !(d->ext_done && !d->ext_open && d->ro_kind == PHIP_ENV_EXTERNAL && d->ro_E == E && d->ro_S == S))
+        return -1;
+    ro_rows_ws(d, E, T);
+    if (d_obs0) {
+        if ((long)E * S > d->ext_obs_cap) {
+            phip_free(d->ext_obs);
+            d->ext_obs = (float*)phip_malloc(sizeof(float) * (size_t)E * S);
+            d->ext_obs_cap = (long)E * S;
+        }
+        phip_d2d(d->ext_obs, d_obs0, sizeof(float) * (size_t)E * S);
+        ro_fresh(d, E, PHIP_ENV_EXTERNAL, S);
+    }
+    ro_carry_swap(d, E);
+    /* rows e·T ← the current observations: the synthetic environment's state is its observation, [E, S] */
+    phip_env_first_obs(1, d->ext_obs, b->d_state_p, E, T, S);
+    d->ext_key = splitmix64(seed ^ 0x524F4C4CULL);
+    d->ext_open = 1;
+    d->ext_done = d->ext_acted = d->ext_t = 0;
+    return 0;
+}
+
+long long ppo_rollout_act(void* vppo, float* d_action) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = ppo ? (PPODev*)ppo->dev : NULL;
+    if (!d || !d_action || !d->ext_open || d->ext_acted || d->ext_t >= d->ro_T) return -1;
+    TrajectoryBuffer* b = ppo->buffer;
+    GaussianPolicy* pol = ppo->policy;
+    const int E = d->ro_E, S = b->state_size, A = b->action_size;
+    const int* rows = d->ro_rows + (long)d->ext_t * E;
+    /* as ppo_rollout_device's step: normalise into the shadow, forward μ over the step's rows, sample into them */
+    float* shadow = obs_on(d) ? obs_shadow(ppo, d) : NULL;
+    if (shadow)
+        phip_obs_normalize_rows(b->d_state_p, rows, shadow, rows, E, S, d->obs_m, d->obs_m + S, d->obs_clip,
+                                d->obs_run);
+    nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
+    const uint64_t step = d->ro_step++;
+    if (cat_on(d)) phip_cat_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
+    d->ext_acted = 1;
+    return (long long)step;
+}
+
+int ppo_rollout_store(void* vppo, const float* d_reward, const float* d_next_obs, const unsigned char* d_term,
+                      const unsigned char* d_trunc, const float* d_obs_after) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = ppo ? (PPODev*)ppo->dev : NULL;
+    if (!d || !d_reward || !d_next_obs || !d_term || !d_trunc || !d->ext_open || !d->ext_acted) return -1;
+    TrajectoryBuffer* b = ppo->buffer;
+    phip_ext_store(d_next_obs, d_obs_after, d_reward, d_term, d_trunc, b->d_state_p, b->d_next_state_p, b->d_reward_p,
+                   (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, d->ext_obs, d->ro_E, d->ro_T,
+                   d->ext_t, b->state_size);
+    d->ext_acted = 0;
+    d->ext_t++;
+    return 0;
+}
+
+int ppo_rollout_end(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    PPODev* d = ppo ? (PPODev*)ppo->dev : NULL;
+    if (!d || !d->ext_open || d->ext_acted || d->ext_t != d->ro_T) return -1;
+    ro_finish(ppo, d, d->ro_E, d->ro_T);
+    d->ext_open = 0;
+    d->ext_done = 1;
+    return 0;
+}
+
+/* ppo_act_device's scratch for m rows (grow-only) */
+static void act_ws(PPODev* d, int m, int S) {
+    if (m <= d->act_m) return;
+    phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
+    d->act_obsn = (float*)phip_malloc(sizeof(float) * (size_t)m * S);
+    d->act_lp = (float*)phip_malloc(sizeof(float) * (size_t)m);
+    d->act_rows = (int*)phip_malloc(sizeof(int) * (size_t)m);
+    phip_rollout_rows(d->act_rows, m, 1);                        /* rows[i] = i */
+    d->act_m = m;
+}
+
+int ppo_act_device(void* vppo, const float* d_obs, int m, int deterministic, unsigned long long seed,
+                   unsigned long long step, float* d_action, float* d_log_prob) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !d_obs || !d_action || m <= 0) return -1;
+    const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
+    PPODev* d = dev_ws(ppo, 1);
+    GaussianPolicy* pol = ppo->policy;
+    const int cat = cat_on(d), norm = obs_on(d);
+    act_ws(d, m, S);
+    /* normalised under the pair as it stands, uncounted, nothing folded (as ppo_eval_device) */
+    if (norm) {
+        obs_ws(ppo, d);
+        phip_obs_normalize_rows(d_obs, NULL, d->act_obsn, NULL, m, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run);
+    }
+    /* through the row list, as the rollout forwards: the same kernels over the same rows */
+    nn_forward_dev_rows(pol->mu, norm ? d->act_obsn : d_obs, d->act_rows, NULL, m);
+    const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
+    float* lp = d_log_prob ? d_log_prob : d->act_lp;
+    if (cat && deterministic) phip_cat_argmax(pol->mu->d_output, d_action, m, A);
+    else if (cat) phip_cat_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, key, step);
+    else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
+    else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
+    return 0;
+}
+
+/* ------------------------------------------------------------------ */
+/* the built-in environments on dense arrays (ppo_ext.h)               */
+/* ------------------------------------------------------------------ */
+int ppo_env_state_floats(int env_kind, int S) {
+    if (env_kind == 0) return S == 3 ? 3 : -1;
+    if (env_kind == 1) return S > 0 ? S : -1;
+    if (env_kind == 2) return S == 4 ? 5 : -1;
+    return -1;
+}
+
+int ppo_env_reset_device(int env_kind, float* d_env_state, float* d_obs, int E, int S, unsigned long long seed) {
+    if (ppo_env_state_floats(env_kind, S) < 0 || !d_env_state || !d_obs || E <= 0) return -1;
+    phip_env_reset(env_kind, d_env_state, d_obs, E, 1, S, splitmix64(seed));
+    phip_env_first_obs(env_kind, d_env_state, d_obs, E, 1, S);   /* T = 1: row e of the dense array */
+    return 0;
+}
+
+int ppo_env_step_device(int env_kind, float* d_env_state, const float* d_action, float* d_next_obs, float* d_obs_after,
+                        float* d_reward, unsigned char* d_term, unsigned char* d_trunc, int E, int S, int A,
+                        int categorical, unsigned long long seed, unsigned long long step) {
+    if (ppo_env_state_floats(env_kind, S) < 0 || E <= 0 || A <= 0) return -1;
+    if (!d_env_state || !d_action || !d_next_obs || !d_obs_after || !d_reward || !d_term || !d_trunc) return -1;
+    if (env_kind == 0 && A != 1) return -1;
+    if (env_kind == 2 && (A != 2 || !categorical)) return -1;
+    if (env_kind == 1 && categorical && A < 2) return -1;
+    phip_env_step_dense(env_kind, d_env_state, d_action, d_next_obs, d_obs_after, d_reward, d_term, d_trunc, E,
+                        (uint64_t)step, S, A, splitmix64(seed ^ 0x524F4C4CULL), categorical != 0);
+    return 0;
 }
 
 /* ------------------------------------------------------------------ */

@@ -191,6 +191,15 @@ _SIGS = {
                                   C.POINTER(C.c_double), C.c_int]),
     "ppo_sample_action_device": (None, [_P, _P, _P, _P, C.c_int, C.c_ulonglong, C.c_ulonglong]),
     "ppo_fill_synthetic": (None, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_float]),
+    "ppo_rollout_begin": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_ulonglong]),
+    "ppo_rollout_act": (C.c_longlong, [_P, _P]),
+    "ppo_rollout_store": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "ppo_rollout_end": (C.c_int, [_P]),
+    "ppo_act_device": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _P, _P]),
+    "ppo_env_state_floats": (C.c_int, [C.c_int, C.c_int]),
+    "ppo_env_reset_device": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_ulonglong]),
+    "ppo_env_step_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_ulonglong, C.c_ulonglong]),
     "ppo_prof_enable": (None, [C.c_int]),
     "ppo_prof_reset": (None, []),
     "ppo_prof_kernel_events": (None, [C.c_int]),
