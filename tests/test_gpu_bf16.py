@@ -1,11 +1,15 @@
 """bf16 compute mode (BASELINE config C5: "4×1024 MLP bf16") — csrc/gemm16.hip through the C ABI.
 
 Two references:
-  * a bf16-emulated one (numpy, float64 accumulation) that rounds exactly what the kernels round:
-    layer inputs and the weight shadow to bf16 on the way into the MFMA, hidden activations and
-    hidden gradients stored as bf16, the network output and the heads' gradient fp32, bias
-    gradients summed from the bf16-rounded gradient.  Tolerance 2e-3·max|ref| (fp32 accumulation
-    order only) — this pins the kernels;
+  * a bf16-emulated one (bf16_ref.emulate: numpy, float64 accumulation) that rounds exactly what the
+    kernels round: layer inputs and the weight shadow to bf16 on the way into the MFMA, hidden
+    activations and hidden gradients stored as bf16, the network output and the heads' gradient fp32,
+    bias gradients summed from the bf16-rounded gradient.  Tolerance 2e-3·max|ref|, the maximum taken
+    over the network output or over the packed gradient of the WHOLE network: this bounds end-to-end
+    drift, rounding-boundary flips of the stored bf16 values included — it does not pin a kernel (the
+    packed maximum is the last layer's bias gradient; a layer-0 grad_W that loses a batch row stays
+    inside it at three of the four shapes below).  The kernels are pinned launch by launch, element by
+    element, at ragged shapes and under every configuration in test_gpu_bf16_kernels.py;
   * the oracle (fp32 restatement of the reference CPU path): bf16 agrees within 3e-2·max|ref|
     (SURVEY §8c's bf16 bound) — this pins that bf16 mode still computes the reference's layers.
 Every bf16 tile configuration is forced once.
@@ -14,55 +18,10 @@ import numpy as np
 import pytest
 
 import ppo_ffi
+from bf16_ref import emulate
 from helpers import F32, dev, nn_grads_packed, nn_set_params_packed
 
 pytestmark = pytest.mark.gpu
-
-
-def bf16(a):
-    """round-to-nearest-even to bf16, returned as float32 (NaN-free inputs)"""
-    u = np.ascontiguousarray(a, F32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(F32)
-
-
-def unpack(sizes, params):
-    out, off = [], 0
-    for i in range(len(sizes) - 1):
-        nw = sizes[i] * sizes[i + 1]
-        W = params[off:off + nw].reshape(sizes[i + 1], sizes[i])
-        off += nw
-        b = params[off:off + sizes[i + 1]]
-        off += sizes[i + 1]
-        out.append((W, b))
-    return out
-
-
-def emulate(sizes, params, x, gout):
-    """bf16-mode forward + backward as the kernels compute it (float64 accumulation)."""
-    layers = unpack(sizes, params)
-    L = len(layers)
-    hs = [bf16(x)]                                  # layer inputs as the MFMA sees them
-    for i, (W, b) in enumerate(layers):
-        z = hs[-1].astype(np.float64) @ bf16(W).astype(np.float64).T + b
-        if i < L - 1:
-            hs.append(bf16(np.maximum(z, 0.0).astype(F32)))
-        else:
-            y = z.astype(F32)
-    grads = [None] * L
-    g = gout.astype(F32)                            # fp32 from the heads, rounded in the loader
-    for i in range(L - 1, -1, -1):
-        W, _ = layers[i]
-        gb16 = bf16(g).astype(np.float64)
-        gW = gb16.T @ hs[i].astype(np.float64)
-        gbias = gb16.sum(axis=0)
-        grads[i] = (gW.astype(F32).ravel(), gbias.astype(F32))
-        if i > 0:
-            gx = gb16 @ bf16(W).astype(np.float64)
-            gx = np.where(hs[i] > 0, gx, 0.0)
-            g = bf16(gx.astype(F32))                # hidden gradients stored bf16
-    packed = np.concatenate([np.concatenate([gw, gb]) for gw, gb in grads])
-    return y, packed
 
 
 def close(got, ref, rel, what):

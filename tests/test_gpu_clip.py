@@ -19,7 +19,7 @@ import pytest
 import ppo_ffi
 from clip_ref import clip_grad_norm
 from helpers import F32, assert_gemm_close, assert_rel_close, gpu_relu_masks, nn_grads_packed, nn_params_packed
-from test_gpu_bf16 import bf16
+from bf16_ref import bf16
 from test_gpu_production import RELU, device_buffer, ref_policy_grads, ref_value_grads
 from test_gpu_update import make_ppo, policy_state
 

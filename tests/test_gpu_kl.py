@@ -22,7 +22,7 @@ import ppo_ffi
 from clip_ref import clip_grad_norm
 from helpers import F32, assert_gemm_close, gpu_relu_masks, nn_grads_packed, nn_params_packed
 from kl_ref import approx_kl, clip_fraction
-from test_gpu_bf16 import bf16
+from bf16_ref import bf16
 from test_gpu_production import RELU, device_buffer, ref_policy_grads
 from test_gpu_update import make_ppo, policy_state
 

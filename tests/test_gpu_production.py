@@ -34,7 +34,7 @@ import pytest
 import ppo_ffi
 from helpers import (F32, assert_gemm_close, assert_normalised_close, assert_rel_close, gpu_relu_masks,
                      nn_grads_packed, nn_input_rows, nn_params_packed, oracle_grads_with_masks)
-from test_gpu_bf16 import bf16, unpack
+from bf16_ref import _bf16_dev, bf16, check_bf16_layers
 from test_gpu_update import adam_first_step, assert_adam_delta, make_ppo, policy_state
 
 pytestmark = pytest.mark.gpu
@@ -373,106 +373,12 @@ def test_c4_timed_value_step(lib, oracle, c4):
 
 # ----------------------------------------------------------------------------- C5: bf16 at the bench shard
 C5 = [1024, 1024, 1024, 1024, 1024, 17]
-ULP = 2.0 ** -8          # bf16 round-to-nearest: relative error ≤ 2^-8 (8 significant bits)
-
-
-def emu_forward(sizes, params, x):
-    """bf16-mode forward as the kernels compute it, end to end (float64 accumulation)."""
-    layers = unpack(sizes, params)
-    hs = [bf16(x)]
-    for i, (W, b) in enumerate(layers):
-        z = hs[-1].astype(np.float64) @ bf16(W).astype(np.float64).T + b
-        if i < len(layers) - 1:
-            hs.append(bf16(np.maximum(z, 0.0).astype(F32)))
-        else:
-            y = z.astype(F32)
-    return hs, y
-
-
-def emu_backward(sizes, params, hs, gout):
-    layers = unpack(sizes, params)
-    grads = [None] * len(layers)
-    g = gout.astype(F32)
-    for i in range(len(layers) - 1, -1, -1):
-        W, _ = layers[i]
-        gb16 = bf16(g).astype(np.float64)
-        grads[i] = ((gb16.T @ hs[i].astype(np.float64)).astype(F32).ravel(), gb16.sum(axis=0).astype(F32))
-        if i > 0:
-            gx = np.where(hs[i] > 0, gb16 @ bf16(W).astype(np.float64), 0.0)
-            g = bf16(gx.astype(F32))
-    return np.concatenate([np.concatenate([gw, gb]) for gw, gb in grads])
 
 
 def close(got, ref, rel, what):
     err = float(np.abs(got - ref).max())
     tol = rel * float(np.abs(ref).max()) + 1e-6
     assert err <= tol, f"{what}: max |err| {err:.3g} > {tol:.3g}"
-
-
-def _bf16_dev(lib, ptr, rows, width):
-    u = ppo_ffi.d2h(lib, ptr, np.uint16, rows * width).reshape(rows, width)
-    return (u.astype(np.uint32) << 16).view(F32)
-
-
-def assert_bf16_rounding(got, want, sum_abs, what):
-    """got (bf16 storage) is the bf16 rounding of an fp32 accumulation of want (float64): within half
-    a bf16 ulp of want, plus the fp32 accumulation bound 2^-15·Σ|terms| (sum_abs)."""
-    tol = ULP * np.abs(want) + 2.0 ** -15 * sum_abs + 1e-12
-    bad = np.abs(got - want) > tol
-    assert not bad.any(), f"{what}: {int(bad.sum())} elements off by more than a bf16 rounding, worst " \
-                          f"{float(np.abs(got - want)[bad].max()):.3g}"
-
-
-def check_bf16_layers(lib, nn_ptr, sizes, params, x, gtop, top_rounded, what):
-    """Teacher-forced check of every bf16 kernel of one minibatch, at production size: each layer's
-    forward from the GPU's own bf16 input activation, each layer's grad_W / bias sums / grad_x from the
-    GPU's own stored bf16 gradient (layers[i+1].d_grad_x) — so a bf16 rounding-boundary flip upstream
-    (inherent to bf16 storage: the flip rate compounds with depth, ≈ 7e-3 of the last hidden layer's
-    elements at C5) does not propagate into the comparison, and every kernel is pinned to fp32
-    accumulation accuracy.  top_rounded: the output layer's gradient enters its products rounded to
-    bf16 (both the separate bf16 launches and the fused bf16 value head, out_head.hip, round it as
-    they stage it)."""
-    nn = nn_ptr.contents
-    L, B = len(sizes) - 1, x.shape[0]
-    layers = unpack(sizes, params)
-    hs = [bf16(x)] + [_bf16_dev(lib, nn.layers[i].d_input, B, sizes[i]) for i in range(1, L)]
-    for i in range(L - 1):                                  # hidden layers: bf16(relu(x·Wᵀ + b))
-        W, b = layers[i]
-        z = hs[i].astype(np.float64) @ bf16(W).astype(np.float64).T + b
-        sa = np.abs(hs[i]).astype(np.float64) @ np.abs(bf16(W)).astype(np.float64).T + np.abs(b)
-        assert_bf16_rounding(hs[i + 1], np.maximum(z, 0.0), sa, f"{what} forward layer {i}")
-    W, b = layers[L - 1]
-    y = ppo_ffi.d2h(lib, nn.d_output, F32, B * sizes[L]).reshape(B, sizes[L])
-    z = hs[L - 1].astype(np.float64) @ bf16(W).astype(np.float64).T + b
-    close(y, z, 1e-5, f"{what} output layer (fp32 out)")
-    grads = nn_grads_packed(lib, nn_ptr)
-    off = 0
-    for i in range(L):
-        W, b = layers[i]
-        nw = W.size
-        if i == L - 1:
-            g = (bf16(gtop) if top_rounded else gtop).astype(np.float64)
-        else:
-            g = _bf16_dev(lib, nn.layers[i + 1].d_grad_x, B, sizes[i + 1]).astype(np.float64)
-        gW = g.T @ hs[i].astype(np.float64)
-        # fp32 sums over B = 16384 rows (split-K partials, wave-level chains, f32 atomics): bounded by
-        # the fp32 summation error of those terms, c·Σ|g·h| with c = 2^-15 (≈ 256 chained additions
-        # of unit roundoff 2^-24 — the chains the kernels use are shorter), not by max|gW|: the
-        # MSE / surrogate gradients change sign row to row, so |Σ g·h| ≪ Σ|g·h|
-        c = 2.0 ** -15
-        sum_abs = np.abs(g).T @ np.abs(hs[i]).astype(np.float64)
-        err = np.abs(grads[off:off + nw].reshape(W.shape) - gW)
-        assert (err <= c * sum_abs + 1e-9).all(), f"{what} grad_W layer {i}: worst err / Σ|g·h| " \
-            f"{float((err / np.maximum(sum_abs, 1e-30)).max()):.3g}"
-        errb = np.abs(grads[off + nw:off + nw + b.size] - g.sum(axis=0))
-        assert (errb <= c * np.abs(g).sum(axis=0) + 1e-9).all(), f"{what} bias grad layer {i}"
-        off += nw + b.size
-        if i > 0:
-            gx = np.where(hs[i] > 0, g @ bf16(W).astype(np.float64), 0.0)
-            sa = np.abs(g) @ np.abs(bf16(W)).astype(np.float64)
-            assert_bf16_rounding(_bf16_dev(lib, nn.layers[i].d_grad_x, B, sizes[i]), gx, sa,
-                                 f"{what} grad_x layer {i}")
-    return grads
 
 
 @pytest.fixture(scope="module")
@@ -571,6 +477,8 @@ def test_c5_bf16_timed_policy_step(lib, oracle, c5):
     assert (err <= tol).all(), "C5 log_std grad vs fp32 oracle"
     flips = assert_adam_delta(mu1, adam_first_step(mu0, gmu, LR), gmu, LR, "C5 policy params")
     assert flips <= mu1.size // 1000
+
+
 def test_c5_bf16_timed_value_step(lib, oracle, c5):
     """One bf16 value minibatch at the bench's C5 shard (N = 524,288, B = 16384, fused bf16 value head):
     every kernel teacher-forced against the bf16 rounding model, the whole gradient against the fp32

@@ -22,7 +22,7 @@ import pytest
 import ppo_ffi
 from helpers import F32, assert_gemm_close, dev, empty, gpu_relu_masks, nn_grads_packed, nn_params_packed, \
     oracle_grads_with_masks
-from test_gpu_bf16 import bf16
+from bf16_ref import bf16
 from test_gpu_production import RELU, check_bf16_layers, close
 from test_gpu_update import make_ppo
 from vclip_ref import vclip_f32, vclip_f64

@@ -13,8 +13,8 @@ sys.path[:0] = [os.path.join(R, "ppo.c_amd"), os.path.join(R, "oracle"), os.path
 import oracle_ffi as oracle  # noqa: E402
 import ppo_ffi  # noqa: E402
 from helpers import F32, nn_grads_packed, nn_params_packed  # noqa: E402
-from test_gpu_bf16 import bf16, unpack  # noqa: E402
-from test_gpu_production import C5, bench_ppo, emu_backward, emu_forward  # noqa: E402
+from bf16_ref import bf16, emu_backward, emu_forward, unpack  # noqa: E402
+from test_gpu_production import C5, bench_ppo  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 16384
 lib = ppo_ffi.load()
