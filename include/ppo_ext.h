@@ -125,7 +125,8 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * integer: integer atomics only; under data parallelism THIS RANK's rows), out[24]=rewards it scaled (limit)
  * (reward normalisation, ppo_set_reward_norm: all three 0 while it is off; callers passing n <= 22 see no
  * change).
- * With the categorical policy (ppo_set_action_dist 1) out[4] is the mean row entropy of the last policy step's
+ * With the categorical policy (ppo_set_action_dist 1) — or the multi-discrete one, its joint row entropy — out[4] is the
+ * mean row entropy of the last policy step's
  * minibatch (Σ H / rows as the head accumulated it; 0 before the first policy step; under data parallelism THIS
  * RANK's rows), not the Gaussian entropy of log σ. */
 void ppo_read_stats(void* ppo, double* out, int n);
@@ -281,6 +282,49 @@ int    ppo_categorical_head_device(const float* d_logits, const float* d_action,
  * for bad arguments, as above. */
 int    ppo_categorical_sample_device(const float* d_logits, int m, int A, unsigned long long key,
                                      unsigned long long offset, float* d_action, float* d_log_prob);
+/* The multi-discrete policy (off by default; not in the reference; gymnasium's MultiDiscrete space): a step's action
+ * is D independent choices, and μ's A = action_size outputs are D softmaxes side by side.  nvec = (n_0 … n_{D−1})
+ * with every n_d >= 2, Σ n_d == A, 2 <= A <= 4096 and 1 <= D <= PPO_MD_MAX_D; component d owns the logits
+ * [o_d, o_d + n_d), o_d = Σ_{j<d} n_j.  It is action distribution 2 and generalises dist 1, which is the case D = 1.
+ * A row's stored action stays A floats: columns 0 … D−1 hold the chosen indices a_d ∈ [0, n_d) as exact floats,
+ * columns D … A−1 are written as +0; reads clamp into [0, n_d).  Per row, fp32, in this order (csrc/ppo_math.h):
+ *     per component d: M_d, e_k, s_d, t_d, ls_d = logf(s_d), lp_d = (z_{o_d + a_d} − M_d) − ls_d, H_d = ls_d − t_d / s_d
+ *     lp = ((lp_0 + lp_1) + lp_2) + …     H = ((H_0 + H_1) + H_2) + …        d ascending
+ *     g  = ∂loss/∂lp of the clipped surrogate on the JOINT lp (one ratio per row)
+ *     ∂loss/∂z_k, k in component d = g·([k == o_d + a_d] − p_k) + (ent_coeff / m)·p_k·((z_k − M_d) − ls_d + H_d)
+ *     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+ * The entropy term of a logit's gradient takes its own component's H_d (∂H/∂z_k = ∂H_d/∂z_k).  A component with
+ * n_d <= 32 is summed k ascending by one lane, a wider one by lane partials combined in a fixed tree, so a row's
+ * outputs are bit-reproducible; with nvec = {A}, A <= 32, lp, H and every gradient element are dist 1's bits.
+ * SAMPLING draws one uniform per (row, component): component d of row e takes u01 of word d & 3 (.x .y .z .w) of
+ * philox(e | ((uint64)(d >> 2) << 32), offset, key), key and offset exactly those dist 1 uses at each call site, and
+ * inverts its own CDF as dist 1 does; d = 0 is dist 1's draw, so D = 1 samples what dist 1 samples bit for bit.  The
+ * stored log-prob is the joint lp.  The deterministic action is the per-component argmax, lowest index on ties.
+ * While it is on: ppo_get_action_dist returns 2; everything said of dist 1 above holds — the multi-launch update loop
+ * with the multi-discrete head (one launch, csrc/multidiscrete.hip), the KL monitor on the joint lp, ppo_read_stats
+ * out[4] = the mean joint row entropy, ppo_rollout_device / ppo_eval_device / ppo_fill_synthetic / the open rollout /
+ * ppo_act_device, the options it composes with, the entry points that stay Gaussian, train_ppo_epoch / eval_ppo ending
+ * the process.  The synthetic environment reads component d = j mod D for observation element j as
+ * c_d = 2·a_d/(n_d − 1) − 1, its reward's action term is −0.01·(Σ_d c_d²)/D; CartPole-v1 accepts nvec = {2} and then
+ * fills the buffers dist 1 fills.  ppo_env_step_device keeps its Gaussian and dist-1 forms only; action masking is
+ * not provided.  ppo_set_action_dist(ppo, 0 | 1) switches away from it; ppo_set_action_dist(ppo, 2) returns −1 (it
+ * has no nvec).  Not part of a checkpoint: set it again after load_ppo.
+ * ppo_set_action_multidiscrete returns 0, or −1 with the setting unchanged for a NULL argument, D out of range, an
+ * n_d < 2, Σ n_d != A, A > 4096 or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).
+ * ppo_get_action_nvec returns D (0 unless the distribution is 2) and fills min(D, cap) entries of out. */
+#define PPO_MD_MAX_D 256
+int    ppo_set_action_multidiscrete(void* ppo, const int* nvec, int D);
+int    ppo_get_action_nvec(void* ppo, int* out, int cap);
+/* The multi-discrete head and sampler on caller-supplied device arrays (test entries: the update and the rollouts
+ * call the same launchers), as their categorical counterparts above; nvec is a HOST array of D widths summing to A.
+ * d_lp / d_ent [m] are the joint log-prob and entropy.  They synchronise.  Return 0, or −1 for bad arguments (a NULL
+ * array, m <= 0, an nvec the setter would decline, NaN eps) with nothing recorded for ppo_last_error. */
+int    ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                     const float* d_old_lp, int m, int A, const int* nvec, int D, float eps,
+                                     float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss);
+int    ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const int* nvec, int D,
+                                       unsigned long long key, unsigned long long offset, float* d_action,
+                                       float* d_log_prob);
 /* Running observation normalisation (off by default; not in the reference; Stable-Baselines3 VecNormalize,
  * CleanRL NormalizeObservation).  Per observation column j the running state is, in double, a shared count n,
  * mean[j] and M2[j] (the sum of squared deviations; population variance M2/n, as SB3's RunningMeanStd).  The

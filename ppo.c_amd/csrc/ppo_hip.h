@@ -138,7 +138,9 @@ void phip_f32_to_bf16(unsigned short* dst, const float* src, long count);
 /* ---------------- batched device rollout (rollout.hip) ---------------- */
 /* env kinds: 0 = Pendulum-v1 (S = 3, A = 1), 1 = synthetic (any S, A), 2 = CartPole-v1 (S = 4, A = 2, categorical
  * actions).  env_state holds PHIP_ENV_STATE(S) floats per environment.  cat != 0 (the step functions): column 0
- * of an action row is a categorical index (kind 1 reads it as 2·index/(A − 1) − 1; kind 2 requires it) */
+ * of an action row is a categorical index (kind 1 reads it as 2·index/(A − 1) − 1; kind 2 requires it).
+ * md_off != NULL (phip_env_step, phip_env_step_eval; cat != 0): the multi-discrete policy's D + 1 offsets — kind
+ * 1 reads columns 0 … D−1 as D indices (rollout.hip) */
 #define PHIP_ENV_STATE(S) ((S) > 5 ? (S) : 5)
 void phip_rollout_rows(int* rows, int E, int T);             /* rows[t·E + e] = e·T + t */
 void phip_env_reset(int kind, float* env_state, float* state, int E, int T, int S, uint64_t seed);
@@ -150,13 +152,13 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
  * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h) */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat);
+                   uint64_t seed, int cat, const int* md_off, int D);
 /* the evaluation's step (ppo_eval_device): the same dynamics (shared __device__ functions) over compact arrays —
  * obs [E, S] is the current observation, read and replaced in place, action [E, A]; reward / term / trunc are
  * written at row e·T + t and cont as phip_env_step writes them; nothing else is kept */
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat);
+                        uint64_t seed, int cat, const int* md_off, int D);
 /* the dense step (ppo_env_step_device): the same dynamics again over [E, ·] arrays the caller owns — action in;
  * the transition's next observation, the observation the next step starts from (the reset one where the episode
  * ended), reward, terminated and the environment's own TimeLimit out.  No segment end, no cont */
@@ -298,6 +300,23 @@ void phip_cat_sample_rows(const float* logits, const int* rows, float* action, f
 /* action[e] ← (argmax_k logits[e, k], 0, …, 0), the lowest index on ties */
 void phip_cat_argmax(const float* logits, float* action, int m, int A);
 
+/* ---------------- multi-discrete policy (multidiscrete.hip) ---------------- */
+#define PHIP_MD_MAX_D 256
+/* D softmaxes side by side over logits [m, A]: component d owns [d_off[d], d_off[d + 1]), d_off (device, D + 1
+ * ints) ascending from 0 to A, every width >= 2; max_n the widest component (the launcher's choice of form).  The
+ * chosen indices are columns 0 … D−1 of action [m, A].  Outputs as phip_cat_head's, lp / ent the joint ones. */
+void phip_md_head(const float* logits, const float* action, const float* adv, const float* old_lp, int m, int A,
+                  const int* d_off, int D, int max_n, float epsilon, float ent_coeff, float* grad, float* lp_out,
+                  float* ent_out, float* d_loss_accum, float* d_ent_accum);
+/* component d of row e from u01 of word d & 3 of philox(e | (d >> 2) << 32, offset, key); the action row (indices
+ * in columns 0 … D−1, zeros after) and the joint log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
+void phip_md_sample(const float* logits, const int* rows, const int* d_off, float* action, float* logprob, int m,
+                    int A, int D, uint64_t key, uint64_t offset);
+void phip_md_sample_rows(const float* logits, const int* rows, const int* d_off, float* action, float* logprob, int E,
+                         int A, int D, uint64_t key, uint64_t step);
+/* action[e] ← the per-component argmax (lowest index on ties) in columns 0 … D−1, zeros after */
+void phip_md_argmax(const float* logits, const int* d_off, float* action, int m, int A, int D);
+
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
  * (n, mean, M2) in double for this shard.  Then normalise with the (global)
@@ -423,9 +442,12 @@ typedef struct {
 /* Σ (expm1(x) − x) and the clipped-row count of one policy minibatch (x = log-prob − old log-prob, rows of
  * μ [m, A]) into rec->sums; one launch, deterministic (no floating-point atomics, grid a function of m), no
  * host read.  decide_here != 0: the same launch also decides (below) from the local sums */
-/* dist: 0 = Gaussian; 1 = categorical — μ holds the logits, column 0 of the action the index, log σ is unread */
+/* dist: 0 = Gaussian; 1 = categorical — μ holds the logits, column 0 of the action the index, log σ is unread;
+ * 2 = multi-discrete — md_off (device, D + 1 offsets) splits the logits, columns 0 … D−1 hold the indices, lp is
+ * the joint one (md_off and D are unread otherwise) */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
-                    int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec);
+                    int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
+                    const int* md_off, int D);
 /* kl = sums[0] / rows_global, clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
  * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the
  * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so

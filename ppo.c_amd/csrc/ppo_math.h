@@ -101,6 +101,43 @@ __device__ __forceinline__ float cat_log_prob_row(const float* z, int A, int a) 
     return cat_log_prob(z[a], M, logf(cat_row_sum(z, A, M, nullptr)));
 }
 
+// ---- Multi-discrete policy (ppo_set_action_multidiscrete; no counterpart in the reference): the A logits of a
+// row are D softmaxes side by side.  nvec = (n_0 … n_{D−1}), every n_d >= 2, Σ n_d = A; component d owns the logits
+// [o_d, o_d + n_d), o_d = Σ_{j<d} n_j (the offsets array off[0 … D], off[D] = A).  The stored action row holds the
+// chosen indices a_d ∈ [0, n_d) as exact floats in columns 0 … D−1 (columns D … A−1 are +0); reads clamp with
+// cat_index(·, n_d).  Per row, all fp32, every component through the cat_* atoms above:
+//     per component d:  M_d, e_k, s_d, t_d, ls_d = logf(s_d), lp_d = cat_log_prob(z_{o_d + a_d}, M_d, ls_d),
+//                       H_d = cat_entropy(ls_d, t_d, s_d)
+//     lp = ((lp_0 + lp_1) + lp_2) + …        H = ((H_0 + H_1) + H_2) + …              d ascending
+//     g  = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)                      one ratio per row, the joint lp
+//     ∂loss/∂z_k, k in component d = cat_grad(g, k == o_d + a_d, z_k, M_d, s_d, ls_d, H_d, ent_coeff / m)
+//     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+// The entropy term of a logit's gradient takes its own component's H_d: ∂H/∂z_k = ∂H_d/∂z_k.  A component with
+// n_d <= 32 is summed k ascending by one lane (md_component); a wider one may combine lane partials by the kernel's
+// fixed tree.  D = 1 is the categorical policy bit for bit.  tests/multidiscrete_ref.py restates it.
+struct MdComp { float M, s, ls, lp, H; };
+// one thread walks component z[0 … n) in index order; a the chosen index inside it
+__device__ __forceinline__ MdComp md_component(const float* z, int n, int a) {
+    MdComp c;
+    c.M = cat_row_max(z, n);
+    float t;
+    c.s = cat_row_sum(z, n, c.M, &t);
+    c.ls = logf(c.s);
+    c.lp = cat_log_prob(z[a], c.M, c.ls);
+    c.H = cat_entropy(c.ls, t, c.s);
+    return c;
+}
+// the joint log-prob of one row by one thread (the KL monitor): cat_log_prob_row per segment, d ascending
+__device__ __forceinline__ float md_log_prob_row(const float* z, const int* off, int D, const float* action) {
+    float lp = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const int o = off[d], n = off[d + 1] - o;
+        const float l = cat_log_prob_row(z + o, n, cat_index(action[d], n));
+        lp = d == 0 ? l : lp + l;
+    }
+    return lp;
+}
+
 // ---- Gaussian entropy (policy.cu:171-193): this constant, then += log σ_j for j ascending, at the call site
 // (the sum inside a helper compiled to other code than the kernels' own loops)
 __device__ __forceinline__ float entropy_start(int A) { return (float)(A * 0.5 * (1 + log(2 * M_PI))); }

@@ -26,6 +26,13 @@
 //     ppo_rollout_device / ppo_eval_device
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e   offset kNoise + g   .x   u01, inverse CDF
 //     ppo_categorical_sample_device(key, offset)          counter i (row)   offset `offset`   .x   u01, inverse CDF
+//   multi-discrete policy (ppo_set_action_multidiscrete; multidiscrete.hip; tests/multidiscrete_ref.py restates
+//   these rows): one uniform per (row, component d); key and offset are the categorical rows' above at each call
+//   site, the counter's high word is d >> 2 and the word is d & 3 — d = 0 is the categorical draw
+//     ppo_fill_synthetic      action noise   key s0 ^ 5   counter i | (d >> 2) << 32   offset 0   word d & 3 (.x .y .z .w)
+//     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
+//                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e | (d >> 2) << 32   offset kNoise + g   word d & 3
+//     ppo_multidiscrete_sample_device(key, offset)        counter i | (d >> 2) << 32   offset `offset`   word d & 3
 #pragma once
 
 #include <cmath>

@@ -16,6 +16,9 @@
 //            o ~ U(−1, 1).  With a categorical policy (ppo_set_action_dist 1) the action row holds an index
 //            in column 0: every element reads tanh's argument as c = 2·index/(A − 1) − 1, whatever j, and
 //            the reward's action term becomes −0.01·c²; the noise, the done draw and the reset are unchanged.
+//            With a multi-discrete policy (ppo_set_action_multidiscrete) columns 0 … D−1 hold D indices: element
+//            j reads component d = j mod D as c_d = 2·a_d/(n_d − 1) − 1 and the reward's action term is
+//            −0.01·(Σ_d c_d²)/D, d ascending — at D = 1 the categorical arithmetic bit for bit.
 //   kind 2 — CartPole-v1 (S = 4, A = 2, categorical policy only): gymnasium's constants (g = 9.8, cart 1.0, pole
 //            0.1, half-length 0.5, force 10, τ = 0.02) and explicit Euler, in fp32 in the order of
 //            cartpole_advance below; action index 1 pushes right.  Terminated when |x| > 2.4 or |θ| > 12·2π/360
@@ -150,14 +153,22 @@ __global__ void pendulum_eval_kernel(float* __restrict__ es, float* __restrict__
 // reward / done decision per env is taken by every thread of the env identically (same Philox draw).
 struct SynthStep { float o2, nxt, reward; bool done; };
 
+// multi-discrete: component d's index (column d of the action row) mapped onto [−1, 1]
+__device__ __forceinline__ float md_centre(const float* __restrict__ ar, const int* __restrict__ md_off, int d) {
+    const int n = md_off[d + 1] - md_off[d];
+    return 2.f * (float)ppo::cat_index(ar[d], n) / (float)(n - 1) - 1.f;
+}
+
 __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restrict__ ar, long k, int e, int j, int A,
-                                                   uint64_t step, uint64_t seed, int cat) {
+                                                   uint64_t step, uint64_t seed, int cat,
+                                                   const int* __restrict__ md_off, int D) {
     SynthStep s;
     const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
     s.done = u01(d.z) < 1.f / 500.f;
     const float eps = normal_at((uint64_t)k, kEnv + 2 * step + 1, seed);
     // categorical: the index of column 0 mapped onto [−1, 1]
-    const float c = cat ? 2.f * (float)ppo::cat_index(ar[0], A) / (float)(A - 1) - 1.f : 0.f;
+    float c = cat ? 2.f * (float)ppo::cat_index(ar[0], A) / (float)(A - 1) - 1.f : 0.f;
+    if (md_off) c = md_centre(ar, md_off, j % D);    // multi-discrete: this element's component
     float o2 = 0.95f * o + 0.05f * tanhf(cat ? c : ar[j % A]) + 0.05f * eps;
     o2 = fminf(fmaxf(o2, -1.f), 1.f);
     s.o2 = o2;
@@ -165,7 +176,15 @@ __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restr
     if (j == 0) {
         float ss = 0.f;
         for (int q = 0; q < A; ++q) ss += ar[q] * ar[q];
-        const float act_term = cat ? -0.01f * (c * c) : -0.01f * ss / (float)A;
+        float act_term = cat ? -0.01f * (c * c) : -0.01f * ss / (float)A;
+        if (md_off) {
+            float cc = 0.f;
+            for (int d = 0; d < D; ++d) {
+                const float cd = md_centre(ar, md_off, d);
+                cc += cd * cd;
+            }
+            act_term = -0.01f * cc / (float)D;
+        }
         s.reward = act_term + 0.1f * sqrtf(-2.f * logf(u01(d.x))) * cosf(2.f * (float)M_PI * u01(d.y));
     }
     s.nxt = s.done ? -1.f + 2.f * u01(philox((uint64_t)k, kReset + step, seed).x) : o2;
@@ -177,12 +196,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed, cat);
+    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed, cat, md_off, D);
     next_state[row * S + j] = s.o2;
     if (j == 0) {
         reward[row] = s.reward;
@@ -198,12 +217,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
 __global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                   float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat, md_off, D);
     if (j == 0) {
         reward[row] = s.reward;
         term[row] = s.done ? 1 : 0;
@@ -370,7 +389,7 @@ __global__ void synth_dense_kernel(float* __restrict__ es, const float* __restri
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
-    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat, nullptr, 0);
     next_obs[k] = s.o2;
     if (j == 0) {
         reward[e] = s.reward;
@@ -469,8 +488,9 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat) {
+                   uint64_t seed, int cat, const int* md_off, int D) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
+    PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step: multi-discrete offsets");
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && A == 1, "phip_env_step: Pendulum-v1 needs S = 3, A = 1");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
@@ -482,15 +502,16 @@ void phip_env_step(int kind, float* env_state, float* state, const float* action
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
-                           seed, cat);
+                           seed, cat, md_off, D);
     }
     PPO_LAUNCH_CHECK();
 }
 
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat) {
+                        uint64_t seed, int cat, const int* md_off, int D) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * S + A + 2));
+    PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step_eval: multi-discrete offsets");
     PPO_REQUIRE(env_state && obs && action && reward && term && trunc && cont && E > 0 && t >= 0 && t < T,
                 "phip_env_step_eval: operands");
     if (kind == 0) {
@@ -504,7 +525,8 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
                            action, reward, term, trunc, cont, E, T, t, step, seed);
     } else {
         hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
-                           env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat);
+                           env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat, md_off,
+                           D);
     }
     PPO_LAUNCH_CHECK();
 }

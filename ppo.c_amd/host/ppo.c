@@ -127,6 +127,12 @@ typedef struct {
     int action_dist;
     float* cat_ent;
     int cat_rows;
+    /* the multi-discrete policy (ppo_set_action_multidiscrete; action_dist == 2; csrc/multidiscrete.hip): μ's A
+     * outputs are md_D softmaxes side by side of widths md_nvec; md_off (device, md_D + 1 ints) their offsets,
+     * md_max_n the widest.  It takes every path the categorical policy takes, with its own kernels */
+    int md_D, md_max_n;
+    int md_nvec[PHIP_MD_MAX_D];
+    int* md_off;
     /* the open rollout (ppo_rollout_begin / _act / _store / _end; ro_kind == PHIP_ENV_EXTERNAL): ext_open while
      * one is open, ext_t the step the next act takes, ext_acted between an act and its store, ext_done once a
      * rollout has ended and ext_obs [ro_E, ro_S] — the observations the next step starts from, as the stores left
@@ -225,6 +231,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->kl);
     phip_free(d->vclip_counts);
     phip_free(d->cat_ent);
+    phip_free(d->md_off);
     phip_free(d->obs_run); phip_free(d->obs_m); phip_free(d->obs_shadow); phip_free(d->obs_next);
     phip_free(d->obs_batch); phip_free(d->obs_all); phip_free(d->obs_counts);
     phip_free(d->rew_run); phip_free(d->rew_scale); phip_free(d->rew_shadow); phip_free(d->rew_batch);
@@ -319,7 +326,22 @@ static int gae_full_forwards(void) {
 /* running observation normalisation (ppo_ext.h ppo_set_obs_norm)      */
 /* ------------------------------------------------------------------ */
 static int obs_on(const PPODev* d) { return d && d->obs_clip > 0.f; }
-static int cat_on(const PPODev* d) { return d && d->action_dist == 1; }
+/* a discrete policy: categorical (1) or multi-discrete (2) — μ's outputs are logits, log σ is unread */
+static int cat_on(const PPODev* d) { return d && (d->action_dist == 1 || d->action_dist == 2); }
+static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
+/* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
+static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
+
+/* the discrete policies' samplers and greedy action, one call per site */
+static void disc_sample_rows(const PPODev* d, const float* logits, const int* rows, float* action, float* logprob,
+                             int E, int A, uint64_t key, uint64_t step) {
+    if (md_on(d)) phip_md_sample_rows(logits, rows, d->md_off, action, logprob, E, A, d->md_D, key, step);
+    else phip_cat_sample_rows(logits, rows, action, logprob, E, A, key, step);
+}
+static void disc_argmax(const PPODev* d, const float* logits, float* action, int m, int A) {
+    if (md_on(d)) phip_md_argmax(logits, d->md_off, action, m, A, d->md_D);
+    else phip_cat_argmax(logits, action, m, A);
+}
 
 /* the running triple and its affine pair (the identity until something is folded or set) */
 static void obs_ws(PPO* ppo, PPODev* d) {
@@ -881,19 +903,26 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     }
     /* μ grads + (top bucket) the log σ gradient behind them */
     const int cat = !tab && cat_on(d);
+    const int kl_dist = cat ? d->action_dist : 0;
     if (cat) {             /* categorical policy: the plain branch with its own head (categorical.hip) */
         /* log σ is unused: the head writes no gradient to it, and the entropy Adam below steps on the zeros
          * kept here, which leaves log σ bit-identical */
         /* ppo_set_action_dist and ppo_set_compute_dtype decline the pair; nn_set_compute_dtype on μ itself does not
          * know the PPO, so the combination is caught where it would run: the head reads fp32 logits */
-        if (mu->dtype != 0) die("ppo_update: the categorical policy needs fp32 compute mode (μ is in bf16 mode)");
+        if (mu->dtype != 0)
+            die(md_on(d) ? "ppo_update: the multi-discrete policy needs fp32 compute mode (μ is in bf16 mode)"
+                         : "ppo_update: the categorical policy needs fp32 compute mode (μ is in bf16 mode)");
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         *ls_zero = 1;
         phip_memset(d->cat_ent, 0, sizeof(float));
         d->cat_rows = B;
         nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
-        phip_cat_head(mu->d_output, act, adv, olp, B, A, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
-                      d->stats + 1, d->cat_ent);
+        if (md_on(d))
+            phip_md_head(mu->d_output, act, adv, olp, B, A, d->md_off, d->md_D, d->md_max_n, ppo->epsilon,
+                         ppo->ent_coeff, d->gmu, NULL, NULL, d->stats + 1, d->cat_ent);
+        else
+            phip_cat_head(mu->d_output, act, adv, olp, B, A, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
+                          d->stats + 1, d->cat_ent);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
     } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
@@ -921,8 +950,8 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const int kl_on = !tab && d->target_kl > 0.f;
     const long kl_rows = (long)B * phip_comm_world();
     if (kl_on && c->comm) {
-        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, cat, ppo->epsilon, d->target_kl, kl_rows, 0,
-                       d->kl);
+        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
+                       0, d->kl, md_off(d), d->md_D);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -943,8 +972,8 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (!ap->flat || !ppo->adam_entropy->flat) die("ppo_update: target-KL early stopping needs flat Adam spans");
         if (c->comm) phip_kl_decide(d->kl, d->target_kl, kl_rows);
         else
-            phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, cat, ppo->epsilon, d->target_kl, kl_rows, 1,
-                           d->kl);
+            phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
+                           1, d->kl, md_off(d), d->md_D);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -1399,7 +1428,7 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         v[23] = (double)cnt[0];
         v[24] = (double)cnt[1];
     }
-    if (cat_on(d)) {                            /* categorical: the mean row entropy of the last policy step */
+    if (cat_on(d)) {         /* categorical / multi-discrete: the mean (joint) row entropy of the last policy step */
         float h = 0.f;
         phip_d2h(&h, d->cat_ent, sizeof(float));
         v[4] = d->cat_rows > 0 ? (double)h / d->cat_rows : 0.0;
@@ -1575,12 +1604,12 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         /* through the row list, as the rollout forwards: the same kernels over the same E rows */
         nn_forward_dev_rows(pol->mu, norm ? d->ev_obsn : d->ev_obs, d->ev_rows, NULL, E);
         const uint64_t step = (uint64_t)t;
-        if (cat && deterministic) phip_cat_argmax(pol->mu->d_output, d->ev_act, E, A);
-        else if (cat) phip_cat_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
+        if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d->ev_act, E, A);
+        else if (cat) disc_sample_rows(d, pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
-                           d->ev_cont, E, T, t, step, S, A, key, cat);
+                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D);
     }
     phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
                       d->ev_agg, NULL);
@@ -1766,7 +1795,7 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
     if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
     phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
-    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec);
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0);
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
     out2[0] = (double)sums[0] / m;
@@ -1858,6 +1887,93 @@ int ppo_get_action_dist(void* vppo) {
     return ppo && ppo->dev ? ((PPODev*)ppo->dev)->action_dist : 0;
 }
 
+/* nvec → the D + 1 offsets in off (host) and the widest component; −1 unless 1 <= D <= PPO_MD_MAX_D, every n_d >= 2,
+ * Σ n_d == A and 2 <= A <= PHIP_CAT_MAX_A */
+static int md_offsets(const int* nvec, int D, int A, int* off) {
+    if (!nvec || D < 1 || D > PHIP_MD_MAX_D || A < 2 || A > PHIP_CAT_MAX_A) return -1;
+    int max_n = 0;
+    off[0] = 0;
+    for (int i = 0; i < D; i++) {
+        if (nvec[i] < 2 || nvec[i] > A) return -1;
+        off[i + 1] = off[i] + nvec[i];
+        if (off[i + 1] > A) return -1;
+        if (nvec[i] > max_n) max_n = nvec[i];
+    }
+    return off[D] == A ? max_n : -1;
+}
+
+/* ppo_ext.h: the multi-discrete policy */
+int ppo_set_action_multidiscrete(void* vppo, const int* nvec, int D) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !nvec) return -1;
+    int off[PHIP_MD_MAX_D + 1];
+    const int max_n = md_offsets(nvec, D, ppo->buffer->action_size, off);
+    if (max_n < 0) return -1;
+    if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;           /* bf16 compute mode */
+    PPODev* d = dev_ws(ppo, 1);
+    if (!d->md_off) d->md_off = (int*)phip_malloc(sizeof(int) * (PHIP_MD_MAX_D + 1));
+    phip_sync();                                     /* nothing in flight reads the offsets being replaced */
+    phip_h2d(d->md_off, off, sizeof(int) * (size_t)(D + 1));
+    memcpy(d->md_nvec, nvec, sizeof(int) * (size_t)D);
+    d->md_D = D;
+    d->md_max_n = max_n;
+    d->action_dist = 2;
+    return 0;
+}
+
+int ppo_get_action_nvec(void* vppo, int* out, int cap) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    if (!md_on(d)) return 0;
+    for (int i = 0; out && i < d->md_D && i < cap; i++) out[i] = d->md_nvec[i];
+    return d->md_D;
+}
+
+/* the multi-discrete head and sampler on caller-supplied device arrays (test entries, as the categorical ones);
+ * nvec is a host array, its offsets go to a device array kept here */
+static int* md_test_offsets(const int* nvec, int D, int A, int* max_n) {
+    static int* d_off = NULL;
+    int off[PHIP_MD_MAX_D + 1];
+    *max_n = md_offsets(nvec, D, A, off);
+    if (*max_n < 0) return NULL;
+    if (!d_off) d_off = (int*)phip_malloc(sizeof(int) * (PHIP_MD_MAX_D + 1));
+    phip_sync();
+    phip_h2d(d_off, off, sizeof(int) * (size_t)(D + 1));
+    return d_off;
+}
+
+int ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                  const float* d_old_lp, int m, int A, const int* nvec, int D, float eps,
+                                  float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
+    static float* word = NULL;
+    if (!d_logits || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || m <= 0 || isnan(eps))
+        return -1;
+    int max_n;
+    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
+    if (!d_off) return -1;
+    if (!word) word = (float*)phip_malloc(4 * sizeof(float));
+    phip_memset(word, 0, 4 * sizeof(float));
+    phip_md_head(d_logits, d_action, d_adv, d_old_lp, m, A, d_off, D, max_n, eps, ent_coeff, d_grad, d_lp, d_ent, word,
+                 NULL);
+    phip_sync();
+    float l = 0.f;
+    phip_d2h(&l, word, sizeof(float));
+    *loss = (double)l;
+    return 0;
+}
+
+int ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const int* nvec, int D,
+                                    unsigned long long key, unsigned long long offset, float* d_action,
+                                    float* d_log_prob) {
+    if (!d_logits || !d_action || !d_log_prob || m <= 0) return -1;
+    int max_n;
+    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
+    if (!d_off) return -1;
+    phip_md_sample(d_logits, NULL, d_off, d_action, d_log_prob, m, A, D, key, offset);
+    phip_sync();
+    return 0;
+}
+
 /* the categorical head and sampler on caller-supplied device arrays (test entries: bad arguments return −1 ahead of
  * any device call, so nothing is recorded for ppo_last_error) */
 int ppo_categorical_head_device(const float* d_logits, const float* d_action, const float* d_adv,
@@ -1915,8 +2031,8 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
                      int n_epochs_value) {
     /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
     if (cat_on((PPODev*)ppo->dev))
-        die("train_ppo_epoch: the categorical policy (ppo_set_action_dist) is not supported by the host rollout; "
-            "use ppo_rollout_device + ppo_update");
+        die("train_ppo_epoch: a discrete policy (ppo_set_action_dist, ppo_set_action_multidiscrete) is not supported "
+            "by the host rollout; use ppo_rollout_device + ppo_update");
     if (obs_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout; "
             "use ppo_rollout_device + ppo_update");
@@ -1937,8 +2053,8 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
     if (cat_on((PPODev*)ppo->dev))
-        die("eval_ppo: the categorical policy (ppo_set_action_dist) is not supported by the host rollout; use "
-            "ppo_eval_device");
+        die("eval_ppo: a discrete policy (ppo_set_action_dist, ppo_set_action_multidiscrete) is not supported by the "
+            "host rollout; use ppo_eval_device");
     if (obs_on((PPODev*)ppo->dev))
         die("eval_ppo: observation normalisation (ppo_set_obs_norm) is not supported by the host rollout");
     reset_buffer(ppo->buffer);
@@ -2044,7 +2160,7 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     const int cat = cat_on(d);
     if (env_kind == 2 && (S != 4 || A != 2 || !cat))
         die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
-            "(ppo_set_action_dist)");
+            "(ppo_set_action_dist, or ppo_set_action_multidiscrete with nvec = {2})");
     d->ext_open = d->ext_done = 0;                               /* an open rollout is simply closed */
     ro_rows_ws(d, E, T);
     if (d->ro_E != E || d->ro_kind != env_kind || d->ro_S != S || !d->env_state) {
@@ -2069,11 +2185,11 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         /* one position in the Philox streams per step of every call: the policy noise and the environment's
          * draws never repeat under a constant seed */
         const uint64_t step = d->ro_step++;
-        if (cat) phip_cat_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
+        if (cat) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
-                      cat);
+                      cat, md_off(d), d->md_D);
     }
     ro_finish(ppo, d, E, T);
 }
@@ -2100,7 +2216,12 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     }
     if (cat_on((PPODev*)ppo->dev)) {     /* categorical: one uniform per row from the "action noise" key */
         nn_forward_dev(ppo->policy->mu, obs, (int)N);
-        phip_cat_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, s0 ^ 0x5, 0);
+        const PPODev* d = (const PPODev*)ppo->dev;
+        if (md_on(d))
+            phip_md_sample(ppo->policy->mu->d_output, NULL, d->md_off, b->d_action_p, b->d_logprob_p, (int)N, A,
+                           d->md_D, s0 ^ 0x5, 0);
+        else
+            phip_cat_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, s0 ^ 0x5, 0);
     } else {
         ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     }
@@ -2161,7 +2282,7 @@ long long ppo_rollout_act(void* vppo, float* d_action) {
                                 d->obs_run);
     nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
     const uint64_t step = d->ro_step++;
-    if (cat_on(d)) phip_cat_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    if (cat_on(d)) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
     d->ext_acted = 1;
@@ -2221,8 +2342,8 @@ int ppo_act_device(void* vppo, const float* d_obs, int m, int deterministic, uns
     nn_forward_dev_rows(pol->mu, norm ? d->act_obsn : d_obs, d->act_rows, NULL, m);
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     float* lp = d_log_prob ? d_log_prob : d->act_lp;
-    if (cat && deterministic) phip_cat_argmax(pol->mu->d_output, d_action, m, A);
-    else if (cat) phip_cat_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, key, step);
+    if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d_action, m, A);
+    else if (cat) disc_sample_rows(d, pol->mu->d_output, d->act_rows, d_action, lp, m, A, key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;

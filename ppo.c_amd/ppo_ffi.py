@@ -161,6 +161,12 @@ _SIGS = {
     "ppo_categorical_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P, _P,
                                               C.POINTER(C.c_double)]),
     "ppo_categorical_sample_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _P, _P]),
+    "ppo_set_action_multidiscrete": (C.c_int, [_P, c_int_p, C.c_int]),
+    "ppo_get_action_nvec": (C.c_int, [_P, c_int_p, C.c_int]),
+    "ppo_multidiscrete_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_float,
+                                                C.c_float, _P, _P, _P, C.POINTER(C.c_double)]),
+    "ppo_multidiscrete_sample_device": (C.c_int, [_P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_ulonglong,
+                                                  C.c_ulonglong, _P, _P]),
     "ppo_set_value_clip": (C.c_int, [_P, C.c_float]),
     "ppo_get_value_clip": (C.c_float, [_P]),
     "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
