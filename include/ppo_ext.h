@@ -306,8 +306,8 @@ int    ppo_categorical_sample_device(const float* d_logits, int m, int A, unsign
  * ppo_act_device, the options it composes with, the entry points that stay Gaussian, train_ppo_epoch / eval_ppo ending
  * the process.  The synthetic environment reads component d = j mod D for observation element j as
  * c_d = 2·a_d/(n_d − 1) − 1, its reward's action term is −0.01·(Σ_d c_d²)/D; CartPole-v1 accepts nvec = {2} and then
- * fills the buffers dist 1 fills.  ppo_env_step_device keeps its Gaussian and dist-1 forms only; action masking is
- * not provided.  ppo_set_action_dist(ppo, 0 | 1) switches away from it; ppo_set_action_dist(ppo, 2) returns −1 (it
+ * fills the buffers dist 1 fills.  ppo_env_step_device keeps its Gaussian and dist-1 forms only; invalid
+ * actions are masked with ppo_set_action_mask (below).  ppo_set_action_dist(ppo, 0 | 1) switches away from it; ppo_set_action_dist(ppo, 2) returns −1 (it
  * has no nvec).  Not part of a checkpoint: set it again after load_ppo.
  * ppo_set_action_multidiscrete returns 0, or −1 with the setting unchanged for a NULL argument, D out of range, an
  * n_d < 2, Σ n_d != A, A > 4096 or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).
@@ -325,6 +325,67 @@ int    ppo_multidiscrete_head_device(const float* d_logits, const float* d_actio
 int    ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const int* nvec, int D,
                                        unsigned long long key, unsigned long long offset, float* d_action,
                                        float* d_log_prob);
+/* INVALID-ACTION MASKING for the categorical and the multi-discrete policy (off by default; not in the reference;
+ * Stable-Baselines3-contrib MaskablePPO, CleanRL ppo_*_mask): state-dependent illegal actions are taken out of the
+ * softmax everywhere it is evaluated — the head (log-prob, entropy, gradient), the sampler, the greedy action and the
+ * target-KL monitor — and the mask is stored per transition, so the update sees the distribution the rollout sampled
+ * from.  The definition (csrc/ppo_math.h "Action masking"):
+ * MASK STORAGE.  A row's mask is W = (A + 31) / 32 uint32 words; bit k & 31 of word k >> 5 set = logit column k is
+ * allowed, k the column in the row of A logits counted across the components; bits at k >= A are ignored.
+ * EFFECTIVE MASK of component d (columns [o_d, o_d + n_d); d = 0, n_0 = A for dist 1), in this order: 1. its stored
+ * bits; 2. none of them set: the component reads as fully allowed — nothing is NaN, nothing aborts; 3. only where a
+ * chosen action exists (head, KL): the chosen column is OR-ed in, so a caller-filled buffer whose action contradicts
+ * its mask still gives a finite log-prob.
+ * ARITHMETIC.  Per component, fp32, k ascending over the allowed columns only: M_d = max z_k, e_k = expf(z_k − M_d),
+ * s_d = Σ e_k, t_d = Σ e_k·(z_k − M_d); ls_d, lp_d, H_d, the joint lp and H, the surrogate on the joint ratio, the
+ * gradient of an allowed column and the loss exactly as above.  A masked column contributes to no max and no sum, its
+ * gradient element is written as +0 and its logit is never read into arithmetic: a NaN, an infinity or 1e30 there
+ * changes no output bit.  With every bit set, lp, H and the gradient are the unmasked multi-discrete head's bits for
+ * the same nvec; masked dist 1 is masked dist 2 with nvec = {A} (for A <= 32 also the categorical head's bits).
+ * SAMPLING inverts the CDF over the allowed columns only — c accumulates e_k over allowed k ascending, the action is
+ * the first allowed k with u·s_d <= c, the fallback the last allowed k — with the same Philox word per (row,
+ * component) as without masking: under a full mask it draws the unmasked action and log-prob bit for bit.  The greedy
+ * action is the lowest allowed index holding the maximum over the allowed columns.
+ * ppo_set_action_mask(ppo, on): on allocates a PPO-owned device store of capacity × W words, every bit set, freed
+ * with the PPO (or when turned off); row r's words are at r·W.  Returns 0, or −1 with the setting unchanged for a
+ * NULL ppo or while the distribution is Gaussian; ppo_set_action_dist(ppo, 0) turns it off, and changing the
+ * distribution or nvec through the setters sets every bit of the store again.  ppo_action_mask_words returns W (0 for
+ * a NULL ppo), ppo_action_mask_buffer the device store — NULL while masking is off — for callers who lay the buffer
+ * themselves.  TrajectoryBuffer and every reference layout are untouched; the setting and the store are not part of a
+ * checkpoint and not hashed by ppo_param_hash, and no collective is added under data parallelism.
+ * While it is on, ppo_update's policy step runs the masked head (one launch, csrc/masked.hip) for both discrete
+ * distributions: minibatch row i reads the mask of its buffer row in place, through the row indices the minibatch
+ * gather already produces — no gather launch is added — and the KL monitor takes the masked joint lp; everything else
+ * in the step and the options it composes with are unchanged.  With masking off, or on with full masks, every
+ * discrete path gives the bits it gives without this feature.
+ * ppo_rollout_act_masked is ppo_rollout_act with d_mask [E, W] (dense, environment e's words at e·W): it samples
+ * under the masks and writes them to the step's rows of the store in the same launch; −1 while masking is off or for
+ * a NULL mask.  While masking is on, plain ppo_rollout_act, ppo_rollout_device and ppo_fill_synthetic write full masks
+ * for the rows they lay (the built-in environments have no illegal actions; their sampled bits are unchanged).
+ * ppo_act_device_masked is ppo_act_device with d_mask [m, W], in the sampled and the deterministic case; −1 while
+ * masking is off or for a NULL mask.  ppo_eval_device stays unmasked. */
+int       ppo_set_action_mask(void* ppo, int on);
+int       ppo_get_action_mask(void* ppo);                 /* 0 for a NULL ppo */
+int       ppo_action_mask_words(void* ppo);
+uint32_t* ppo_action_mask_buffer(void* ppo);
+long long ppo_rollout_act_masked(void* ppo, const uint32_t* d_mask, float* d_action);
+int       ppo_act_device_masked(void* ppo, const float* d_obs, const uint32_t* d_mask, int m, int deterministic,
+                                unsigned long long seed, unsigned long long step, float* d_action,
+                                float* d_log_prob);
+/* The masked head, sampler and greedy action on caller-supplied device arrays (test entries: the update, the rollouts
+ * and ppo_act_device_masked call the same launchers), as their multi-discrete counterparts; nvec is a HOST array
+ * (dist 1: nvec = {A}).  Head: d_mask holds W words per row, minibatch row i's at d_mask[d_rows[i]·W] (d_rows NULL:
+ * i).  Sampler / argmax: d_mask dense [m, W].  They synchronise.  Return 0, or −1 for bad arguments (a NULL array
+ * other than d_rows, m <= 0, an nvec the setter would decline, NaN eps) with nothing recorded for ppo_last_error. */
+int       ppo_masked_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                 const float* d_old_lp, const uint32_t* d_mask, const int* d_rows, int m, int A,
+                                 const int* nvec, int D, float eps, float ent_coeff, float* d_grad, float* d_lp,
+                                 float* d_ent, double* loss);
+int       ppo_masked_sample_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
+                                   unsigned long long key, unsigned long long offset, float* d_action,
+                                   float* d_log_prob);
+int       ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
+                                   float* d_action);
 /* Running observation normalisation (off by default; not in the reference; Stable-Baselines3 VecNormalize,
  * CleanRL NormalizeObservation).  Per observation column j the running state is, in double, a shared count n,
  * mean[j] and M2[j] (the sum of squared deviations; population variance M2/n, as SB3's RunningMeanStd).  The

@@ -5,7 +5,9 @@
 //   lp_i  = Gaussian log-prob of action_i under (μ_i, log σ)           (ppo_math.h log_prob_row, as the loss)
 //           — or, with a categorical policy (dist 1), cat_log_prob_row of the index in the action's column 0
 //           under the logits μ_i; or, with a multi-discrete policy (dist 2), md_log_prob_row: the joint log-prob
-//           of the indices in columns 0 … D−1; nothing else differs
+//           of the indices in columns 0 … D−1; nothing else differs.  With action masking (mask not NULL; dist 2,
+//           the categorical policy as nvec = {A}): md_log_prob_row_masked under the W words at mask[rows[i]·W]
+//           (rows NULL: i) — the masked head's lp; mask NULL is the unmasked path and its bits
 //   x_i   = (double)lp_i − (double)old_lp_i
 //   kl    = Σ (expm1(x_i) − x_i) / rows          (Schulman's k3 estimator; double: (r − 1) − log r cancels in fp32)
 //   frac  = Σ 1[|(float)exp(x_i) − 1| > ε] / rows
@@ -63,11 +65,15 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
                                                      const float* __restrict__ action,
                                                      const float* __restrict__ old_lp, int m, int A, int dist,
                                                      float eps, float target_kl, double rows_global, int decide_here,
-                                                     PhipKlRec* rec, const int* __restrict__ md_off, int D) {
+                                                     PhipKlRec* rec, const int* __restrict__ md_off, int D,
+                                                     const uint32_t* __restrict__ mask, const int* __restrict__ rows) {
     __shared__ double s[TPB + 1];             // s[TPB]: "this workgroup drew the last ticket"
     double kl = 0.0, cnt = 0.0;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < m; i += (long)gridDim.x * TPB) {
-        const float lp = dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A)
+        const int W = (A + 31) / 32;
+        const float lp = mask      ? ppo::md_log_prob_row_masked(mu + i * A, md_off, D, action + i * A,
+                                                                 mask + (rows ? (long)rows[i] : i) * W)
+                         : dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A)
                          : dist  ? ppo::cat_log_prob_row(mu + i * A, A, ppo::cat_index(action[i * A], A))
                                  : ppo::log_prob_row(mu + i * A, log_std, action + i * A, A);
         const double x = (double)lp - (double)old_lp[i];
@@ -131,13 +137,14 @@ extern "C" {
 
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
-                    const int* md_off, int D) {
+                    const int* md_off, int D, const uint32_t* mask, const int* rows) {
     static_assert(PHIP_KL_PARTS <= TPB, "the last workgroup folds one pair of partials per thread");
     PPO_REQUIRE(m > 0 && A > 0 && rows_global > 0 && rec, "phip_policy_kl: shape");
     PPO_REQUIRE(dist != 2 || (md_off && D >= 1 && 2 * D <= A), "phip_policy_kl: multi-discrete offsets");
+    PPO_REQUIRE(!mask || dist == 2, "phip_policy_kl: a mask needs the multi-discrete form (dist 1 as nvec = {A})");
     ppo::ProfScope ps(PPO_K_ADAM, 8.0 * (double)m * A + 4.0 * m);
     hipLaunchKernelGGL(kl_sum_kernel, dim3(grid_for(m)), dim3(TPB), 0, ppo::stream(), mu, log_std, action, old_lp, m,
-                       A, dist, eps, target_kl, (double)rows_global, decide_here, rec, md_off, D);
+                       A, dist, eps, target_kl, (double)rows_global, decide_here, rec, md_off, D, mask, rows);
     PPO_LAUNCH_CHECK();
 }
 

@@ -317,6 +317,30 @@ void phip_md_sample_rows(const float* logits, const int* rows, const int* d_off,
 /* action[e] ← the per-component argmax (lowest index on ties) in columns 0 … D−1, zeros after */
 void phip_md_argmax(const float* logits, const int* d_off, float* action, int m, int A, int D);
 
+/* ---------------- action masking (masked.hip) ---------------- */
+/* A row's mask is W = (A + 31) / 32 words, bit k & 31 of word k >> 5 = logit column k allowed (ppo_math.h "Action
+ * masking": a component with no stored bit set is fully allowed; the head also allows the chosen column).  The
+ * categorical policy runs these as D = 1, d_off = {0, A}.
+ * phip_md_head under masks: minibatch row i reads its W words at mask[rows[i]·W] (rows NULL: i).  A full mask gives
+ * phip_md_head's lp, entropy and gradient bits; a masked column's gradient is +0 and its logit never read into
+ * arithmetic. */
+void phip_masked_head(const float* logits, const float* action, const float* adv, const float* old_lp,
+                      const uint32_t* mask, const int* rows, int m, int A, const int* d_off, int D, int max_n,
+                      float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out, float* d_loss_accum,
+                      float* d_ent_accum);
+/* phip_md_sample over the allowed columns of the dense mask [m, W] (row e of the mask for row e of the logits);
+ * mask_out (may be NULL): row rows[e]'s W words ← the mask sampled under.  A full mask draws phip_md_sample's bits. */
+void phip_masked_sample(const float* logits, const uint32_t* mask, const int* rows, const int* d_off, float* action,
+                        float* logprob, uint32_t* mask_out, int m, int A, int D, uint64_t key, uint64_t offset);
+void phip_masked_sample_rows(const float* logits, const uint32_t* mask, const int* rows, const int* d_off,
+                             float* action, float* logprob, uint32_t* mask_out, int E, int A, int D, uint64_t key,
+                             uint64_t step);
+/* per component the lowest allowed index holding the maximum over the allowed columns; mask dense [m, W] */
+void phip_masked_argmax(const float* logits, const uint32_t* mask, const int* d_off, float* action, int m, int A,
+                        int D);
+/* mask[rows[e]·W + j] ← all ones for e < E: the rows a step laid with the unmasked sampler */
+void phip_mask_fill_rows(uint32_t* mask, const int* rows, int E, int A);
+
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
  * (n, mean, M2) in double for this shard.  Then normalise with the (global)
@@ -444,10 +468,12 @@ typedef struct {
  * host read.  decide_here != 0: the same launch also decides (below) from the local sums */
 /* dist: 0 = Gaussian; 1 = categorical — μ holds the logits, column 0 of the action the index, log σ is unread;
  * 2 = multi-discrete — md_off (device, D + 1 offsets) splits the logits, columns 0 … D−1 hold the indices, lp is
- * the joint one (md_off and D are unread otherwise) */
+ * the joint one (md_off and D are unread otherwise).  mask (NULL: today's path and bits; needs dist 2, the
+ * categorical policy passing the offsets {0, A}): minibatch row i reads its (A + 31) / 32 words at mask[rows[i]·W]
+ * (rows NULL: i) and lp is the masked joint log-prob (ppo_math.h md_log_prob_row_masked) */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
-                    const int* md_off, int D);
+                    const int* md_off, int D, const uint32_t* mask, const int* rows);
 /* kl = sums[0] / rows_global, clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
  * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the
  * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so

@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdint>
 
 namespace ppo {
 
@@ -133,6 +134,111 @@ __device__ __forceinline__ float md_log_prob_row(const float* z, const int* off,
     for (int d = 0; d < D; ++d) {
         const int o = off[d], n = off[d + 1] - o;
         const float l = cat_log_prob_row(z + o, n, cat_index(action[d], n));
+        lp = d == 0 ? l : lp + l;
+    }
+    return lp;
+}
+
+// ---- Action masking (ppo_set_action_mask; no counterpart in the reference; csrc/masked.hip): a row of A logits
+// carries W = (A + 31) / 32 words, bit k & 31 of word k >> 5 set = column k allowed, k counted across the
+// components; bits at k >= A are ignored.  The EFFECTIVE mask of component d, columns [o_d, o_d + n_d):
+//     1. its stored bits;
+//     2. none of them set: every column of the component is allowed (nothing is NaN, nothing aborts);
+//     3. where a chosen action exists (the head, the KL monitor): the chosen column is allowed too.
+// Per component, fp32, k ascending over the ALLOWED columns only, the atoms above:
+//     M_d = max z_k,  e_k = cat_exp(z_k, M_d),  s_d = Σ e_k,  t_d = Σ e_k·(z_k − M_d),
+//     ls_d = logf(s_d),  lp_d = cat_log_prob(z_{o_d + a_d}, M_d, ls_d),  H_d = cat_entropy(ls_d, t_d, s_d)
+// A masked column enters no max and no sum, its gradient element is +0 and its logit is never read into arithmetic
+// (a NaN, an infinity or 1e30 there changes no output bit).  Joint lp and H, the surrogate, cat_grad on the allowed
+// columns and the loss are the multi-discrete policy's.  With every bit set each function below gives its unmasked
+// counterpart's bits (md_component, md_log_prob_row).  The sampler inverts the CDF over the allowed columns (the
+// fallback is the last allowed one); the greedy action is the lowest allowed index holding the allowed maximum.
+// tests/masked_ref.py restates it.
+__device__ __forceinline__ bool mask_bit(const uint32_t* w, int k) { return (w[k >> 5] >> (k & 31)) & 1u; }
+// any stored bit of columns [o, o + n)
+__device__ __forceinline__ bool mask_any(const uint32_t* w, int o, int n) {
+    const int last = o + n - 1;
+    for (int j = o >> 5; j <= last >> 5; ++j) {
+        uint32_t v = w[j];
+        if (j == o >> 5) v &= ~0u << (o & 31);
+        if (j == last >> 5) v &= ~0u >> (31 - (last & 31));
+        if (v) return true;
+    }
+    return false;
+}
+// the effective mask of one component, fixed once per (row, component); a the chosen index inside it (−1: none).
+// n <= 32: the three rules folded into one word, bit k = column o + k; wider: rule 2 in `full`, rule 3 in `a`, the
+// stored bits read in place
+struct MaskComp {
+    const uint32_t* w;
+    int o, a;
+    uint32_t win;
+    bool narrow, full;
+    __device__ __forceinline__ bool allowed(int k) const {
+        return narrow ? (win >> k) & 1u : (full || k == a || mask_bit(w, o + k));
+    }
+};
+__device__ __forceinline__ MaskComp mask_component(const uint32_t* w, int o, int n, int a) {
+    MaskComp mc;
+    mc.w = w; mc.o = o; mc.a = a;
+    mc.narrow = n <= 32;
+    mc.win = 0u;
+    mc.full = false;
+    if (mc.narrow) {
+        const int j = o >> 5, sh = o & 31;
+        uint32_t v = w[j] >> sh;
+        if (sh && ((o + n - 1) >> 5) > j) v |= w[j + 1] << (32 - sh);
+        const uint32_t all = ~0u >> (32 - n);
+        v &= all;
+        if (!v) v = all;
+        if (a >= 0) v |= 1u << a;
+        mc.win = v;
+    } else {
+        mc.full = !mask_any(w, o, n);
+    }
+    return mc;
+}
+// one thread walks component z[0 … n) under its effective mask; a the chosen index inside it.  The masked joint
+// log-prob of the head's one-lane form and of the KL monitor is this function's lp.
+__device__ __forceinline__ float masked_row_max(const float* z, int n, const MaskComp& mc) {
+    bool first = true;
+    float M = 0.f;
+    for (int k = 0; k < n; ++k) {
+        if (!mc.allowed(k)) continue;
+        M = first ? z[k] : fmaxf(M, z[k]);           // cat_row_max's sequence over the allowed columns
+        first = false;
+    }
+    return M;
+}
+__device__ __forceinline__ float masked_row_sum(const float* z, int n, float M, const MaskComp& mc, float* t) {
+    float s = 0.f, tt = 0.f;
+    for (int k = 0; k < n; ++k) {
+        if (!mc.allowed(k)) continue;
+        const float e = cat_exp(z[k], M);
+        s += e;
+        tt += e * (z[k] - M);
+    }
+    if (t) *t = tt;
+    return s;
+}
+__device__ __forceinline__ MdComp md_component_masked(const float* z, int n, int a, const MaskComp& mc) {
+    MdComp c;
+    c.M = masked_row_max(z, n, mc);
+    float t;
+    c.s = masked_row_sum(z, n, c.M, mc, &t);
+    c.ls = logf(c.s);
+    c.lp = cat_log_prob(z[a], c.M, c.ls);
+    c.H = cat_entropy(c.ls, t, c.s);
+    return c;
+}
+// the masked joint log-prob of one row by one thread (the KL monitor): w the row's W words
+__device__ __forceinline__ float md_log_prob_row_masked(const float* z, const int* off, int D, const float* action,
+                                                        const uint32_t* w) {
+    float lp = 0.f;
+    for (int d = 0; d < D; ++d) {
+        const int o = off[d], n = off[d + 1] - o;
+        const int a = cat_index(action[d], n);
+        const float l = md_component_masked(z + o, n, a, mask_component(w, o, n, a)).lp;
         lp = d == 0 ? l : lp + l;
     }
     return lp;

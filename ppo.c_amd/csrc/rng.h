@@ -33,6 +33,9 @@
 //     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e | (d >> 2) << 32   offset kNoise + g   word d & 3
 //     ppo_multidiscrete_sample_device(key, offset)        counter i | (d >> 2) << 32   offset `offset`   word d & 3
+//   action masking (ppo_set_action_mask; masked.hip): the masked sampler reads the multi-discrete rows above, word
+//   for word (the categorical policy as D = 1) — ppo_rollout_act_masked / ppo_act_device_masked the policy-noise
+//   row, ppo_masked_sample_device(key, offset) the last one; only the CDF it inverts differs
 #pragma once
 
 #include <cmath>

@@ -145,6 +145,14 @@ typedef struct {
     int act_m;
     float *act_obsn, *act_lp;
     int* act_rows;
+    /* invalid-action masking (ppo_set_action_mask; csrc/masked.hip; a discrete policy only): while mask_on the
+     * store `mask` holds capacity × W words, W = (A + 31) / 32, row r's words at r·W, bit k & 31 of word k >> 5 =
+     * logit column k allowed — whatever lays buffer rows writes them, the policy step reads them through the
+     * minibatch's row indices.  NULL while off.  cat_off = the device offsets {0, A}: the categorical policy runs the
+     * masked kernels as nvec = {A}.  Not part of a checkpoint, not hashed, no collective */
+    int mask_on;
+    uint32_t* mask;
+    int* cat_off;
 } PPODev;
 
 static float* g_v = NULL;         /* V(state), V(next_state) for compute_gae_cuda */
@@ -242,6 +250,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ev_reward); phip_free(d->ev_rows); phip_free(d->ev_term); phip_free(d->ev_trunc);
     phip_free(d->ev_cont); phip_free(d->ev_agg);
     phip_free(d->ext_obs); phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
+    phip_free(d->mask); phip_free(d->cat_off);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -331,6 +340,18 @@ static int cat_on(const PPODev* d) { return d && (d->action_dist == 1 || d->acti
 static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
 /* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
 static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
+
+/* action masking: on, the words of one row, and the offsets / component count / widest component the masked kernels
+ * run the discrete policy with (the categorical one as nvec = {A}) */
+static int mask_on(const PPODev* d) { return cat_on(d) && d->mask_on && d->mask; }
+static int mask_words(int A) { return (A + 31) / 32; }
+static const int* disc_off(const PPODev* d) { return md_on(d) ? d->md_off : d->cat_off; }
+static int disc_D(const PPODev* d) { return md_on(d) ? d->md_D : 1; }
+static int disc_max_n(const PPODev* d, int A) { return md_on(d) ? d->md_max_n : A; }
+/* rows [0, n) of the store ← full masks: what an unmasked sampler lays */
+static void mask_fill_full(PPODev* d, long n, int A) {
+    if (mask_on(d)) phip_memset(d->mask, 0xFF, sizeof(uint32_t) * (size_t)n * (size_t)mask_words(A));
+}
 
 /* the discrete policies' samplers and greedy action, one call per site */
 static void disc_sample_rows(const PPODev* d, const float* logits, const int* rows, float* action, float* logprob,
@@ -903,7 +924,12 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     }
     /* μ grads + (top bucket) the log σ gradient behind them */
     const int cat = !tab && cat_on(d);
-    const int kl_dist = cat ? d->action_dist : 0;
+    /* the KL monitor under masking: the masked joint lp, the categorical policy as nvec = {A} */
+    const int kl_mask = cat && mask_on(d);
+    const int kl_dist = kl_mask ? 2 : cat ? d->action_dist : 0;
+    const int* kl_off = kl_mask ? disc_off(d) : md_off(d);
+    const int kl_D = kl_mask ? disc_D(d) : d->md_D;
+    const uint32_t* kl_m = kl_mask ? d->mask : NULL;
     if (cat) {             /* categorical policy: the plain branch with its own head (categorical.hip) */
         /* log σ is unused: the head writes no gradient to it, and the entropy Adam below steps on the zeros
          * kept here, which leaves log σ bit-identical */
@@ -917,7 +943,11 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         phip_memset(d->cat_ent, 0, sizeof(float));
         d->cat_rows = B;
         nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
-        if (md_on(d))
+        if (mask_on(d))    /* either discrete policy under the stored masks, read in place through the row indices */
+            phip_masked_head(mu->d_output, act, adv, olp, d->mask, rows, B, A, disc_off(d), disc_D(d),
+                             disc_max_n(d, A), ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL, d->stats + 1,
+                             d->cat_ent);
+        else if (md_on(d))
             phip_md_head(mu->d_output, act, adv, olp, B, A, d->md_off, d->md_D, d->md_max_n, ppo->epsilon,
                          ppo->ent_coeff, d->gmu, NULL, NULL, d->stats + 1, d->cat_ent);
         else
@@ -951,7 +981,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const long kl_rows = (long)B * phip_comm_world();
     if (kl_on && c->comm) {
         phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
-                       0, d->kl, md_off(d), d->md_D);
+                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -973,7 +1003,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (c->comm) phip_kl_decide(d->kl, d->target_kl, kl_rows);
         else
             phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
-                           1, d->kl, md_off(d), d->md_D);
+                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -1795,7 +1825,7 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
     if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
     phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
-    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0);
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL);
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
     out2[0] = (double)sums[0] / m;
@@ -1869,6 +1899,28 @@ int ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float eps
     return 0;
 }
 
+/* the mask store: on — capacity × W words (allocated once: neither capacity nor A changes), every bit set, and the
+ * categorical policy's offsets {0, A}; off — freed once nothing in flight reads it */
+static void mask_store(PPO* ppo, PPODev* d, int on) {
+    const int A = ppo->buffer->action_size;
+    phip_sync();
+    if (!on) {
+        phip_free(d->mask);
+        d->mask = NULL;
+        d->mask_on = 0;
+        return;
+    }
+    const size_t bytes = sizeof(uint32_t) * (size_t)ppo->buffer->capacity * (size_t)mask_words(A);
+    if (!d->mask) d->mask = (uint32_t*)phip_malloc(bytes);
+    phip_memset(d->mask, 0xFF, bytes);
+    if (!d->cat_off) {
+        const int off[2] = {0, A};
+        d->cat_off = (int*)phip_malloc(sizeof(off));
+        phip_h2d(d->cat_off, off, sizeof(off));
+    }
+    d->mask_on = 1;
+}
+
 /* ppo_ext.h: the action distribution */
 int ppo_set_action_dist(void* vppo, int dist) {
     PPO* ppo = (PPO*)vppo;
@@ -1878,7 +1930,11 @@ int ppo_set_action_dist(void* vppo, int dist) {
         if (A < 2 || A > PHIP_CAT_MAX_A) return -1;
         if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;       /* bf16 compute mode */
     }
-    dev_ws(ppo, 1)->action_dist = dist;
+    PPODev* d = dev_ws(ppo, 1);
+    d->action_dist = dist;
+    /* masking belongs to a discrete policy: off with it; under another one the columns mean something else: full
+     * masks again */
+    if (d->mask_on) mask_store(ppo, d, dist != 0);
     return 0;
 }
 
@@ -1918,6 +1974,7 @@ int ppo_set_action_multidiscrete(void* vppo, const int* nvec, int D) {
     d->md_D = D;
     d->md_max_n = max_n;
     d->action_dist = 2;
+    if (d->mask_on) mask_store(ppo, d, 1);           /* the columns mean something else now: full masks again */
     return 0;
 }
 
@@ -1970,6 +2027,76 @@ int ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const i
     const int* d_off = md_test_offsets(nvec, D, A, &max_n);
     if (!d_off) return -1;
     phip_md_sample(d_logits, NULL, d_off, d_action, d_log_prob, m, A, D, key, offset);
+    phip_sync();
+    return 0;
+}
+
+/* ppo_ext.h: invalid-action masking */
+int ppo_set_action_mask(void* vppo, int on) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo) return -1;
+    PPODev* d = dev_ws(ppo, 1);
+    if (!cat_on(d)) return -1;                       /* a Gaussian policy has no columns to mask */
+    if ((on != 0) != (d->mask_on != 0)) mask_store(ppo, d, on != 0);
+    return 0;
+}
+
+int ppo_get_action_mask(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo && mask_on((const PPODev*)ppo->dev);
+}
+
+int ppo_action_mask_words(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo ? mask_words(ppo->buffer->action_size) : 0;
+}
+
+uint32_t* ppo_action_mask_buffer(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo && mask_on((const PPODev*)ppo->dev) ? ((PPODev*)ppo->dev)->mask : NULL;
+}
+
+/* the masked head, sampler and greedy action on caller-supplied device arrays (test entries, as the multi-discrete
+ * ones; the categorical policy is nvec = {A}) */
+int ppo_masked_head_device(const float* d_logits, const float* d_action, const float* d_adv, const float* d_old_lp,
+                           const uint32_t* d_mask, const int* d_rows, int m, int A, const int* nvec, int D, float eps,
+                           float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
+    static float* word = NULL;
+    if (!d_logits || !d_action || !d_adv || !d_old_lp || !d_mask || !d_grad || !d_lp || !d_ent || !loss || m <= 0 ||
+        isnan(eps))
+        return -1;
+    int max_n;
+    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
+    if (!d_off) return -1;
+    if (!word) word = (float*)phip_malloc(4 * sizeof(float));
+    phip_memset(word, 0, 4 * sizeof(float));
+    phip_masked_head(d_logits, d_action, d_adv, d_old_lp, d_mask, d_rows, m, A, d_off, D, max_n, eps, ent_coeff, d_grad,
+                     d_lp, d_ent, word, NULL);
+    phip_sync();
+    float l = 0.f;
+    phip_d2h(&l, word, sizeof(float));
+    *loss = (double)l;
+    return 0;
+}
+
+int ppo_masked_sample_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
+                             unsigned long long key, unsigned long long offset, float* d_action, float* d_log_prob) {
+    if (!d_logits || !d_mask || !d_action || !d_log_prob || m <= 0) return -1;
+    int max_n;
+    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
+    if (!d_off) return -1;
+    phip_masked_sample(d_logits, d_mask, NULL, d_off, d_action, d_log_prob, NULL, m, A, D, key, offset);
+    phip_sync();
+    return 0;
+}
+
+int ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
+                             float* d_action) {
+    if (!d_logits || !d_mask || !d_action || m <= 0) return -1;
+    int max_n;
+    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
+    if (!d_off) return -1;
+    phip_masked_argmax(d_logits, d_mask, d_off, d_action, m, A, D);
     phip_sync();
     return 0;
 }
@@ -2172,6 +2299,7 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     ro_carry_swap(d, E);
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     GaussianPolicy* pol = ppo->policy;
+    mask_fill_full(d, N, A);                         /* the built-in environments have no illegal actions */
     phip_env_first_obs(env_kind, d->env_state, b->d_state_p, E, T, S);
     /* observation normalisation: each step's E rows are normalised through the row map into the shadow (the
      * same rows there) and μ is forwarded from it; the buffer keeps the raw observations */
@@ -2216,7 +2344,8 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
     }
     if (cat_on((PPODev*)ppo->dev)) {     /* categorical: one uniform per row from the "action noise" key */
         nn_forward_dev(ppo->policy->mu, obs, (int)N);
-        const PPODev* d = (const PPODev*)ppo->dev;
+        PPODev* d = (PPODev*)ppo->dev;
+        mask_fill_full(d, N, A);                     /* sampled unmasked: the rows carry full masks */
         if (md_on(d))
             phip_md_sample(ppo->policy->mu->d_output, NULL, d->md_off, b->d_action_p, b->d_logprob_p, (int)N, A,
                            d->md_D, s0 ^ 0x5, 0);
@@ -2267,8 +2396,8 @@ int ppo_rollout_begin(void* vppo, int n_envs, int horizon, const float* d_obs0, 
     return 0;
 }
 
-long long ppo_rollout_act(void* vppo, float* d_action) {
-    PPO* ppo = (PPO*)vppo;
+/* one act of the open rollout; d_mask [E, W] (NULL: unmasked — the step's rows get full masks while masking is on) */
+static long long rollout_act(PPO* ppo, const uint32_t* d_mask, float* d_action) {
     PPODev* d = ppo ? (PPODev*)ppo->dev : NULL;
     if (!d || !d_action || !d->ext_open || d->ext_acted || d->ext_t >= d->ro_T) return -1;
     TrajectoryBuffer* b = ppo->buffer;
@@ -2282,11 +2411,23 @@ long long ppo_rollout_act(void* vppo, float* d_action) {
                                 d->obs_run);
     nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
     const uint64_t step = d->ro_step++;
-    if (cat_on(d)) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    if (d_mask)            /* under the caller's masks, which go to the step's rows of the store in the same launch */
+        phip_masked_sample_rows(pol->mu->d_output, d_mask, rows, disc_off(d), b->d_action_p, b->d_logprob_p, d->mask, E,
+                                A, disc_D(d), d->ext_key, step);
+    else if (cat_on(d)) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    if (!d_mask && mask_on(d)) phip_mask_fill_rows(d->mask, rows, E, A);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
     d->ext_acted = 1;
     return (long long)step;
+}
+
+long long ppo_rollout_act(void* vppo, float* d_action) { return rollout_act((PPO*)vppo, NULL, d_action); }
+
+long long ppo_rollout_act_masked(void* vppo, const uint32_t* d_mask, float* d_action) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !d_mask || !mask_on((const PPODev*)ppo->dev)) return -1;
+    return rollout_act(ppo, d_mask, d_action);
 }
 
 int ppo_rollout_store(void* vppo, const float* d_reward, const float* d_next_obs, const unsigned char* d_term,
@@ -2324,9 +2465,9 @@ static void act_ws(PPODev* d, int m, int S) {
     d->act_m = m;
 }
 
-int ppo_act_device(void* vppo, const float* d_obs, int m, int deterministic, unsigned long long seed,
-                   unsigned long long step, float* d_action, float* d_log_prob) {
-    PPO* ppo = (PPO*)vppo;
+/* d_mask [m, W] (NULL: unmasked) */
+static int act_device(PPO* ppo, const float* d_obs, const uint32_t* d_mask, int m, int deterministic,
+                      unsigned long long seed, unsigned long long step, float* d_action, float* d_log_prob) {
     if (!ppo || !d_obs || !d_action || m <= 0) return -1;
     const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
     PPODev* d = dev_ws(ppo, 1);
@@ -2342,11 +2483,27 @@ int ppo_act_device(void* vppo, const float* d_obs, int m, int deterministic, uns
     nn_forward_dev_rows(pol->mu, norm ? d->act_obsn : d_obs, d->act_rows, NULL, m);
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     float* lp = d_log_prob ? d_log_prob : d->act_lp;
-    if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d_action, m, A);
+    if (d_mask && deterministic) phip_masked_argmax(pol->mu->d_output, d_mask, disc_off(d), d_action, m, A, disc_D(d));
+    else if (d_mask)
+        phip_masked_sample_rows(pol->mu->d_output, d_mask, d->act_rows, disc_off(d), d_action, lp, NULL, m, A,
+                                disc_D(d), key, step);
+    else if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d_action, m, A);
     else if (cat) disc_sample_rows(d, pol->mu->d_output, d->act_rows, d_action, lp, m, A, key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;
+}
+
+int ppo_act_device(void* vppo, const float* d_obs, int m, int deterministic, unsigned long long seed,
+                   unsigned long long step, float* d_action, float* d_log_prob) {
+    return act_device((PPO*)vppo, d_obs, NULL, m, deterministic, seed, step, d_action, d_log_prob);
+}
+
+int ppo_act_device_masked(void* vppo, const float* d_obs, const uint32_t* d_mask, int m, int deterministic,
+                          unsigned long long seed, unsigned long long step, float* d_action, float* d_log_prob) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !d_mask || !mask_on((const PPODev*)ppo->dev)) return -1;
+    return act_device(ppo, d_obs, d_mask, m, deterministic, seed, step, d_action, d_log_prob);
 }
 
 /* ------------------------------------------------------------------ */

@@ -167,6 +167,17 @@ _SIGS = {
                                                 C.c_float, _P, _P, _P, C.POINTER(C.c_double)]),
     "ppo_multidiscrete_sample_device": (C.c_int, [_P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_ulonglong,
                                                   C.c_ulonglong, _P, _P]),
+    "ppo_set_action_mask": (C.c_int, [_P, C.c_int]),
+    "ppo_get_action_mask": (C.c_int, [_P]),
+    "ppo_action_mask_words": (C.c_int, [_P]),
+    "ppo_action_mask_buffer": (_P, [_P]),
+    "ppo_rollout_act_masked": (C.c_longlong, [_P, _P, _P]),
+    "ppo_act_device_masked": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_ulonglong, C.c_ulonglong, _P, _P]),
+    "ppo_masked_head_device": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_float,
+                                         C.c_float, _P, _P, _P, C.POINTER(C.c_double)]),
+    "ppo_masked_sample_device": (C.c_int, [_P, _P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_ulonglong, C.c_ulonglong,
+                                           _P, _P]),
+    "ppo_masked_argmax_device": (C.c_int, [_P, _P, C.c_int, C.c_int, c_int_p, C.c_int, _P]),
     "ppo_set_value_clip": (C.c_int, [_P, C.c_float]),
     "ppo_get_value_clip": (C.c_float, [_P]),
     "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
