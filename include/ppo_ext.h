@@ -141,8 +141,8 @@ void ppo_reset_stats(void* ppo);
  * feeds the policy Adam and the entropy Adam).  The norm is deterministic (no floating-point atomics),
  * so replicas stay bit-identical under data parallelism.  While clipping is on, ppo_update runs the
  * multi-launch loop: the single-workgroup / cluster phases (small networks, B = 64) and graph replay do
- * not clip and are not taken.  The setting is not part of a checkpoint (save_ppo keeps the reference's
- * byte layout): set it again after load_ppo.
+ * not clip and are not taken.  The setting is not part of a checkpoint (save_ppo's, which keeps the reference's
+ * byte layout; ppo_save_state keeps it): set it again after load_ppo.
  * max_norm <= 0 or +inf: off.  Returns 0, or −1 for NaN (setting unchanged). */
 int    ppo_set_max_grad_norm(void* ppo, float max_norm);
 float  ppo_get_max_grad_norm(void* ppo);                  /* 0 when off */
@@ -166,8 +166,8 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
  * step behind the gradient's, same stream and communicator) and kl is the mean over the global minibatch:
  * EVERY RANK MUST HOLD THE SAME target_kl SETTING, or the ranks issue different sequences of collectives.
  * While it is on, ppo_update runs the multi-launch loop (no single-workgroup / cluster phases, no graph
- * replay), as with gradient clipping, and works together with it.  Not part of a checkpoint: set it again
- * after load_ppo.
+ * replay), as with gradient clipping, and works together with it.  Not part of a checkpoint (save_ppo's; ppo_save_state keeps it):
+ * set it again after load_ppo.
  * target_kl > 0: on; +inf: measure only, never stop; <= 0: off.  Returns 0, or −1 for NaN (unchanged). */
 int    ppo_set_target_kl(void* ppo, float target_kl);
 float  ppo_get_target_kl(void* ppo);                      /* 0 when off */
@@ -197,7 +197,8 @@ int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const flo
  * launch is added to a value step.  While it is on, ppo_update runs the multi-launch loop (no single-workgroup /
  * cluster phases, no graph replay), as with gradient clipping and target-KL early stopping, and works together
  * with both and with data parallelism: the head is element-wise, so no collective is added and the order of
- * collectives does not depend on the setting.  Not part of a checkpoint: set it again after load_ppo.
+ * collectives does not depend on the setting.  Not part of a checkpoint (save_ppo's; ppo_save_state keeps it): set it
+ * again after load_ppo.
  * eps_v > 0 and finite: on; <= 0 or +inf: off.  Returns 0, or −1 for NaN (setting unchanged). */
 int    ppo_set_value_clip(void* ppo, float eps_v);
 float  ppo_get_value_clip(void* ppo);                     /* 0 when off */
@@ -263,7 +264,7 @@ int    ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float 
  * to train against a caller-stepped environment the open rollout (ppo_rollout_begin … _end).  The host rollout
  * has no discrete form: train_ppo_epoch / eval_ppo END THE PROCESS with a message while it is on.
  * The setting lives with the PPO, not in GaussianPolicy (whose layout is the reference's).  Not part of a
- * checkpoint: set it again after load_ppo.
+ * checkpoint (save_ppo's; ppo_save_state keeps it): set it again after load_ppo.
  * Returns 0, or −1 with the setting unchanged for an unknown dist, and for dist 1 with A < 2, A > 4096 or bf16
  * compute mode (ppo_set_compute_dtype(ppo, 1) in turn returns −1 while dist is 1).  nn_set_compute_dtype called on
  * the policy network itself has no handle to the PPO and is not declined: ppo_update ENDS THE PROCESS with a message
@@ -308,7 +309,7 @@ int    ppo_categorical_sample_device(const float* d_logits, int m, int A, unsign
  * c_d = 2·a_d/(n_d − 1) − 1, its reward's action term is −0.01·(Σ_d c_d²)/D; CartPole-v1 accepts nvec = {2} and then
  * fills the buffers dist 1 fills.  ppo_env_step_device keeps its Gaussian and dist-1 forms only; invalid
  * actions are masked with ppo_set_action_mask (below).  ppo_set_action_dist(ppo, 0 | 1) switches away from it; ppo_set_action_dist(ppo, 2) returns −1 (it
- * has no nvec).  Not part of a checkpoint: set it again after load_ppo.
+ * has no nvec).  Not part of a checkpoint (save_ppo's; ppo_save_state keeps it): set it again after load_ppo.
  * ppo_set_action_multidiscrete returns 0, or −1 with the setting unchanged for a NULL argument, D out of range, an
  * n_d < 2, Σ n_d != A, A > 4096 or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).
  * ppo_get_action_nvec returns D (0 unless the distribution is 2) and fills min(D, cap) entries of out. */
@@ -352,7 +353,7 @@ int    ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, cons
  * distribution or nvec through the setters sets every bit of the store again.  ppo_action_mask_words returns W (0 for
  * a NULL ppo), ppo_action_mask_buffer the device store — NULL while masking is off — for callers who lay the buffer
  * themselves.  TrajectoryBuffer and every reference layout are untouched; the setting and the store are not part of a
- * checkpoint and not hashed by ppo_param_hash, and no collective is added under data parallelism.
+ * checkpoint (save_ppo's; ppo_save_state keeps it) and not hashed by ppo_param_hash, and no collective is added under data parallelism.
  * While it is on, ppo_update's policy step runs the masked head (one launch, csrc/masked.hip) for both discrete
  * distributions: minibatch row i reads the mask of its buffer row in place, through the row indices the minibatch
  * gather already produces — no gather launch is added — and the KL monitor takes the masked joint lp; everything else
@@ -414,7 +415,8 @@ int       ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask
  * right behind GAE's own all-gather, combined in rank order and folded, so every rank holds bit-identical
  * statistics: EVERY RANK MUST HOLD THE SAME on/off AND frozen SETTING, or the ranks issue different sequences
  * of collectives.  While it is on, ppo_param_hash and the replica check also cover the 1 + 2S doubles.
- * Not part of a checkpoint (save_ppo keeps the reference's byte layout): save and restore the state with
+ * Not part of a checkpoint (save_ppo's, which keeps the reference's byte layout; ppo_save_state keeps it): with load_ppo,
+ * save and restore the state with
  * ppo_obs_norm_get_state / _set_state and set the option again after load_ppo.  Turning it off keeps the state.
  * clip > 0: on (+inf: normalise, never clamp); <= 0: off.  Returns 0, or −1 for NaN (setting unchanged). */
 int    ppo_set_obs_norm(void* ppo, float clip);
@@ -487,7 +489,8 @@ int    ppo_obs_stats_device(const float* d_x, long n, int S, double* out);
  * (PPO_COMM_LOOPBACK=k): the loopback all-gather hands the peers registered by ppo_comm_loopback_peers to any
  * gather of their length, and this triple has the length of GAE's Welford triple — registered peers would feed
  * both gathers, so do not combine them with this option.
- * Not part of a checkpoint: save and restore the state with ppo_reward_norm_get_state / _set_state.  Turning
+ * Not part of a checkpoint (save_ppo's; ppo_save_state keeps it): with load_ppo, save and restore the state with
+ * ppo_reward_norm_get_state / _set_state.  Turning
  * it off keeps the state.
  * clip > 0: on (+inf: scale, never clamp); <= 0: off.  Returns 0, or −1 for NaN (setting unchanged). */
 int    ppo_set_reward_norm(void* ppo, float clip);
@@ -543,7 +546,7 @@ int    ppo_reward_returns_device(const float* d_reward, const unsigned char* d_t
  * allocated and set fresh on the first call and on a change of n_envs, env_kind or state_size, which drops the
  * episodes in progress and keeps the window.  ppo_fill_synthetic, the host rollout and ppo_update do not touch the
  * tracker.  Under data parallelism the statistics are THIS RANK's environments; no collective is added.  Not
- * hashed (ppo_param_hash) and not part of a checkpoint.
+ * hashed (ppo_param_hash) and not part of a checkpoint (save_ppo's; ppo_save_state keeps it).
  * ppo_episode_stats: out[0..7] since the last reset, out[8..15] the last rollout, each
  *     {episodes n, mean return, population std sqrt(M2/n), min, max, mean length Σlen/n, mean discounted
  *      return, M2}                          (host double arithmetic on the aggregate; all 0 where n == 0) */
@@ -667,7 +670,8 @@ void ppo_rollout_device(void* ppo, int n_envs, int horizon, int env_kind, unsign
  * episode scan with cont[], the advantages zeroed, idx / full, the buffer pointed at the device, rollout-laid.
  * Composes with every option of ppo_update (both normalisers, the categorical policy, clipping, target KL, tanh
  * networks, data parallelism: per rank, no collective added).  The open rollout's own state (step t, the current
- * observations) is not part of a checkpoint. */
+ * observations) is not part of a checkpoint (save_ppo's; ppo_save_state keeps an ended rollout's continuation
+ * observations, and declines while one is open). */
 int       ppo_rollout_begin(void* ppo, int n_envs, int horizon, const float* d_obs0, unsigned long long seed);
 long long ppo_rollout_act(void* ppo, float* d_action);
 int       ppo_rollout_store(void* ppo, const float* d_reward, const float* d_next_obs, const unsigned char* d_term,
@@ -708,6 +712,55 @@ int ppo_env_step_device(int env_kind, float* d_env_state, const float* d_action,
  * synchronises.  bf16 copies (x0_dtype 1) are not converted: returns −1 for them and for m beyond the
  * last forward, else 0. */
 int ppo_nn_input_rows(void* nn, float* out, int m);
+
+/* ---------------- training-state checkpoints ----------------
+ * save_ppo / load_ppo keep the reference's byte layout: five hyper-parameters, the two networks, log σ and the three
+ * Adams.  ppo_save_state keeps THE WHOLE TRAINING STATE, so that a run stopped between two updates and resumed with
+ * ppo_load_state is the run that was interrupted, bit for bit: the same rollouts, minibatch orders, parameters,
+ * normaliser states and episode statistics as if it had never stopped (DESIGN.md §4 "Training-state checkpoints"
+ * gives the file format).  A checkpoint is D2H / H2D copies between updates: no kernel, nothing on the update or
+ * rollout path changes.
+ * WHAT IS KEPT: save_ppo's byte stream itself; the settings — max_grad_norm, target_kl, value_clip, both normalisers'
+ * clip and freeze flag, the episode tracker's gamma, the action distribution with nvec, masking, both networks'
+ * compute dtype (applied on load through their setters: the distribution before the mask, the dtype last); both
+ * normalisers' running triples (the fp32 pair and scale are refreshed on load as _set_state refreshes them); the
+ * device shuffle's epoch key; and, once a rollout has run, the rollout's state — the built-in environments' device
+ * state, the Philox position, cont[], both return carries and whether an update has scanned the last rollout, the
+ * episode tracker's per-environment state and both aggregates, and an ended open rollout's continuation observations
+ * (ppo_rollout_begin(…, NULL, seed) continues after the load).
+ * PPO_CKPT_BUFFER also stores the rows [0, limit) of the trajectory buffer (state, action, log-prob, reward,
+ * next-state and both flags, from wherever the buffer currently points; advantages and targets are not stored: every
+ * update recomputes them) and, while masking is on, the mask store's limit · W words: a save taken between a rollout
+ * and its update resumes into that update.  Without the flag the buffer's contents are not kept: the loaded PPO has an
+ * empty buffer (idx = 0, not full, not rollout-laid, full masks) and must roll out before it updates — the usual place
+ * to save is behind an update.  A loaded buffer is device-resident.
+ * NOT STATE — after a load these are as on a fresh PPO: the ppo_read_stats accumulators and the KL history, the step
+ * limit (ppo_set_step_limit), ppo_value_clip_old_values' caller pointer, every workspace and scratch (the minibatch
+ * and phase gathers, ppo_eval_device's and ppo_act_device's scratch, captured graphs), the process-wide GEMM engine
+ * and tuning knobs, and an RCCL communicator.
+ * PPO_SHUFFLE_HOST_RAND draws from libc rand(), whose state cannot be captured: the bit-for-bit promise holds for
+ * PPO_SHUFFLE_DEVICE, and as far as the update itself is reproducible run to run.  The host rollout's
+ * Env — like a caller's simulator behind the open rollout — is the caller's object and is not kept either.
+ * Under data parallelism every rank saves and loads its own file; no collective is added, and
+ * ppo_comm_check_replicas is how a caller checks the ranks after loading.
+ * ppo_save_state synchronises libppo's streams, copies to the host, writes path + ".tmp" and renames it, so an
+ * interrupted save never leaves a half-written file under path.  Returns 0, or −1 with nothing written and nothing
+ * recorded for ppo_last_error: a NULL argument, an unwritable path, or an open rollout in progress (between
+ * ppo_rollout_begin and _end: partly laid rows are not a state worth keeping).
+ * ppo_load_state validates the whole file on the host — magic, version, bounds, every section's checksum, every
+ * section's length against the shapes in the legacy header — before it touches the device, builds the PPO from the
+ * legacy section (use_cuda = true) and applies the others.  Any failure (a missing, short or damaged file, a version
+ * above 1, a section that contradicts the shapes, an nvec the setter declines) returns NULL with a one-line message in
+ * err (err_cap bytes, may be NULL): the process stays alive, nothing leaks, nothing is recorded for ppo_last_error.
+ * ppo_state_image serialises to memory what ppo_save_state writes — a pure function of the state: no timestamps, no
+ * pointers, every gap zero — and returns its size (out NULL: the size only), or −1 when cap is too small, for a NULL
+ * ppo or an open rollout.  ppo_state_hash is FNV-1a-64 over that image (0 where there is none): two PPOs with equal
+ * hashes under PPO_CKPT_BUFFER continue identically. */
+enum { PPO_CKPT_BUFFER = 1 };   /* also store the trajectory buffer's rows (and the mask store's) */
+int   ppo_save_state(void* ppo, const char* path, int flags);
+void* ppo_load_state(const char* path, char* err, int err_cap);
+unsigned long long ppo_state_hash(void* ppo, int flags);
+int   ppo_state_image(void* ppo, int flags, void* out, long cap);
 
 /* ---------------- compute precision ---------------- */
 /* 0 = fp32 (default: exact fp32 MFMA GEMMs), 1 = bf16 MFMA GEMMs with fp32 accumulation, fp32

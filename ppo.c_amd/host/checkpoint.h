@@ -1,0 +1,52 @@
+/*
+ * checkpoint.h — the container of a training-state checkpoint (DESIGN.md §4 "Training-state checkpoints"):
+ * its constants and the indexer / validator of an image in memory.  Nothing here needs HIP or libppo:
+ * checkpoint_index.c implements it with libc alone and compiles on its own for the CPU.
+ */
+#ifndef PPO_HOST_CHECKPOINT_H
+#define PPO_HOST_CHECKPOINT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#define CKPT_MAGIC "PPOSTATE"
+#define CKPT_VERSION 1u
+#define CKPT_HEADER_BYTES 20u          /* magic[8], u32 version, u32 flags, u32 section count */
+#define CKPT_SECTION_BYTES 24u         /* u32 tag, u32 reserved (0), u64 payload bytes, u64 FNV-1a-64 of the payload */
+
+/* section tags; 0 and everything above CKPT_TAG_BUFFER is unknown to this version and skipped */
+enum { CKPT_TAG_LEGACY = 1, CKPT_TAG_SETTINGS = 2, CKPT_TAG_NORMALISERS = 3, CKPT_TAG_SHUFFLE = 4,
+       CKPT_TAG_ROLLOUT = 5, CKPT_TAG_BUFFER = 6, CKPT_NTAG = 7 };
+/* header flags: bit 0 is the caller's PPO_CKPT_BUFFER (a Buffer section follows); bit 1 is set by the writer
+ * when a Rollout section follows — both optional sections are announced in the header, so a damaged tag
+ * cannot make one vanish unnoticed */
+enum { CKPT_F_BUFFER = 1, CKPT_F_ROLLOUT = 2 };
+
+#define CKPT_SETTINGS_FIXED 52u        /* bytes of the Settings payload around nvec[D] */
+#define CKPT_ROLLOUT_FIXED 32u         /* bytes of the Rollout payload ahead of env_state */
+#define CKPT_BUFFER_FIXED 16u          /* idx, full, limit, mask words */
+#define CKPT_ENV_EXTERNAL 3            /* ro_kind of the open rollout (ppo_hip.h PHIP_ENV_EXTERNAL) */
+#define CKPT_MD_MAX_D 256              /* ppo_ext.h PPO_MD_MAX_D */
+
+typedef struct {
+    int present;
+    uint64_t off, len;                 /* the payload inside the image */
+} CkptSection;
+
+typedef struct {
+    uint32_t version, flags, count;
+    CkptSection sec[CKPT_NTAG];        /* by tag */
+    int S, A, cap;                     /* the shapes in the legacy header */
+    int action_dist, md_D, mask_on;    /* from Settings */
+    int has_obs;                       /* Normalisers holds the observation triple */
+    char err[160];
+} CkptIndex;
+
+/* indexes and validates an image: magic, version, bounds, checksums, zero padding, the required sections and
+ * every section's length against the shapes in the legacy header.  Returns 0, or −1 with one line in ix->err. */
+int ckpt_index(const void* buf, size_t len, CkptIndex* ix);
+uint64_t ckpt_fnv1a64(const void* p, size_t n);
+uint32_t ckpt_rd32(const uint8_t* p);
+uint64_t ckpt_rd64(const uint8_t* p);
+
+#endif

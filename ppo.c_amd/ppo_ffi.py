@@ -217,6 +217,10 @@ _SIGS = {
     "ppo_env_reset_device": (C.c_int, [C.c_int, _P, _P, C.c_int, C.c_int, C.c_ulonglong]),
     "ppo_env_step_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_ulonglong, C.c_ulonglong]),
+    "ppo_save_state": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "ppo_load_state": (C.POINTER(PPO), [C.c_char_p, C.c_char_p, C.c_int]),
+    "ppo_state_hash": (C.c_ulonglong, [_P, C.c_int]),
+    "ppo_state_image": (C.c_int, [_P, C.c_int, _P, C.c_long]),
     "ppo_prof_enable": (None, [C.c_int]),
     "ppo_prof_reset": (None, []),
     "ppo_prof_kernel_events": (None, [C.c_int]),
