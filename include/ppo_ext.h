@@ -302,7 +302,7 @@ int    ppo_categorical_sample_device(const float* d_logits, int m, int A, unsign
  * inverts its own CDF as dist 1 does; d = 0 is dist 1's draw, so D = 1 samples what dist 1 samples bit for bit.  The
  * stored log-prob is the joint lp.  The deterministic action is the per-component argmax, lowest index on ties.
  * While it is on: ppo_get_action_dist returns 2; everything said of dist 1 above holds — the multi-launch update loop
- * with the multi-discrete head (one launch, csrc/multidiscrete.hip), the KL monitor on the joint lp, ppo_read_stats
+ * with the multi-discrete head (one launch, csrc/discrete.hip), the KL monitor on the joint lp, ppo_read_stats
  * out[4] = the mean joint row entropy, ppo_rollout_device / ppo_eval_device / ppo_fill_synthetic / the open rollout /
  * ppo_act_device, the options it composes with, the entry points that stay Gaussian, train_ppo_epoch / eval_ppo ending
  * the process.  The synthetic environment reads component d = j mod D for observation element j as
@@ -354,7 +354,7 @@ int    ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, cons
  * a NULL ppo), ppo_action_mask_buffer the device store — NULL while masking is off — for callers who lay the buffer
  * themselves.  TrajectoryBuffer and every reference layout are untouched; the setting and the store are not part of a
  * checkpoint (save_ppo's; ppo_save_state keeps it) and not hashed by ppo_param_hash, and no collective is added under data parallelism.
- * While it is on, ppo_update's policy step runs the masked head (one launch, csrc/masked.hip) for both discrete
+ * While it is on, ppo_update's policy step runs the masked head (one launch, csrc/discrete.hip) for both discrete
  * distributions: minibatch row i reads the mask of its buffer row in place, through the row indices the minibatch
  * gather already produces — no gather launch is added — and the KL monitor takes the masked joint lp; everything else
  * in the step and the options it composes with are unchanged.  With masking off, or on with full masks, every

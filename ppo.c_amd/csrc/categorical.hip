@@ -1,7 +1,10 @@
-// categorical.hip — the categorical policy over A discrete choices (ppo_set_action_dist(ppo, 1); no counterpart
-// in the reference): the clipped-surrogate head of a policy minibatch step, the inverse-CDF sampler of rollouts,
-// evaluation and ppo_fill_synthetic, and the greedy action of deterministic evaluation.  μ's A outputs are the
-// logits.  The per-row arithmetic is ppo_math.h's cat_* atoms and ppo::surrogate, called, never restated.
+// categorical.hip — the head of the categorical policy over A discrete choices (ppo_set_action_dist(ppo, 1); no
+// counterpart in the reference): the clipped surrogate of a policy minibatch step while no action mask is on.  μ's A
+// outputs are the logits.  The per-row arithmetic is ppo_math.h's cat_* atoms and ppo::surrogate, called, never
+// restated.  The policy is discrete.hip's at D = 1, offsets {0, A}, bit for bit, and its sampler, its greedy action
+// and its masked head are discrete.hip's kernels.  This head stays as the dist-1 fast path: it keeps a row in
+// registers and moves it between lanes by DPP, where discrete.hip's tile head walks components through LDS, and the
+// two have not been timed against each other at D = 1.
 //
 // HEAD.  One launch per policy step.  It reads the logits [m, A] once and writes their gradient [m, A]: the
 // traffic is 2·m·A·4 bytes plus 12 bytes per row (advantage, old log-prob, column 0 of the stored action — of
@@ -23,45 +26,15 @@
 // word.  That last step IS order-dependent (the workgroups arrive in any order), exactly as the Gaussian head's
 // loss word is today; neither word feeds back into a parameter.
 // log σ is not used and no gradient is written to it.
-//
-// SAMPLER.  One lane per row, one uniform per row: u = u01(philox(counter, offset, key).x) ∈ (0, 1],
-// c_k = Σ_{j<=k} e_j in fp32 with k ascending, thr = u·c_{A−1}, a = min{k : thr <= c_k}, clamped to A − 1;
-// log-prob = cat_log_prob of a with s = c_{A−1}.  The action row is written as A floats: column 0 the index as
-// an exact float, columns 1 … A−1 zero.  The streams it reads are listed in rng.h's table.
 #include "dev.h"
 #include "ppo_math.h"
-#include "rng.h"
 
 #include <cmath>
 
 namespace {
 
-using namespace ppo_rng;
-
 constexpr int TPB = 256;
 constexpr int WAVES = TPB / 64;
-
-// wave max on DPP moves, the tree of dev.h's row_sum16 / wave_sum64: every lane gets the wave's value
-__device__ __forceinline__ float wave_max64(float v) {
-    v = fmaxf(v, ppo::dpp_mov<0xB1>(v));
-    v = fmaxf(v, ppo::dpp_mov<0x4E>(v));
-    v = fmaxf(v, ppo::dpp_mov<0x141>(v));
-    v = fmaxf(v, ppo::dpp_mov<0x140>(v));
-    return fmaxf(fmaxf(ppo::lane_value(v, 0), ppo::lane_value(v, 16)),
-                 fmaxf(ppo::lane_value(v, 32), ppo::lane_value(v, 48)));
-}
-
-// the workgroup's sum of one value per wave-leader (lanes with (tid & 63) == 0 pass theirs), to thread 0
-__device__ __forceinline__ float block_sum_waves(float wave_total, float* red) {
-    const int tid = threadIdx.x;
-    if ((tid & 63) == 0) red[tid >> 6] = wave_total;
-    __syncthreads();
-    float r = 0.f;
-    if (tid == 0)
-        for (int w = 0; w < WAVES; ++w) r += red[w];
-    __syncthreads();
-    return r;
-}
 
 // ------------------------------------------------------------------ head, A <= 32: one lane per row
 template <int AMAX>
@@ -123,8 +96,8 @@ __global__ __launch_bounds__(TPB) void cat_head_lane_kernel(
         grad[base + e] = tile[row * pitch + k];
     }
     const float ws = ppo::wave_sum64(sur), wh = ppo::wave_sum64(H);
-    const float bs = block_sum_waves(ws, red);
-    const float bh = block_sum_waves(wh, red);
+    const float bs = ppo::block_sum_waves<WAVES>(ws, red);
+    const float bh = ppo::block_sum_waves<WAVES>(wh, red);
     if (tid == 0) {
         if (d_loss_accum) atomicAdd(d_loss_accum, -bs / m - ent_coeff * bh / m);
         if (d_ent_accum) atomicAdd(d_ent_accum, bh);
@@ -151,7 +124,7 @@ __global__ __launch_bounds__(TPB) void cat_head_wave_kernel(
             z[q] = k < A ? zr[k] : -INFINITY;
             M = fmaxf(M, z[q]);
         }
-        M = wave_max64(M);
+        M = ppo::wave_max64(M);
         float s = 0.f, t = 0.f;
 #pragma unroll
         for (int q = 0; q < K; ++q)
@@ -181,50 +154,12 @@ __global__ __launch_bounds__(TPB) void cat_head_wave_kernel(
         }
     }
     // every lane of a wave holds the same sur / H: the wave's total is its row's value
-    const float bs = block_sum_waves(sur, red);
-    const float bh = block_sum_waves(H, red);
+    const float bs = ppo::block_sum_waves<WAVES>(sur, red);
+    const float bh = ppo::block_sum_waves<WAVES>(H, red);
     if (tid == 0) {
         if (d_loss_accum) atomicAdd(d_loss_accum, -bs / m - ent_coeff * bh / m);
         if (d_ent_accum) atomicAdd(d_ent_accum, bh);
     }
-}
-
-// ------------------------------------------------------------------ sampler / greedy action
-// row e of `logits`; the action and log-prob go to row rows[e] (NULL: e)
-__global__ void cat_sample_kernel(const float* __restrict__ logits, const int* __restrict__ rows,
-                                  float* __restrict__ action, float* __restrict__ logprob, int m, int A,
-                                  uint64_t key, uint64_t offset) {
-    const long e = (long)blockIdx.x * TPB + threadIdx.x;
-    if (e >= m) return;
-    const float* z = logits + e * A;
-    const float M = ppo::cat_row_max(z, A);
-    const float s = ppo::cat_row_sum(z, A, M, nullptr);
-    const float thr = u01(philox((uint64_t)e, offset, key).x) * s;
-    int a = A - 1;                                   // the clamp: u <= 1 gives thr <= c_{A−1} already
-    float c = 0.f;
-    for (int k = 0; k < A; ++k) {
-        c += ppo::cat_exp(z[k], M);
-        if (thr <= c) { a = k; break; }
-    }
-    const long row = rows ? rows[e] : e;
-    float* ar = action + row * A;
-    ar[0] = (float)a;
-    for (int k = 1; k < A; ++k) ar[k] = 0.f;
-    if (logprob) logprob[row] = ppo::cat_log_prob(z[a], M, logf(s));
-}
-
-// argmax_k z_k, the lowest index on ties; action [m, A] compact
-__global__ void cat_argmax_kernel(const float* __restrict__ logits, float* __restrict__ action, int m, int A) {
-    const long e = (long)blockIdx.x * TPB + threadIdx.x;
-    if (e >= m) return;
-    const float* z = logits + e * A;
-    int a = 0;
-    float best = z[0];
-    for (int k = 1; k < A; ++k)
-        if (z[k] > best) { best = z[k]; a = k; }
-    float* ar = action + e * A;
-    ar[0] = (float)a;
-    for (int k = 1; k < A; ++k) ar[k] = 0.f;
 }
 
 }  // namespace
@@ -257,29 +192,6 @@ void phip_cat_head(const float* logits, const float* action, const float* adv, c
     else CAT_WAVE(64);
 #undef CAT_LANE
 #undef CAT_WAVE
-    PPO_LAUNCH_CHECK();
-}
-
-void phip_cat_sample(const float* logits, const int* rows, float* action, float* logprob, int m, int A, uint64_t key,
-                     uint64_t offset) {
-    if (m <= 0) return;
-    PPO_REQUIRE(A >= 2 && logits && action, "phip_cat_sample: operands");
-    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * m * (2.0 * A + 1));
-    hipLaunchKernelGGL(cat_sample_kernel, dim3(ppo_divup(m, TPB)), dim3(TPB), 0, ppo::stream(), logits, rows, action,
-                       logprob, m, A, key, offset);
-    PPO_LAUNCH_CHECK();
-}
-
-void phip_cat_sample_rows(const float* logits, const int* rows, float* action, float* logprob, int E, int A,
-                          uint64_t key, uint64_t step) {
-    phip_cat_sample(logits, rows, action, logprob, E, A, key, kNoise + step);
-}
-
-void phip_cat_argmax(const float* logits, float* action, int m, int A) {
-    if (m <= 0) return;
-    PPO_REQUIRE(A >= 2 && logits && action, "phip_cat_argmax: operands");
-    ppo::ProfScope ps(PPO_K_OTHER, 4.0 * m * (2.0 * A));
-    hipLaunchKernelGGL(cat_argmax_kernel, dim3(ppo_divup(m, TPB)), dim3(TPB), 0, ppo::stream(), logits, action, m, A);
     PPO_LAUNCH_CHECK();
 }
 

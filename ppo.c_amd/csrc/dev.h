@@ -82,6 +82,27 @@ __device__ __forceinline__ float wave_sum64(float v) {
     v = row_sum16(v);
     return ((lane_value(v, 0) + lane_value(v, 16)) + lane_value(v, 32)) + lane_value(v, 48);
 }
+// wave max on the same DPP tree: every lane gets the wave's value
+__device__ __forceinline__ float wave_max64(float v) {
+    v = fmaxf(v, dpp_mov<0xB1>(v));
+    v = fmaxf(v, dpp_mov<0x4E>(v));
+    v = fmaxf(v, dpp_mov<0x141>(v));
+    v = fmaxf(v, dpp_mov<0x140>(v));
+    return fmaxf(fmaxf(lane_value(v, 0), lane_value(v, 16)), fmaxf(lane_value(v, 32), lane_value(v, 48)));
+}
+// the sum over a workgroup of WAVES waves of one value per wave (its lanes with (tid & 63) == 0 pass it), wave
+// ascending, to thread 0; red: WAVES floats of LDS.  Two barriers: every thread of the workgroup calls it
+template <int WAVES>
+__device__ __forceinline__ float block_sum_waves(float wave_total, float* red) {
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) red[tid >> 6] = wave_total;
+    __syncthreads();
+    float r = 0.f;
+    if (tid == 0)
+        for (int w = 0; w < WAVES; ++w) r += red[w];
+    __syncthreads();
+    return r;
+}
 
 }  // namespace ppo
 

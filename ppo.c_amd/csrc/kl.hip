@@ -6,8 +6,8 @@
 //           — or, with a categorical policy (dist 1), cat_log_prob_row of the index in the action's column 0
 //           under the logits μ_i; or, with a multi-discrete policy (dist 2), md_log_prob_row: the joint log-prob
 //           of the indices in columns 0 … D−1; nothing else differs.  With action masking (mask not NULL; dist 2,
-//           the categorical policy as nvec = {A}): md_log_prob_row_masked under the W words at mask[rows[i]·W]
-//           (rows NULL: i) — the masked head's lp; mask NULL is the unmasked path and its bits
+//           the categorical policy as nvec = {A}): md_log_prob_row under the W words at mask[rows[i]·W] (rows
+//           NULL: i) — the masked head's lp; mask NULL is the unmasked path and its bits
 //   x_i   = (double)lp_i − (double)old_lp_i
 //   kl    = Σ (expm1(x_i) − x_i) / rows          (Schulman's k3 estimator; double: (r − 1) − log r cancels in fp32)
 //   frac  = Σ 1[|(float)exp(x_i) − 1| > ε] / rows
@@ -71,9 +71,9 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
     double kl = 0.0, cnt = 0.0;
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < m; i += (long)gridDim.x * TPB) {
         const int W = (A + 31) / 32;
-        const float lp = mask      ? ppo::md_log_prob_row_masked(mu + i * A, md_off, D, action + i * A,
-                                                                 mask + (rows ? (long)rows[i] : i) * W)
-                         : dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A)
+        const float lp = mask      ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A,
+                                                          ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
+                         : dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A, ppo::NoMask{})
                          : dist  ? ppo::cat_log_prob_row(mu + i * A, A, ppo::cat_index(action[i * A], A))
                                  : ppo::log_prob_row(mu + i * A, log_std, action + i * A, A);
         const double x = (double)lp - (double)old_lp[i];

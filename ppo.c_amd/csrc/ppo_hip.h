@@ -281,7 +281,7 @@ void phip_policy_head(const float* mu, const float* log_std, const float* action
                       float* grad_mu, float* grad_log_std, float* d_loss_accum,
                       int ls_zeroed);
 
-/* ---------------- categorical policy (categorical.hip) ---------------- */
+/* ---------------- categorical policy: the unmasked head (categorical.hip) ---------------- */
 #define PHIP_CAT_MAX_A 4096
 /* the clipped-surrogate head over logits [m, A] (2 <= A <= PHIP_CAT_MAX_A), the chosen index in column 0 of
  * action [m, A]: grad [m, A] = ∂loss/∂logits written, lp_out / ent_out (may be NULL) [m] = the row's log-prob /
@@ -290,54 +290,35 @@ void phip_policy_head(const float* mu, const float* log_std, const float* action
 void phip_cat_head(const float* logits, const float* action, const float* adv, const float* old_lp, int m, int A,
                    float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out, float* d_loss_accum,
                    float* d_ent_accum);
-/* inverse-CDF sample of row e from u01(philox(e, offset, key).x); the action row (index, 0, …, 0) and the
- * log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
-void phip_cat_sample(const float* logits, const int* rows, float* action, float* logprob, int m, int A, uint64_t key,
-                     uint64_t offset);
-/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
-void phip_cat_sample_rows(const float* logits, const int* rows, float* action, float* logprob, int E, int A,
-                          uint64_t key, uint64_t step);
-/* action[e] ← (argmax_k logits[e, k], 0, …, 0), the lowest index on ties */
-void phip_cat_argmax(const float* logits, float* action, int m, int A);
 
-/* ---------------- multi-discrete policy (multidiscrete.hip) ---------------- */
+/* ---------------- discrete policies, masked or not: tile head, sampler, greedy action (discrete.hip) ---------- */
 #define PHIP_MD_MAX_D 256
 /* D softmaxes side by side over logits [m, A]: component d owns [d_off[d], d_off[d + 1]), d_off (device, D + 1
  * ints) ascending from 0 to A, every width >= 2; max_n the widest component (the launcher's choice of form).  The
- * chosen indices are columns 0 … D−1 of action [m, A].  Outputs as phip_cat_head's, lp / ent the joint ones. */
-void phip_md_head(const float* logits, const float* action, const float* adv, const float* old_lp, int m, int A,
-                  const int* d_off, int D, int max_n, float epsilon, float ent_coeff, float* grad, float* lp_out,
-                  float* ent_out, float* d_loss_accum, float* d_ent_accum);
-/* component d of row e from u01 of word d & 3 of philox(e | (d >> 2) << 32, offset, key); the action row (indices
- * in columns 0 … D−1, zeros after) and the joint log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
-void phip_md_sample(const float* logits, const int* rows, const int* d_off, float* action, float* logprob, int m,
-                    int A, int D, uint64_t key, uint64_t offset);
-void phip_md_sample_rows(const float* logits, const int* rows, const int* d_off, float* action, float* logprob, int E,
-                         int A, int D, uint64_t key, uint64_t step);
-/* action[e] ← the per-component argmax (lowest index on ties) in columns 0 … D−1, zeros after */
-void phip_md_argmax(const float* logits, const int* d_off, float* action, int m, int A, int D);
-
-/* ---------------- action masking (masked.hip) ---------------- */
-/* A row's mask is W = (A + 31) / 32 words, bit k & 31 of word k >> 5 = logit column k allowed (ppo_math.h "Action
- * masking": a component with no stored bit set is fully allowed; the head also allows the chosen column).  The
- * categorical policy runs these as D = 1, d_off = {0, A}.
- * phip_md_head under masks: minibatch row i reads its W words at mask[rows[i]·W] (rows NULL: i).  A full mask gives
- * phip_md_head's lp, entropy and gradient bits; a masked column's gradient is +0 and its logit never read into
- * arithmetic. */
-void phip_masked_head(const float* logits, const float* action, const float* adv, const float* old_lp,
-                      const uint32_t* mask, const int* rows, int m, int A, const int* d_off, int D, int max_n,
-                      float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out, float* d_loss_accum,
-                      float* d_ent_accum);
-/* phip_md_sample over the allowed columns of the dense mask [m, W] (row e of the mask for row e of the logits);
- * mask_out (may be NULL): row rows[e]'s W words ← the mask sampled under.  A full mask draws phip_md_sample's bits. */
-void phip_masked_sample(const float* logits, const uint32_t* mask, const int* rows, const int* d_off, float* action,
-                        float* logprob, uint32_t* mask_out, int m, int A, int D, uint64_t key, uint64_t offset);
-void phip_masked_sample_rows(const float* logits, const uint32_t* mask, const int* rows, const int* d_off,
-                             float* action, float* logprob, uint32_t* mask_out, int E, int A, int D, uint64_t key,
-                             uint64_t step);
-/* per component the lowest allowed index holding the maximum over the allowed columns; mask dense [m, W] */
-void phip_masked_argmax(const float* logits, const uint32_t* mask, const int* d_off, float* action, int m, int A,
-                        int D);
+ * chosen indices are columns 0 … D−1 of action [m, A].  The categorical policy is D = 1, d_off = {0, A}.
+ * A row's mask is W = (A + 31) / 32 words, bit k & 31 of word k >> 5 = logit column k allowed (ppo_math.h "Action
+ * masking": a component with no stored bit set is fully allowed; the head also allows the chosen column).  mask NULL
+ * selects the unmasked kernels; a full mask gives their bits.
+ * The head: outputs as phip_cat_head's, lp / ent the joint ones.  With a mask, minibatch row i reads its W words at
+ * mask[rows[i]·W] (rows NULL: i; unread without a mask); a masked column's gradient is +0 and its logit never read
+ * into arithmetic. */
+void phip_disc_head(const float* logits, const float* action, const float* adv, const float* old_lp,
+                    const uint32_t* mask, const int* rows, int m, int A, const int* d_off, int D, int max_n,
+                    float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out, float* d_loss_accum,
+                    float* d_ent_accum);
+/* component d of row e from u01 of word d & 3 of philox(e | (d >> 2) << 32, offset, key), inverse CDF over the
+ * allowed columns of the dense mask [m, W] (row e of the mask for row e of the logits; NULL: every column); the
+ * action row (indices in columns 0 … D−1, zeros after) and the joint log-prob (may be NULL) go to row rows[e] (rows
+ * NULL: e); mask_out (may be NULL; needs a mask): row rows[e]'s W words ← the mask sampled under */
+void phip_disc_sample(const float* logits, const uint32_t* mask, const int* rows, const int* d_off, float* action,
+                      float* logprob, uint32_t* mask_out, int m, int A, int D, uint64_t key, uint64_t offset);
+/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
+void phip_disc_sample_rows(const float* logits, const uint32_t* mask, const int* rows, const int* d_off, float* action,
+                           float* logprob, uint32_t* mask_out, int E, int A, int D, uint64_t key, uint64_t step);
+/* action[e] ← per component the lowest allowed index holding the maximum over the allowed columns, in columns
+ * 0 … D−1, zeros after; mask dense [m, W] (NULL: every column) */
+void phip_disc_argmax(const float* logits, const uint32_t* mask, const int* d_off, float* action, int m, int A,
+                      int D);
 /* mask[rows[e]·W + j] ← all ones for e < E: the rows a step laid with the unmasked sampler */
 void phip_mask_fill_rows(uint32_t* mask, const int* rows, int E, int A);
 
@@ -470,7 +451,7 @@ typedef struct {
  * 2 = multi-discrete — md_off (device, D + 1 offsets) splits the logits, columns 0 … D−1 hold the indices, lp is
  * the joint one (md_off and D are unread otherwise).  mask (NULL: today's path and bits; needs dist 2, the
  * categorical policy passing the offsets {0, A}): minibatch row i reads its (A + 31) / 32 words at mask[rows[i]·W]
- * (rows NULL: i) and lp is the masked joint log-prob (ppo_math.h md_log_prob_row_masked) */
+ * (rows NULL: i) and lp is the masked joint log-prob (ppo_math.h md_log_prob_row over MaskRow) */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
                     const int* md_off, int D, const uint32_t* mask, const int* rows);

@@ -75,16 +75,30 @@ __device__ __forceinline__ float cat_grad(float g, bool chosen, float z, float M
     const float p = cat_exp(z, M) / s;
     return g * ((chosen ? 1.f : 0.f) - p) + cm * p * (((z - M) - ls) + H);
 }
-// one thread walks a whole row in index order (the sampler, the KL monitor, evaluation): M, s and — when t is
-// not NULL — t
-__device__ __forceinline__ float cat_row_max(const float* z, int A) {
-    float M = z[0];
-    for (int k = 1; k < A; ++k) M = fmaxf(M, z[k]);
+// one thread walks z[0 … n) in index order under a mask (the sampler, the KL monitor, evaluation, a one-lane
+// component of the head): M, s and — when t is not NULL — t over the columns mk allows.  M starts from the first
+// allowed logit and then takes fmaxf; s and t add k ascending.  NoMask allows every column (and is its own
+// per-component view, see "Action masking" below): M = z[0], then fmaxf for k = 1 …, the unmasked sequence.
+struct NoMask {
+    __device__ __forceinline__ bool allowed(int) const { return true; }
+    __device__ __forceinline__ NoMask component(int, int, int) const { return *this; }
+};
+template <class Mask = NoMask>
+__device__ __forceinline__ float cat_row_max(const float* z, int n, const Mask& mk = Mask()) {
+    bool first = true;
+    float M = 0.f;
+    for (int k = 0; k < n; ++k) {
+        if (!mk.allowed(k)) continue;
+        M = first ? z[k] : fmaxf(M, z[k]);
+        first = false;
+    }
     return M;
 }
-__device__ __forceinline__ float cat_row_sum(const float* z, int A, float M, float* t) {
+template <class Mask = NoMask>
+__device__ __forceinline__ float cat_row_sum(const float* z, int n, float M, float* t, const Mask& mk = Mask()) {
     float s = 0.f, tt = 0.f;
-    for (int k = 0; k < A; ++k) {
+    for (int k = 0; k < n; ++k) {
+        if (!mk.allowed(k)) continue;
         const float e = cat_exp(z[k], M);
         s += e;
         tt += e * (z[k] - M);
@@ -117,29 +131,34 @@ __device__ __forceinline__ float cat_log_prob_row(const float* z, int A, int a) 
 // n_d <= 32 is summed k ascending by one lane (md_component); a wider one may combine lane partials by the kernel's
 // fixed tree.  D = 1 is the categorical policy bit for bit.  tests/multidiscrete_ref.py restates it.
 struct MdComp { float M, s, ls, lp, H; };
-// one thread walks component z[0 … n) in index order; a the chosen index inside it
-__device__ __forceinline__ MdComp md_component(const float* z, int n, int a) {
+// one thread walks component z[0 … n) in index order under its effective mask mk; a the chosen index inside it
+template <class Mask>
+__device__ __forceinline__ MdComp md_component(const float* z, int n, int a, const Mask& mk) {
     MdComp c;
-    c.M = cat_row_max(z, n);
+    c.M = cat_row_max(z, n, mk);
     float t;
-    c.s = cat_row_sum(z, n, c.M, &t);
+    c.s = cat_row_sum(z, n, c.M, &t, mk);
     c.ls = logf(c.s);
     c.lp = cat_log_prob(z[a], c.M, c.ls);
     c.H = cat_entropy(c.ls, t, c.s);
     return c;
 }
-// the joint log-prob of one row by one thread (the KL monitor): cat_log_prob_row per segment, d ascending
-__device__ __forceinline__ float md_log_prob_row(const float* z, const int* off, int D, const float* action) {
+// the joint log-prob of one row by one thread (the KL monitor): md_component's lp per segment, d ascending; rm the
+// row's mask (NoMask, or MaskRow over its W words)
+template <class RowMask>
+__device__ __forceinline__ float md_log_prob_row(const float* z, const int* off, int D, const float* action,
+                                                 const RowMask& rm) {
     float lp = 0.f;
     for (int d = 0; d < D; ++d) {
         const int o = off[d], n = off[d + 1] - o;
-        const float l = cat_log_prob_row(z + o, n, cat_index(action[d], n));
+        const int a = cat_index(action[d], n);
+        const float l = md_component(z + o, n, a, rm.component(o, n, a)).lp;
         lp = d == 0 ? l : lp + l;
     }
     return lp;
 }
 
-// ---- Action masking (ppo_set_action_mask; no counterpart in the reference; csrc/masked.hip): a row of A logits
+// ---- Action masking (ppo_set_action_mask; no counterpart in the reference; csrc/discrete.hip): a row of A logits
 // carries W = (A + 31) / 32 words, bit k & 31 of word k >> 5 set = column k allowed, k counted across the
 // components; bits at k >= A are ignored.  The EFFECTIVE mask of component d, columns [o_d, o_d + n_d):
 //     1. its stored bits;
@@ -150,10 +169,11 @@ __device__ __forceinline__ float md_log_prob_row(const float* z, const int* off,
 //     ls_d = logf(s_d),  lp_d = cat_log_prob(z_{o_d + a_d}, M_d, ls_d),  H_d = cat_entropy(ls_d, t_d, s_d)
 // A masked column enters no max and no sum, its gradient element is +0 and its logit is never read into arithmetic
 // (a NaN, an infinity or 1e30 there changes no output bit).  Joint lp and H, the surrogate, cat_grad on the allowed
-// columns and the loss are the multi-discrete policy's.  With every bit set each function below gives its unmasked
-// counterpart's bits (md_component, md_log_prob_row).  The sampler inverts the CDF over the allowed columns (the
-// fallback is the last allowed one); the greedy action is the lowest allowed index holding the allowed maximum.
-// tests/masked_ref.py restates it.
+// columns and the loss are the multi-discrete policy's.  There is one definition: cat_row_max, cat_row_sum,
+// md_component and md_log_prob_row above take the mask as a type, MaskComp here or NoMask; with every bit set
+// MaskComp skips nothing, which is NoMask's sequence and its bits.  The sampler inverts the CDF over the allowed
+// columns (the fallback is the last allowed one); the greedy action is the lowest allowed index holding the allowed
+// maximum.  tests/masked_ref.py restates it.
 __device__ __forceinline__ bool mask_bit(const uint32_t* w, int k) { return (w[k >> 5] >> (k & 31)) & 1u; }
 // any stored bit of columns [o, o + n)
 __device__ __forceinline__ bool mask_any(const uint32_t* w, int o, int n) {
@@ -198,50 +218,16 @@ __device__ __forceinline__ MaskComp mask_component(const uint32_t* w, int o, int
     }
     return mc;
 }
-// one thread walks component z[0 … n) under its effective mask; a the chosen index inside it.  The masked joint
-// log-prob of the head's one-lane form and of the KL monitor is this function's lp.
-__device__ __forceinline__ float masked_row_max(const float* z, int n, const MaskComp& mc) {
-    bool first = true;
-    float M = 0.f;
-    for (int k = 0; k < n; ++k) {
-        if (!mc.allowed(k)) continue;
-        M = first ? z[k] : fmaxf(M, z[k]);           // cat_row_max's sequence over the allowed columns
-        first = false;
-    }
-    return M;
-}
-__device__ __forceinline__ float masked_row_sum(const float* z, int n, float M, const MaskComp& mc, float* t) {
-    float s = 0.f, tt = 0.f;
-    for (int k = 0; k < n; ++k) {
-        if (!mc.allowed(k)) continue;
-        const float e = cat_exp(z[k], M);
-        s += e;
-        tt += e * (z[k] - M);
-    }
-    if (t) *t = tt;
-    return s;
-}
-__device__ __forceinline__ MdComp md_component_masked(const float* z, int n, int a, const MaskComp& mc) {
-    MdComp c;
-    c.M = masked_row_max(z, n, mc);
-    float t;
-    c.s = masked_row_sum(z, n, c.M, mc, &t);
-    c.ls = logf(c.s);
-    c.lp = cat_log_prob(z[a], c.M, c.ls);
-    c.H = cat_entropy(c.ls, t, c.s);
-    return c;
-}
-// the masked joint log-prob of one row by one thread (the KL monitor): w the row's W words
-__device__ __forceinline__ float md_log_prob_row_masked(const float* z, const int* off, int D, const float* action,
-                                                        const uint32_t* w) {
-    float lp = 0.f;
-    for (int d = 0; d < D; ++d) {
-        const int o = off[d], n = off[d + 1] - o;
-        const int a = cat_index(action[d], n);
-        const float l = md_component_masked(z + o, n, a, mask_component(w, o, n, a)).lp;
-        lp = d == 0 ? l : lp + l;
-    }
-    return lp;
+// a row's W words as the source of its components' effective masks (NoMask is the unmasked counterpart)
+struct MaskRow {
+    const uint32_t* w;
+    __device__ __forceinline__ MaskComp component(int o, int n, int a) const { return mask_component(w, o, n, a); }
+};
+// the row mask of a kernel instantiated with or without masking; w is unread when MASKED is false
+template <bool MASKED>
+__device__ __forceinline__ auto mask_row(const uint32_t* w) {
+    if constexpr (MASKED) return MaskRow{w};
+    else return NoMask{};
 }
 
 // ---- Gaussian entropy (policy.cu:171-193): this constant, then += log σ_j for j ascending, at the call site

@@ -21,20 +21,20 @@
 //     env ε          same key                           counter e·S + j   offset kEnv + 2g + 1     .x .y   N(0, 1)
 //     reset          same key                           counter e (Pendulum: .x θ, .y θ̇) or e·S + j (.x)   offset kReset + g
 //   CartPole-v1 (env_kind 2): first reset and reset at counter e, .x .y .z .w → x, ẋ, θ, θ̇ ~ U(−0.05, 0.05)
-//   categorical policy (ppo_set_action_dist 1; categorical.hip; tests/categorical_ref.py restates these rows):
+//   categorical policy (ppo_set_action_dist 1; discrete.hip at D = 1; tests/categorical_ref.py restates these rows):
 //     ppo_fill_synthetic      action noise   key s0 ^ 5   counter i (row)   offset 0          .x   u01, inverse CDF
 //     ppo_rollout_device / ppo_eval_device
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e   offset kNoise + g   .x   u01, inverse CDF
 //     ppo_categorical_sample_device(key, offset)          counter i (row)   offset `offset`   .x   u01, inverse CDF
-//   multi-discrete policy (ppo_set_action_multidiscrete; multidiscrete.hip; tests/multidiscrete_ref.py restates
+//   multi-discrete policy (ppo_set_action_multidiscrete; discrete.hip; tests/multidiscrete_ref.py restates
 //   these rows): one uniform per (row, component d); key and offset are the categorical rows' above at each call
 //   site, the counter's high word is d >> 2 and the word is d & 3 — d = 0 is the categorical draw
 //     ppo_fill_synthetic      action noise   key s0 ^ 5   counter i | (d >> 2) << 32   offset 0   word d & 3 (.x .y .z .w)
 //     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e | (d >> 2) << 32   offset kNoise + g   word d & 3
 //     ppo_multidiscrete_sample_device(key, offset)        counter i | (d >> 2) << 32   offset `offset`   word d & 3
-//   action masking (ppo_set_action_mask; masked.hip): the masked sampler reads the multi-discrete rows above, word
-//   for word (the categorical policy as D = 1) — ppo_rollout_act_masked / ppo_act_device_masked the policy-noise
+//   action masking (ppo_set_action_mask; discrete.hip): the same sampler under a mask reads the multi-discrete rows
+//   above, word for word (the categorical policy as D = 1) — ppo_rollout_act_masked / ppo_act_device_masked the policy-noise
 //   row, ppo_masked_sample_device(key, offset) the last one; only the CDF it inverts differs
 #pragma once
 

@@ -103,7 +103,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->kl);
     phip_free(d->vclip_counts);
     phip_free(d->cat_ent);
-    phip_free(d->md_off);
+    phip_free(d->md_off); phip_free(d->cat_off);
     phip_free(d->obs_run); phip_free(d->obs_m); phip_free(d->obs_shadow); phip_free(d->obs_next);
     phip_free(d->obs_batch); phip_free(d->obs_all); phip_free(d->obs_counts);
     phip_free(d->rew_run); phip_free(d->rew_scale); phip_free(d->rew_shadow); phip_free(d->rew_batch);
@@ -114,7 +114,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ev_reward); phip_free(d->ev_rows); phip_free(d->ev_term); phip_free(d->ev_trunc);
     phip_free(d->ev_cont); phip_free(d->ev_agg);
     phip_free(d->ext_obs); phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
-    phip_free(d->mask); phip_free(d->cat_off);
+    phip_free(d->mask);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -205,27 +205,17 @@ static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
 /* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
 static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
 
-/* action masking: on, the words of one row, and the offsets / component count / widest component the masked kernels
- * run the discrete policy with (the categorical one as nvec = {A}) */
-static int mask_on(const PPODev* d) { return cat_on(d) && d->mask_on && d->mask; }
-static int mask_words(int A) { return (A + 31) / 32; }
+/* the shape the discrete kernels (discrete.hip) run either policy with: the offsets, the component count and the
+ * widest component (the categorical policy as nvec = {A}) */
 static const int* disc_off(const PPODev* d) { return md_on(d) ? d->md_off : d->cat_off; }
 static int disc_D(const PPODev* d) { return md_on(d) ? d->md_D : 1; }
 static int disc_max_n(const PPODev* d, int A) { return md_on(d) ? d->md_max_n : A; }
+/* action masking: on, and the words of one row */
+static int mask_on(const PPODev* d) { return cat_on(d) && d->mask_on && d->mask; }
+static int mask_words(int A) { return (A + 31) / 32; }
 /* rows [0, n) of the store ← full masks: what an unmasked sampler lays */
 static void mask_fill_full(PPODev* d, long n, int A) {
     if (mask_on(d)) phip_memset(d->mask, 0xFF, sizeof(uint32_t) * (size_t)n * (size_t)mask_words(A));
-}
-
-/* the discrete policies' samplers and greedy action, one call per site */
-static void disc_sample_rows(const PPODev* d, const float* logits, const int* rows, float* action, float* logprob,
-                             int E, int A, uint64_t key, uint64_t step) {
-    if (md_on(d)) phip_md_sample_rows(logits, rows, d->md_off, action, logprob, E, A, d->md_D, key, step);
-    else phip_cat_sample_rows(logits, rows, action, logprob, E, A, key, step);
-}
-static void disc_argmax(const PPODev* d, const float* logits, float* action, int m, int A) {
-    if (md_on(d)) phip_md_argmax(logits, d->md_off, action, m, A, d->md_D);
-    else phip_cat_argmax(logits, action, m, A);
 }
 
 /* the running triple and its affine pair (the identity until something is folded or set) */
@@ -794,7 +784,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const int* kl_off = kl_mask ? disc_off(d) : md_off(d);
     const int kl_D = kl_mask ? disc_D(d) : d->md_D;
     const uint32_t* kl_m = kl_mask ? d->mask : NULL;
-    if (cat) {             /* categorical policy: the plain branch with its own head (categorical.hip) */
+    if (cat) {             /* a discrete policy: the plain branch with its own head */
         /* log σ is unused: the head writes no gradient to it, and the entropy Adam below steps on the zeros
          * kept here, which leaves log σ bit-identical */
         /* ppo_set_action_dist and ppo_set_compute_dtype decline the pair; nn_set_compute_dtype on μ itself does not
@@ -807,16 +797,14 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         phip_memset(d->cat_ent, 0, sizeof(float));
         d->cat_rows = B;
         nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
-        if (mask_on(d))    /* either discrete policy under the stored masks, read in place through the row indices */
-            phip_masked_head(mu->d_output, act, adv, olp, d->mask, rows, B, A, disc_off(d), disc_D(d),
-                             disc_max_n(d, A), ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL, d->stats + 1,
-                             d->cat_ent);
-        else if (md_on(d))
-            phip_md_head(mu->d_output, act, adv, olp, B, A, d->md_off, d->md_D, d->md_max_n, ppo->epsilon,
-                         ppo->ent_coeff, d->gmu, NULL, NULL, d->stats + 1, d->cat_ent);
-        else
+        const int masked = mask_on(d);
+        if (!md_on(d) && !masked)     /* the categorical policy's register-resident head (categorical.hip) */
             phip_cat_head(mu->d_output, act, adv, olp, B, A, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
                           d->stats + 1, d->cat_ent);
+        else               /* the tile head; under masking the stored masks, read in place through the row indices */
+            phip_disc_head(mu->d_output, act, adv, olp, masked ? d->mask : NULL, masked ? rows : NULL, B, A,
+                           disc_off(d), disc_D(d), disc_max_n(d, A), ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
+                           d->stats + 1, d->cat_ent);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
     } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
@@ -1498,8 +1486,10 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         /* through the row list, as the rollout forwards: the same kernels over the same E rows */
         nn_forward_dev_rows(pol->mu, norm ? d->ev_obsn : d->ev_obs, d->ev_rows, NULL, E);
         const uint64_t step = (uint64_t)t;
-        if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d->ev_act, E, A);
-        else if (cat) disc_sample_rows(d, pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
+        if (cat && deterministic) phip_disc_argmax(pol->mu->d_output, NULL, disc_off(d), d->ev_act, E, A, disc_D(d));
+        else if (cat)
+            phip_disc_sample_rows(pol->mu->d_output, NULL, d->ev_rows, disc_off(d), d->ev_act, d->ev_lp, NULL, E, A,
+                                  disc_D(d), key, step);
         else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
@@ -1763,8 +1753,8 @@ int ppo_policy_head_device(int form, int m, int A, int n, int relu_in, float eps
     return 0;
 }
 
-/* the mask store: on — capacity × W words (allocated once: neither capacity nor A changes), every bit set, and the
- * categorical policy's offsets {0, A}; off — freed once nothing in flight reads it */
+/* the mask store: on — capacity × W words (allocated once: neither capacity nor A changes), every bit set; off —
+ * freed once nothing in flight reads it */
 static void mask_store(PPO* ppo, PPODev* d, int on) {
     const int A = ppo->buffer->action_size;
     phip_sync();
@@ -1777,11 +1767,6 @@ static void mask_store(PPO* ppo, PPODev* d, int on) {
     const size_t bytes = sizeof(uint32_t) * (size_t)ppo->buffer->capacity * (size_t)mask_words(A);
     if (!d->mask) d->mask = (uint32_t*)phip_malloc(bytes);
     phip_memset(d->mask, 0xFF, bytes);
-    if (!d->cat_off) {
-        const int off[2] = {0, A};
-        d->cat_off = (int*)phip_malloc(sizeof(off));
-        phip_h2d(d->cat_off, off, sizeof(off));
-    }
     d->mask_on = 1;
 }
 
@@ -1795,6 +1780,11 @@ int ppo_set_action_dist(void* vppo, int dist) {
         if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;       /* bf16 compute mode */
     }
     PPODev* d = dev_ws(ppo, 1);
+    if (dist == 1 && !d->cat_off) {                  /* the categorical policy as nvec = {A}: A never changes */
+        const int off[2] = {0, ppo->buffer->action_size};
+        d->cat_off = (int*)phip_malloc(sizeof(off));
+        phip_h2d(d->cat_off, off, sizeof(off));
+    }
     d->action_dist = dist;
     /* masking belongs to a discrete policy: off with it; under another one the columns mean something else: full
      * masks again */
@@ -1850,8 +1840,9 @@ int ppo_get_action_nvec(void* vppo, int* out, int cap) {
     return d->md_D;
 }
 
-/* the multi-discrete head and sampler on caller-supplied device arrays (test entries, as the categorical ones);
- * nvec is a host array, its offsets go to a device array kept here */
+/* the discrete head and sampler on caller-supplied device arrays (the test entries below: bad arguments return −1
+ * ahead of any device call, so nothing is recorded for ppo_last_error); nvec is a host array, its offsets go to a
+ * device array kept here */
 static int* md_test_offsets(const int* nvec, int D, int A, int* max_n) {
     static int* d_off = NULL;
     int off[PHIP_MD_MAX_D + 1];
@@ -1863,9 +1854,10 @@ static int* md_test_offsets(const int* nvec, int D, int A, int* max_n) {
     return d_off;
 }
 
-int ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, const float* d_adv,
-                                  const float* d_old_lp, int m, int A, const int* nvec, int D, float eps,
-                                  float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
+/* d_mask NULL: the unmasked head (d_rows unread) */
+static int disc_head_device(const float* d_logits, const float* d_action, const float* d_adv, const float* d_old_lp,
+                            const uint32_t* d_mask, const int* d_rows, int m, int A, const int* nvec, int D, float eps,
+                            float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
     static float* word = NULL;
     if (!d_logits || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || m <= 0 || isnan(eps))
         return -1;
@@ -1874,8 +1866,8 @@ int ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, 
     if (!d_off) return -1;
     if (!word) word = (float*)phip_malloc(4 * sizeof(float));
     phip_memset(word, 0, 4 * sizeof(float));
-    phip_md_head(d_logits, d_action, d_adv, d_old_lp, m, A, d_off, D, max_n, eps, ent_coeff, d_grad, d_lp, d_ent, word,
-                 NULL);
+    phip_disc_head(d_logits, d_action, d_adv, d_old_lp, d_mask, d_rows, m, A, d_off, D, max_n, eps, ent_coeff, d_grad,
+                   d_lp, d_ent, word, NULL);
     phip_sync();
     float l = 0.f;
     phip_d2h(&l, word, sizeof(float));
@@ -1883,16 +1875,29 @@ int ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, 
     return 0;
 }
 
-int ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const int* nvec, int D,
-                                    unsigned long long key, unsigned long long offset, float* d_action,
-                                    float* d_log_prob) {
+/* d_mask NULL: the unmasked sampler */
+static int disc_sample_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
+                              unsigned long long key, unsigned long long offset, float* d_action, float* d_log_prob) {
     if (!d_logits || !d_action || !d_log_prob || m <= 0) return -1;
     int max_n;
     const int* d_off = md_test_offsets(nvec, D, A, &max_n);
     if (!d_off) return -1;
-    phip_md_sample(d_logits, NULL, d_off, d_action, d_log_prob, m, A, D, key, offset);
+    phip_disc_sample(d_logits, d_mask, NULL, d_off, d_action, d_log_prob, NULL, m, A, D, key, offset);
     phip_sync();
     return 0;
+}
+
+int ppo_multidiscrete_head_device(const float* d_logits, const float* d_action, const float* d_adv,
+                                  const float* d_old_lp, int m, int A, const int* nvec, int D, float eps,
+                                  float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
+    return disc_head_device(d_logits, d_action, d_adv, d_old_lp, NULL, NULL, m, A, nvec, D, eps, ent_coeff, d_grad,
+                            d_lp, d_ent, loss);
+}
+
+int ppo_multidiscrete_sample_device(const float* d_logits, int m, int A, const int* nvec, int D,
+                                    unsigned long long key, unsigned long long offset, float* d_action,
+                                    float* d_log_prob) {
+    return disc_sample_device(d_logits, NULL, m, A, nvec, D, key, offset, d_action, d_log_prob);
 }
 
 /* ppo_ext.h: invalid-action masking */
@@ -1920,38 +1925,20 @@ uint32_t* ppo_action_mask_buffer(void* vppo) {
     return ppo && mask_on((const PPODev*)ppo->dev) ? ((PPODev*)ppo->dev)->mask : NULL;
 }
 
-/* the masked head, sampler and greedy action on caller-supplied device arrays (test entries, as the multi-discrete
- * ones; the categorical policy is nvec = {A}) */
+/* the masked head, sampler and greedy action on caller-supplied device arrays (test entries; the categorical policy
+ * is nvec = {A}) */
 int ppo_masked_head_device(const float* d_logits, const float* d_action, const float* d_adv, const float* d_old_lp,
                            const uint32_t* d_mask, const int* d_rows, int m, int A, const int* nvec, int D, float eps,
                            float ent_coeff, float* d_grad, float* d_lp, float* d_ent, double* loss) {
-    static float* word = NULL;
-    if (!d_logits || !d_action || !d_adv || !d_old_lp || !d_mask || !d_grad || !d_lp || !d_ent || !loss || m <= 0 ||
-        isnan(eps))
-        return -1;
-    int max_n;
-    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
-    if (!d_off) return -1;
-    if (!word) word = (float*)phip_malloc(4 * sizeof(float));
-    phip_memset(word, 0, 4 * sizeof(float));
-    phip_masked_head(d_logits, d_action, d_adv, d_old_lp, d_mask, d_rows, m, A, d_off, D, max_n, eps, ent_coeff, d_grad,
-                     d_lp, d_ent, word, NULL);
-    phip_sync();
-    float l = 0.f;
-    phip_d2h(&l, word, sizeof(float));
-    *loss = (double)l;
-    return 0;
+    if (!d_mask) return -1;
+    return disc_head_device(d_logits, d_action, d_adv, d_old_lp, d_mask, d_rows, m, A, nvec, D, eps, ent_coeff, d_grad,
+                            d_lp, d_ent, loss);
 }
 
 int ppo_masked_sample_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
                              unsigned long long key, unsigned long long offset, float* d_action, float* d_log_prob) {
-    if (!d_logits || !d_mask || !d_action || !d_log_prob || m <= 0) return -1;
-    int max_n;
-    const int* d_off = md_test_offsets(nvec, D, A, &max_n);
-    if (!d_off) return -1;
-    phip_masked_sample(d_logits, d_mask, NULL, d_off, d_action, d_log_prob, NULL, m, A, D, key, offset);
-    phip_sync();
-    return 0;
+    if (!d_mask) return -1;
+    return disc_sample_device(d_logits, d_mask, m, A, nvec, D, key, offset, d_action, d_log_prob);
 }
 
 int ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask, int m, int A, const int* nvec, int D,
@@ -1960,13 +1947,12 @@ int ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask, int 
     int max_n;
     const int* d_off = md_test_offsets(nvec, D, A, &max_n);
     if (!d_off) return -1;
-    phip_masked_argmax(d_logits, d_mask, d_off, d_action, m, A, D);
+    phip_disc_argmax(d_logits, d_mask, d_off, d_action, m, A, D);
     phip_sync();
     return 0;
 }
 
-/* the categorical head and sampler on caller-supplied device arrays (test entries: bad arguments return −1 ahead of
- * any device call, so nothing is recorded for ppo_last_error) */
+/* the categorical head and sampler on caller-supplied device arrays (test entries); the sampler is nvec = {A} */
 int ppo_categorical_head_device(const float* d_logits, const float* d_action, const float* d_adv,
                                 const float* d_old_lp, int m, int A, float eps, float ent_coeff, float* d_grad,
                                 float* d_lp, float* d_ent, double* loss) {
@@ -1986,10 +1972,7 @@ int ppo_categorical_head_device(const float* d_logits, const float* d_action, co
 
 int ppo_categorical_sample_device(const float* d_logits, int m, int A, unsigned long long key,
                                   unsigned long long offset, float* d_action, float* d_log_prob) {
-    if (!d_logits || !d_action || !d_log_prob || m <= 0 || A < 2 || A > PHIP_CAT_MAX_A) return -1;
-    phip_cat_sample(d_logits, NULL, d_action, d_log_prob, m, A, key, offset);
-    phip_sync();
-    return 0;
+    return disc_sample_device(d_logits, NULL, m, A, &A, 1, key, offset, d_action, d_log_prob);
 }
 
 /* ppo_ext.h: global gradient-norm clipping */
@@ -2179,7 +2162,9 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         /* one position in the Philox streams per step of every call: the policy noise and the environment's
          * draws never repeat under a constant seed */
         const uint64_t step = d->ro_step++;
-        if (cat) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
+        if (cat)
+            phip_disc_sample_rows(pol->mu->d_output, NULL, rows, disc_off(d), b->d_action_p, b->d_logprob_p, NULL, E, A,
+                                  disc_D(d), key, step);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
@@ -2208,15 +2193,12 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
         obs = obs_shadow(ppo, d);
         phip_obs_normalize(b->d_state_p, obs, N, S, d->obs_m, d->obs_m + S, d->obs_clip, d->obs_run, NULL);
     }
-    if (cat_on((PPODev*)ppo->dev)) {     /* categorical: one uniform per row from the "action noise" key */
+    if (cat_on((PPODev*)ppo->dev)) {     /* discrete: one uniform per (row, component) from the "action noise" key */
         nn_forward_dev(ppo->policy->mu, obs, (int)N);
         PPODev* d = (PPODev*)ppo->dev;
         mask_fill_full(d, N, A);                     /* sampled unmasked: the rows carry full masks */
-        if (md_on(d))
-            phip_md_sample(ppo->policy->mu->d_output, NULL, d->md_off, b->d_action_p, b->d_logprob_p, (int)N, A,
-                           d->md_D, s0 ^ 0x5, 0);
-        else
-            phip_cat_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, s0 ^ 0x5, 0);
+        phip_disc_sample(ppo->policy->mu->d_output, NULL, NULL, disc_off(d), b->d_action_p, b->d_logprob_p, NULL, (int)N,
+                         A, disc_D(d), s0 ^ 0x5, 0);
     } else {
         ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     }
@@ -2277,10 +2259,9 @@ static long long rollout_act(PPO* ppo, const uint32_t* d_mask, float* d_action) 
                                 d->obs_run);
     nn_forward_dev_rows(pol->mu, shadow ? shadow : b->d_state_p, rows, NULL, E);
     const uint64_t step = d->ro_step++;
-    if (d_mask)            /* under the caller's masks, which go to the step's rows of the store in the same launch */
-        phip_masked_sample_rows(pol->mu->d_output, d_mask, rows, disc_off(d), b->d_action_p, b->d_logprob_p, d->mask, E,
-                                A, disc_D(d), d->ext_key, step);
-    else if (cat_on(d)) disc_sample_rows(d, pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
+    if (cat_on(d))         /* under the caller's masks, which go to the step's rows of the store in the same launch */
+        phip_disc_sample_rows(pol->mu->d_output, d_mask, rows, disc_off(d), b->d_action_p, b->d_logprob_p,
+                              d_mask ? d->mask : NULL, E, A, disc_D(d), d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     if (!d_mask && mask_on(d)) phip_mask_fill_rows(d->mask, rows, E, A);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
@@ -2349,12 +2330,10 @@ static int act_device(PPO* ppo, const float* d_obs, const uint32_t* d_mask, int 
     nn_forward_dev_rows(pol->mu, norm ? d->act_obsn : d_obs, d->act_rows, NULL, m);
     const uint64_t key = splitmix64(seed ^ 0x524F4C4CULL);
     float* lp = d_log_prob ? d_log_prob : d->act_lp;
-    if (d_mask && deterministic) phip_masked_argmax(pol->mu->d_output, d_mask, disc_off(d), d_action, m, A, disc_D(d));
-    else if (d_mask)
-        phip_masked_sample_rows(pol->mu->d_output, d_mask, d->act_rows, disc_off(d), d_action, lp, NULL, m, A,
-                                disc_D(d), key, step);
-    else if (cat && deterministic) disc_argmax(d, pol->mu->d_output, d_action, m, A);
-    else if (cat) disc_sample_rows(d, pol->mu->d_output, d->act_rows, d_action, lp, m, A, key, step);
+    if (cat && deterministic) phip_disc_argmax(pol->mu->d_output, d_mask, disc_off(d), d_action, m, A, disc_D(d));
+    else if (cat)
+        phip_disc_sample_rows(pol->mu->d_output, d_mask, d->act_rows, disc_off(d), d_action, lp, NULL, m, A, disc_D(d),
+                              key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;

@@ -116,17 +116,18 @@ typedef struct {
     unsigned char *ev_term, *ev_trunc, *ev_cont;
     double* ev_agg;
     /* the action distribution (ppo_set_action_dist; 0 = diagonal Gaussian, 1 = categorical over A choices, μ's
-     * outputs the logits; csrc/categorical.hip) and the categorical head's entropy word: Σ of the row entropies
+     * outputs the logits; csrc/categorical.hip, csrc/discrete.hip) and the discrete heads' entropy word: Σ of the row entropies
      * of the last policy step's minibatch and that minibatch's rows (ppo_read_stats out[4]) */
     int action_dist;
     float* cat_ent;
     int cat_rows;
-    /* the multi-discrete policy (ppo_set_action_multidiscrete; action_dist == 2; csrc/multidiscrete.hip): μ's A
+    /* the multi-discrete policy (ppo_set_action_multidiscrete; action_dist == 2; csrc/discrete.hip): μ's A
      * outputs are md_D softmaxes side by side of widths md_nvec; md_off (device, md_D + 1 ints) their offsets,
-     * md_max_n the widest.  It takes every path the categorical policy takes, with its own kernels */
+     * md_max_n the widest.  cat_off = the device offsets {0, A}, laid when ppo_set_action_dist selects the categorical
+     * policy: it samples, takes its greedy action and runs its masked head through the same kernels as nvec = {A} */
     int md_D, md_max_n;
     int md_nvec[PHIP_MD_MAX_D];
-    int* md_off;
+    int *md_off, *cat_off;
     /* the open rollout (ppo_rollout_begin / _act / _store / _end; ro_kind == PHIP_ENV_EXTERNAL): ext_open while
      * one is open, ext_t the step the next act takes, ext_acted between an act and its store, ext_done once a
      * rollout has ended and ext_obs [ro_E, ro_S] — the observations the next step starts from, as the stores left
@@ -139,14 +140,13 @@ typedef struct {
     int act_m;
     float *act_obsn, *act_lp;
     int* act_rows;
-    /* invalid-action masking (ppo_set_action_mask; csrc/masked.hip; a discrete policy only): while mask_on the
+    /* invalid-action masking (ppo_set_action_mask; csrc/discrete.hip; a discrete policy only): while mask_on the
      * store `mask` holds capacity × W words, W = (A + 31) / 32, row r's words at r·W, bit k & 31 of word k >> 5 =
      * logit column k allowed — whatever lays buffer rows writes them, the policy step reads them through the
-     * minibatch's row indices.  NULL while off.  cat_off = the device offsets {0, A}: the categorical policy runs the
-     * masked kernels as nvec = {A}.  Not part of save_ppo's checkpoint (ppo_save_state keeps it), not hashed, no collective */
+     * minibatch's row indices.  NULL while off.  Not part of save_ppo's checkpoint (ppo_save_state keeps it), not
+     * hashed, no collective */
     int mask_on;
     uint32_t* mask;
-    int* cat_off;
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

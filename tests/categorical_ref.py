@@ -1,5 +1,5 @@
-"""The categorical policy (csrc/ppo_math.h cat_* atoms + surrogate, csrc/categorical.hip, and CartPole-v1 of
-csrc/rollout.hip), restated independently of the kernels:
+"""The categorical policy (csrc/ppo_math.h cat_* atoms + surrogate, csrc/categorical.hip's head, csrc/discrete.hip's
+sampler at D = 1, and CartPole-v1 of csrc/rollout.hip), restated independently of the kernels:
 
   * head_f64        the definition in float64, from the fp32 inputs as given;
   * head_f32        an fp32 numpy mirror in the stated order (k ascending, libm's expf / logf);

@@ -1,4 +1,4 @@
-"""Invalid-action masking (csrc/ppo_math.h "Action masking", csrc/masked.hip), restated independently of the kernels
+"""Invalid-action masking (csrc/ppo_math.h "Action masking", csrc/discrete.hip), restated independently of the kernels
 on multidiscrete_ref's and categorical_ref's definitions:
 
   * pack / unpack / effective   the storage (W = (A + 31) // 32 words a row, bit k & 31 of word k >> 5 = column k

@@ -1,4 +1,4 @@
-"""The multi-discrete policy (csrc/ppo_math.h md_* on the cat_* atoms, csrc/multidiscrete.hip), restated
+"""The multi-discrete policy (csrc/ppo_math.h md_* on the cat_* atoms, csrc/discrete.hip), restated
 independently of the kernels, segment by segment on categorical_ref's definitions:
 
   * head_f64      the definition in float64: D softmaxes side by side, joint lp and H, one surrogate on the joint

@@ -1,5 +1,5 @@
-"""The categorical policy on the device (ppo_set_action_dist; csrc/categorical.hip) against tests/categorical_ref.py:
-the head row by row, the sampler, a whole update, and the argument handling.  Every bound comes from
+"""The categorical policy on the device (ppo_set_action_dist; csrc/categorical.hip, csrc/discrete.hip) against
+tests/categorical_ref.py: the head row by row, the sampler, a whole update, and the argument handling.  Every bound comes from
 categorical_ref (derived from the rounding of the listed operations and validated by the fp32 mirror on the CPU in
 test_categorical_cpu.py); nothing is taken from a run of the kernels.
 

@@ -1,4 +1,4 @@
-"""Invalid-action masking on the device (ppo_set_action_mask; csrc/masked.hip) against tests/masked_ref.py: the head
+"""Invalid-action masking on the device (ppo_set_action_mask; csrc/discrete.hip) against tests/masked_ref.py: the head
 row by row, a full mask against the unmasked heads bit for bit, the sampler and the greedy action, the KL monitor, one
 policy step of an update, the open rollout and the argument handling.  Every bound comes from masked_ref /
 multidiscrete_ref / categorical_ref (derived from the rounding of the listed operations and validated by the fp32

@@ -1,4 +1,4 @@
-"""The multi-discrete policy on the device (ppo_set_action_multidiscrete; csrc/multidiscrete.hip) against
+"""The multi-discrete policy on the device (ppo_set_action_multidiscrete; csrc/discrete.hip) against
 tests/multidiscrete_ref.py: the head row by row, D = 1 against the categorical head bit for bit, the sampler, a
 whole update, bit-identity with the categorical policy through the whole library, the synthetic rollout, the open
 rollout and the argument handling.  Every bound comes from multidiscrete_ref / categorical_ref (derived from the
