@@ -125,6 +125,9 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * integer: integer atomics only; under data parallelism THIS RANK's rows), out[24]=rewards it scaled (limit)
  * (reward normalisation, ppo_set_reward_norm: all three 0 while it is off; callers passing n <= 22 see no
  * change).
+ * out[25]=the policy learning rate in use, out[26]=the value learning rate in use (ppo_get_lr), out[27]=policy steps
+ * that raised the rate, out[28]=policy steps that lowered it, both since the last reset (the adaptive schedule,
+ * ppo_set_lr_schedule: both 0 under the other schedules; callers passing n <= 25 see no change).
  * With the categorical policy (ppo_set_action_dist 1) — or the multi-discrete one, its joint row entropy — out[4] is the
  * mean row entropy of the last policy step's
  * minibatch (Σ H / rows as the head accumulated it; 0 before the first policy step; under data parallelism THIS
@@ -178,6 +181,66 @@ int    ppo_kl_history(void* ppo, double* out, int n);
  * [m] → out2 = {approximate KL, clip fraction}; returns 0, −1 for bad arguments; synchronises */
 int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
                             int m, int A, float eps, double* out2);
+/* Learning-rate schedules (constant by default; not in the reference).  kind picks one; p0 … p2 are its parameters.
+ *   PPO_LR_CONSTANT  today's behaviour on today's code path, bit for bit: ppo->lr_policy and ppo->lr_V are read from
+ *                    the struct by every update and passed to the Adam kernels by value.  p0 … p2 are ignored.
+ *   PPO_LR_LINEAR    linear decay (CleanRL anneal_lr, Stable-Baselines3 linear_schedule).  p0 = total updates N >= 1,
+ *                    p1 = final fraction f in [0, 1], p2 unused.  Update number u counts the ppo_update calls since
+ *                    the setter, from 0; update u runs with
+ *                        lr = (float)((double)base · (1 − (1 − f)·(min(u, N)/N)))   (double, rounded once, on the host;
+ *                                                                                    u >= N gives (float)(base·f))
+ *                    for base = ppo->lr_policy and base = ppo->lr_V alike, passed by value: no kernel differs, and
+ *                    every update path (single-workgroup / cluster phases, graph replay) stays available.
+ *   PPO_LR_ADAPTIVE  the KL-adaptive rate of rl_games and rsl_rl (schedule = "adaptive", desired_kl).  p0 = desired_kl
+ *                    > 0, p1 = lr_min > 0, p2 = lr_max >= lr_min, all finite.  The policy rate is one fp32 word on
+ *                    the device, set by the setter to clamp(ppo->lr_policy, lr_min, lr_max); the struct field is
+ *                    the base and is never written.  While the schedule is on, the KL monitor runs exactly as under
+ *                    ppo_set_target_kl(ppo, +inf) (a finite target keeps working alongside), and every policy
+ *                    minibatch step, once its kl is known and before the stop test, applies in fp32 (IEEE division
+ *                    and product):
+ *                        if      (kl > 2.0f · desired_kl)               lr = fmaxf(lr_min, lr / 1.5f);   lowered += 1
+ *                        else if (kl < 0.5f · desired_kl && kl > 0.0f)  lr = fminf(lr_max, lr · 1.5f);   raised  += 1
+ *                    A NaN kl changes nothing; once target-KL early stopping has stopped the update, the rate no
+ *                    longer changes.  The step's own policy and entropy Adams read the new word through a pointer
+ *                    (step = lr / bias_correction1 computed by the kernel: the fp32 division the host does otherwise,
+ *                    so an equal rate gives equal bits); the host never reads the rate inside an epoch.  kl is the k3
+ *                    estimator of ppo_set_target_kl above — mean(expm1(x) − x) over the minibatch — NOT the
+ *                    closed-form Gaussian KL rsl_rl evaluates, so a desired_kl tuned there carries over only roughly.
+ *                    The value rate stays ppo->lr_V by value unless coupled (below).  As target KL, the schedule
+ *                    takes the multi-launch loop (no single-workgroup / cluster phases, no graph replay) and works
+ *                    with clipping, both normalisers, the discrete policies and bf16 mode.  Under data parallelism
+ *                    the rule runs on the all-reduced sums, so every rank takes the same decision from the same bits
+ *                    and no collective is added; EVERY RANK MUST HOLD THE SAME SCHEDULE, and ppo_param_hash /
+ *                    ppo_comm_check_replicas cover the two rate words while it is on.
+ * The setter restarts the schedule (u = 0, the adaptive rate back at the clamped base, both counters 0).  Not part of a
+ * checkpoint (save_ppo's; ppo_save_state keeps the kind, the parameters, the coupling, u, the rate words and the
+ * counters): set it again after load_ppo.
+ * Returns 0, or −1 with the setting unchanged for an unknown kind, a NaN parameter or a parameter outside the
+ * ranges above. */
+enum { PPO_LR_CONSTANT = 0, PPO_LR_LINEAR = 1, PPO_LR_ADAPTIVE = 2 };
+int  ppo_set_lr_schedule(void* ppo, int kind, float p0, float p1, float p2);
+/* returns the kind; out4 (may be NULL) = {p0, p1, p2, couple_value}: p0 … p2 are zeros for the constant schedule,
+ * couple_value is the flag as ppo_lr_couple_value left it, whatever the schedule */
+int  ppo_get_lr_schedule(void* ppo, float* out4);
+/* Value-rate coupling of the adaptive schedule (off by default; without that schedule the flag is kept and unused).
+ * The value loop runs beside the policy loop on its own stream, so nothing changes its rate inside an update: with
+ * coupling on, one one-thread launch at the start of each ppo_update, ahead of the loops' fork, sets
+ *     lr_v = lr_V · (lr / clamp(lr_policy, lr_min, lr_max))          (fp32: one division, one product)
+ * from the policy rate as the previous update left it, and the value Adam reads that word for the whole update —
+ * deterministic, no cross-stream read.  Returns the previous value, −1 for a NULL ppo. */
+int  ppo_lr_couple_value(void* ppo, int on);
+/* out2 = {policy lr, value lr} in use now: what an update starting now would pass (constant, linear) or the device
+ * words as they stand (adaptive; the value word only under coupling, where it is the last update's).  Returns 0, −1
+ * for a NULL argument; synchronises */
+int  ppo_get_lr(void* ppo, double* out2);
+/* the rate each decided policy step of the last ppo_update ran its Adam with (adaptive schedule), in step order,
+ * into out[0, min(n, steps, 4096)); returns the number of decided steps (0 under the other schedules); synchronises */
+int  ppo_lr_history(void* ppo, float* out, int n);
+/* One adam_update_cuda step of a device Adam with the rate read from the device word d_lr, through the Adam kernels'
+ * pointer variants (a test entry: the update calls them through the adaptive schedule).  Returns 0, −1 for a NULL or
+ * host Adam or a NULL d_lr */
+int  ppo_adam_update_lr_device(void* adam, const float* d_lr);
+
 /* PPO2 value-loss clipping (off by default; not in the reference; baselines PPO2, CleanRL clip_vloss,
  * Stable-Baselines3 clip_range_vf).  For a value minibatch of m rows, with y the network's value of a row, t its
  * target (adv_target), v_old its old value and eps_v > 0 the clip range, every form of the value head (the plain

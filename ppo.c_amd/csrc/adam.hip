@@ -93,6 +93,23 @@ __global__ void adam_flat_vec_kernel(float* __restrict__ p, float* __restrict__ 
     adam_vec_body(p, g, m, v, n, step, b1, b2, bc2, clip_scale(scale, coef), w16, n16, zero_g);
 }
 
+// The learning rate through a device word (the KL-adaptive schedule, kl.hip: decide() wrote it in a launch before
+// this one): step = *lr / bias_correction1, the fp32 division the host does for the by-value kernels, so an equal
+// rate gives equal bits.  A kernel of its own per form, picked on the host — the by-value kernels are untouched.
+__device__ __forceinline__ float dev_step(const float* __restrict__ lr, float bc1) { return *lr / bc1; }
+
+__global__ void adam_flat_vec_lrp_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, long n, const float* __restrict__ lr, float bc1,
+                                         float b1, float b2, float bc2, float scale, __bf16* __restrict__ w16,
+                                         long n16, int zero_g, const float* __restrict__ coef,
+                                         const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) {
+        if (zero_g) clear_vec_body(g, n);
+        return;
+    }
+    adam_vec_body(p, g, m, v, n, dev_step(lr, bc1), b1, b2, bc2, clip_scale(scale, coef), w16, n16, zero_g);
+}
+
 // a second, small flat span in the same launch (the policy step's entropy Adam beside the network's,
 // ppo.cu:440-442 — independent parameters): the last workgroup's first s.n threads, scalar
 struct SideSpan {
@@ -120,6 +137,35 @@ __global__ void adam_flat_vec_pair_kernel(float* __restrict__ p, float* __restri
         if (s.zero_g) s.g[j] = 0.f;
     }
     adam_vec_body(p, g, m, v, n, step, b1, b2, bc2, scale, w16, n16, zero_g);
+}
+
+// the pair with both rates through device words: the side span takes its own pointer
+struct SideSpanLrp {
+    float* p; float* g; float* m; float* v; int n; const float* lr; float bc1, bc2, scale; int zero_g;
+};
+__global__ void adam_flat_vec_pair_lrp_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                              float* __restrict__ v, long n, const float* __restrict__ lr, float bc1,
+                                              float b1, float b2, float bc2, float scale,
+                                              __bf16* __restrict__ w16, long n16, int zero_g, SideSpanLrp s,
+                                              const float* __restrict__ coef, const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) {
+        if (s.zero_g && blockIdx.x == gridDim.x - 1 && threadIdx.x < s.n) s.g[threadIdx.x] = 0.f;
+        if (zero_g) clear_vec_body(g, n);
+        return;
+    }
+    if (coef) {
+        const float c = *coef;
+        scale = scale * c;
+        s.scale = s.scale * c;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x < s.n) {
+        const int j = threadIdx.x;
+        float pp = s.p[j], mm = s.m[j], vv = s.v[j];
+        adam_elem(pp, s.g[j], mm, vv, dev_step(s.lr, s.bc1), b1, b2, s.bc2, s.scale);
+        s.p[j] = pp; s.m[j] = mm; s.v[j] = vv;
+        if (s.zero_g) s.g[j] = 0.f;
+    }
+    adam_vec_body(p, g, m, v, n, dev_step(lr, bc1), b1, b2, bc2, scale, w16, n16, zero_g);
 }
 
 // the flat Adam with its step size / bias correction from the step table (graph replay); which = 0
@@ -172,16 +218,29 @@ __global__ void adam_flat_tab_kernel(float* __restrict__ p, float* __restrict__ 
     }
 }
 
-__global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
-                                 float scale, const float* __restrict__ coef, const unsigned* __restrict__ skip) {
-    if (step_skipped(skip)) return;
-    scale = clip_scale(scale, coef);
+__device__ __forceinline__ void adam_scalar_body(float* __restrict__ p, const float* __restrict__ g,
+                                                 float* __restrict__ m, float* __restrict__ v, long n, float step,
+                                                 float b1, float b2, float bc2, float scale) {
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < n; i += (long)gridDim.x * TPB) {
         float pp = p[i], mm = m[i], vv = v[i];
         adam_elem(pp, g[i], mm, vv, step, b1, b2, bc2, scale);
         p[i] = pp; m[i] = mm; v[i] = vv;
     }
+}
+
+__global__ void adam_flat_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long n, float step, float b1, float b2, float bc2,
+                                 float scale, const float* __restrict__ coef, const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) return;
+    adam_scalar_body(p, g, m, v, n, step, b1, b2, bc2, clip_scale(scale, coef));
+}
+
+__global__ void adam_flat_lrp_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                     float* __restrict__ v, long n, const float* __restrict__ lr, float bc1, float b1,
+                                     float b2, float bc2, float scale, const float* __restrict__ coef,
+                                     const unsigned* __restrict__ skip) {
+    if (step_skipped(skip)) return;
+    adam_scalar_body(p, g, m, v, n, dev_step(lr, bc1), b1, b2, bc2, clip_scale(scale, coef));
 }
 
 constexpr int MAXT = 24;
@@ -192,8 +251,8 @@ struct TensorTable {
     int count;
 };
 
-__global__ void adam_multi_kernel(TensorTable t, float* __restrict__ m, float* __restrict__ v, float step, float b1,
-                                  float b2, float bc2, float scale) {
+__device__ __forceinline__ void adam_multi_body(const TensorTable& t, float* __restrict__ m, float* __restrict__ v,
+                                                float step, float b1, float b2, float bc2, float scale) {
     const long total = t.start[t.count];
     for (long i = blockIdx.x * (long)TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
         int k = 0;
@@ -203,6 +262,17 @@ __global__ void adam_multi_kernel(TensorTable t, float* __restrict__ m, float* _
         adam_elem(pp, t.g[k][j], mm, vv, step, b1, b2, bc2, scale);
         t.p[k][j] = pp; m[i] = mm; v[i] = vv;
     }
+}
+
+__global__ void adam_multi_kernel(TensorTable t, float* __restrict__ m, float* __restrict__ v, float step, float b1,
+                                  float b2, float bc2, float scale) {
+    adam_multi_body(t, m, v, step, b1, b2, bc2, scale);
+}
+
+__global__ void adam_multi_lrp_kernel(TensorTable t, float* __restrict__ m, float* __restrict__ v,
+                                      const float* __restrict__ lr, float bc1, float b1, float b2, float bc2,
+                                      float scale) {
+    adam_multi_body(t, m, v, dev_step(lr, bc1), b1, b2, bc2, scale);
 }
 
 int grid_for(long n) {
@@ -216,24 +286,50 @@ int grid_for(long n) {
 
 extern "C" {
 
-void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                        float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g, const float* coef, const unsigned* skip) {
+// lr_dev != nullptr: the rate is read from that device word by the *_lrp kernels (lr is then unused)
+static void adam_flat_launch(float* p, float* g, float* m, float* v, long n, float lr, const float* lr_dev,
+                             float beta1, float beta2, float bias_correction1, float bias_correction2,
+                             float grad_scale, unsigned short* w16, long n16, int zero_g, const float* coef,
+                             const unsigned* skip) {
     if (n <= 0) return;
     const float step = lr / bias_correction1;
     ppo::ProfScope ps(PPO_K_ADAM, 28.0 * n + (w16 ? 2.0 * n16 : 0.0) + (zero_g ? 4.0 * n : 0.0));
     const bool vec = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0 &&
                      ((uintptr_t)w16 & 7u) == 0;
     if (vec) {
-        hipLaunchKernelGGL(adam_flat_vec_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
-                           v, n, step, beta1, beta2, bias_correction2, grad_scale,
-                           reinterpret_cast<__bf16*>(w16), n16, zero_g, coef, skip);
+        if (lr_dev)
+            hipLaunchKernelGGL(adam_flat_vec_lrp_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p,
+                               g, m, v, n, lr_dev, bias_correction1, beta1, beta2, bias_correction2, grad_scale,
+                               reinterpret_cast<__bf16*>(w16), n16, zero_g, coef, skip);
+        else
+            hipLaunchKernelGGL(adam_flat_vec_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g,
+                               m, v, n, step, beta1, beta2, bias_correction2, grad_scale,
+                               reinterpret_cast<__bf16*>(w16), n16, zero_g, coef, skip);
     } else {
         PPO_REQUIRE(!w16 && !zero_g, "phip_adam_flat_w16: unaligned span with a bf16 shadow or gradient clear");
-        hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n)), dim3(TPB), 0, ppo::stream(), p, g, m, v, n, step,
-                           beta1, beta2, bias_correction2, grad_scale, coef, skip);
+        if (lr_dev)
+            hipLaunchKernelGGL(adam_flat_lrp_kernel, dim3(grid_for(n)), dim3(TPB), 0, ppo::stream(), p, g, m, v, n,
+                               lr_dev, bias_correction1, beta1, beta2, bias_correction2, grad_scale, coef, skip);
+        else
+            hipLaunchKernelGGL(adam_flat_kernel, dim3(grid_for(n)), dim3(TPB), 0, ppo::stream(), p, g, m, v, n, step,
+                               beta1, beta2, bias_correction2, grad_scale, coef, skip);
     }
     PPO_LAUNCH_CHECK();
+}
+
+void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
+                        float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
+                        long n16, int zero_g, const float* coef, const unsigned* skip) {
+    adam_flat_launch(p, g, m, v, n, lr, nullptr, beta1, beta2, bias_correction1, bias_correction2, grad_scale, w16,
+                     n16, zero_g, coef, skip);
+}
+
+void phip_adam_flat_w16_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1, float beta2,
+                            float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
+                            long n16, int zero_g, const float* coef, const unsigned* skip) {
+    PPO_REQUIRE(lr, "phip_adam_flat_w16_lrp: NULL rate");
+    adam_flat_launch(p, g, m, v, n, 0.f, lr, beta1, beta2, bias_correction1, bias_correction2, grad_scale, w16, n16,
+                     zero_g, coef, skip);
 }
 
 void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
@@ -248,6 +344,22 @@ void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float l
     SideSpan s{p2, g2, m2, v2, n2, lr2 / bias_correction1_2, bias_correction2_2, grad_scale2, zero_g2};
     hipLaunchKernelGGL(adam_flat_vec_pair_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g, m,
                        v, n, lr / bias_correction1, beta1, beta2, bias_correction2, grad_scale,
+                       reinterpret_cast<__bf16*>(w16), n16, zero_g, s, coef, skip);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_adam_flat_pair_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1,
+                             float beta2, float bias_correction1, float bias_correction2, float grad_scale,
+                             unsigned short* w16, long n16, int zero_g, float* p2, float* g2, float* m2, float* v2,
+                             int n2, const float* lr2, float bias_correction1_2, float bias_correction2_2,
+                             float grad_scale2, int zero_g2, const float* coef, const unsigned* skip) {
+    PPO_REQUIRE(n > 0 && n2 >= 0 && n2 <= TPB && lr && lr2, "phip_adam_flat_pair_lrp: spans");
+    PPO_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0 && ((uintptr_t)w16 & 7u) == 0,
+                "phip_adam_flat_pair_lrp: the network span must be 16-B aligned");
+    ppo::ProfScope ps(PPO_K_ADAM, 28.0 * (n + n2) + (w16 ? 2.0 * n16 : 0.0) + (zero_g ? 4.0 * n : 0.0));
+    SideSpanLrp s{p2, g2, m2, v2, n2, lr2, bias_correction1_2, bias_correction2_2, grad_scale2, zero_g2};
+    hipLaunchKernelGGL(adam_flat_vec_pair_lrp_kernel, dim3(grid_for((n + 3) / 4)), dim3(TPB), 0, ppo::stream(), p, g,
+                       m, v, n, lr, bias_correction1, beta1, beta2, bias_correction2, grad_scale,
                        reinterpret_cast<__bf16*>(w16), n16, zero_g, s, coef, skip);
     PPO_LAUNCH_CHECK();
 }
@@ -269,9 +381,9 @@ void phip_adam_flat(float* p, const float* g, float* m, float* v, long n, float 
                        grad_scale, nullptr, 0, 0, nullptr, nullptr);
 }
 
-void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
-                     float* v, float lr, float beta1, float beta2, float bias_correction1, float bias_correction2,
-                     float grad_scale) {
+static void adam_multi_launch(float* const* params, float* const* grads, const int* lengths, int num_tensors,
+                              float* m, float* v, float lr, const float* lr_dev, float beta1, float beta2,
+                              float bias_correction1, float bias_correction2, float grad_scale) {
     const float step = lr / bias_correction1;
     long base = 0;
     for (int t0 = 0; t0 < num_tensors; t0 += MAXT) {
@@ -286,12 +398,32 @@ void phip_adam_multi(float* const* params, float* const* grads, const int* lengt
         const long total = t.start[t.count];
         if (total > 0) {
             ppo::ProfScope ps(PPO_K_ADAM, 28.0 * total);
-            hipLaunchKernelGGL(adam_multi_kernel, dim3(grid_for(total)), dim3(TPB), 0, ppo::stream(), t, m + base,
-                               v + base, step, beta1, beta2, bias_correction2, grad_scale);
+            if (lr_dev)
+                hipLaunchKernelGGL(adam_multi_lrp_kernel, dim3(grid_for(total)), dim3(TPB), 0, ppo::stream(), t,
+                                   m + base, v + base, lr_dev, bias_correction1, beta1, beta2, bias_correction2,
+                                   grad_scale);
+            else
+                hipLaunchKernelGGL(adam_multi_kernel, dim3(grid_for(total)), dim3(TPB), 0, ppo::stream(), t, m + base,
+                                   v + base, step, beta1, beta2, bias_correction2, grad_scale);
             PPO_LAUNCH_CHECK();
         }
         base += total;
     }
+}
+
+void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
+                     float* v, float lr, float beta1, float beta2, float bias_correction1, float bias_correction2,
+                     float grad_scale) {
+    adam_multi_launch(params, grads, lengths, num_tensors, m, v, lr, nullptr, beta1, beta2, bias_correction1,
+                      bias_correction2, grad_scale);
+}
+
+void phip_adam_multi_lrp(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
+                         float* v, const float* lr, float beta1, float beta2, float bias_correction1,
+                         float bias_correction2, float grad_scale) {
+    PPO_REQUIRE(lr, "phip_adam_multi_lrp: NULL rate");
+    adam_multi_launch(params, grads, lengths, num_tensors, m, v, 0.f, lr, beta1, beta2, bias_correction1,
+                      bias_correction2, grad_scale);
 }
 
 }  // extern "C"

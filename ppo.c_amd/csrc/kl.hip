@@ -12,6 +12,9 @@
 //   kl    = Σ (expm1(x_i) − x_i) / rows          (Schulman's k3 estimator; double: (r − 1) − log r cancels in fp32)
 //   frac  = Σ 1[|(float)exp(x_i) − 1| > ε] / rows
 //   if (!stopped && kl > 1.5f · target_kl) { stopped = 1; stop_step = step; }      (Stable-Baselines3's rule)
+// With the KL-adaptive learning-rate schedule on (ppo_set_lr_schedule, PPO_LR_ADAPTIVE) the same decision first moves
+// the record's rate: lr /= 1.5 (floor lr_min) when kl > 2·desired_kl, lr *= 1.5 (cap lr_max) when 0 < kl < desired_kl/2;
+// lr_hist[step] keeps the rate the step's Adam then reads through a pointer.
 // left in a device record; the step's Adam reads `stopped` through a pointer (adam.hip) and takes no step once
 // it is set.  The host never reads the record inside an epoch.
 //
@@ -51,6 +54,24 @@ __device__ __forceinline__ void decide(PhipKlRec* rec, float target_kl, double r
     rec->clip_frac = (float)((double)rec->sums[1] / rows_global);
     unsigned stopped = rec->stopped;
     const unsigned step = rec->step;
+    /* the KL-adaptive learning rate (lr_kl = desired_kl; 0: the schedule is off and nothing here runs): rl_games' /
+     * rsl_rl's rule on this step's kl, in fp32 with IEEE division and product, before the stop test; once the update
+     * has stopped the rate stays.  The step's Adam launches read rec->lr behind this launch (adam.hip, *_lrp). */
+    const float want = rec->lr_kl;
+    if (want > 0.f) {
+        float lr = rec->lr;
+        if (!stopped) {
+            if (kl > 2.0f * want) {                       // NaN compares false on both branches: nothing changes
+                lr = fmaxf(rec->lr_min, lr / 1.5f);
+                rec->lr_lowered += 1u;
+            } else if (kl < 0.5f * want && kl > 0.0f) {
+                lr = fminf(rec->lr_max, lr * 1.5f);
+                rec->lr_raised += 1u;
+            }
+            rec->lr = lr;
+        }
+        if (step < (unsigned)PHIP_KL_HIST) rec->lr_hist[step] = lr;
+    }
     if (!stopped && kl > 1.5f * target_kl) {          // NaN compares false: never stops
         stopped = 1u;
         rec->stopped = 1u;
@@ -124,6 +145,12 @@ __global__ void kl_decide_kernel(PhipKlRec* rec, float target_kl, double rows_gl
     if (blockIdx.x == 0 && threadIdx.x == 0) decide(rec, target_kl, rows_global);
 }
 
+// value-rate coupling, one thread, once per update ahead of the loops' fork: the value Adam's word for the whole
+// update, lr_v = lr_V · (lr / base), base = clamp(lr_policy, lr_min, lr_max) — one fp32 division, one product
+__global__ void lr_couple_kernel(PhipKlRec* rec, float lr_V, float base) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) rec->lr_v = lr_V * (rec->lr / base);
+}
+
 int grid_for(int m) {
     long g = ((long)m + TPB - 1) / TPB;
     if (g < 1) g = 1;
@@ -152,6 +179,13 @@ void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global) {
     PPO_REQUIRE(rows_global > 0 && rec, "phip_kl_decide: shape");
     ppo::ProfScope ps(PPO_K_ADAM, 64.0);
     hipLaunchKernelGGL(kl_decide_kernel, dim3(1), dim3(64), 0, ppo::stream(), rec, target_kl, (double)rows_global);
+    PPO_LAUNCH_CHECK();
+}
+
+void phip_lr_couple(PhipKlRec* rec, float lr_V, float base) {
+    PPO_REQUIRE(rec && base > 0.f, "phip_lr_couple: arguments");
+    ppo::ProfScope ps(PPO_K_OTHER, 16.0);              // not an Adam launch: kept out of that class's counts
+    hipLaunchKernelGGL(lr_couple_kernel, dim3(1), dim3(64), 0, ppo::stream(), rec, lr_V, base);
     PPO_LAUNCH_CHECK();
 }
 

@@ -403,6 +403,19 @@ void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float l
                          long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
                          float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
                          const float* coef, const unsigned* skip);
+/* the three launchers with the learning rate(s) read from device words: step = *lr / bias_correction1 computed by
+ * the kernel (the *_lrp kernels; the same fp32 division, so an equal rate gives equal bits) */
+void phip_adam_flat_w16_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1, float beta2,
+                            float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
+                            long n16, int zero_g, const float* coef, const unsigned* skip);
+void phip_adam_flat_pair_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1,
+                             float beta2, float bias_correction1, float bias_correction2, float grad_scale,
+                             unsigned short* w16, long n16, int zero_g, float* p2, float* g2, float* m2, float* v2,
+                             int n2, const float* lr2, float bias_correction1_2, float bias_correction2_2,
+                             float grad_scale2, int zero_g2, const float* coef, const unsigned* skip);
+void phip_adam_multi_lrp(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
+                         float* v, const float* lr, float beta1, float beta2, float bias_correction1,
+                         float bias_correction2, float grad_scale);
 /* multi-tensor: ptrs/lengths are HOST arrays describing device tensors; m/v are flat */
 void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors,
                      float* m, float* v, float lr, float beta1, float beta2,
@@ -443,6 +456,14 @@ typedef struct {
     unsigned pad;
     double partial[2 * PHIP_KL_PARTS];
     float hist[PHIP_KL_HIST];       /* KL per decided step of the current update (later steps are not recorded) */
+    /* the KL-adaptive learning rate (ppo_set_lr_schedule, PPO_LR_ADAPTIVE), behind everything the record held
+     * before: with lr_kl == 0 (off) decide() neither reads nor writes anything below */
+    float lr;                       /* the policy rate: the policy and entropy Adams read it through a pointer */
+    float lr_v;                     /* the value rate under coupling (phip_lr_couple), read by the value Adam */
+    float lr_kl, lr_min, lr_max;    /* desired_kl (0: off) and the clamp range */
+    unsigned lr_raised, lr_lowered; /* steps that raised / lowered the rate since the counters were cleared */
+    unsigned lr_pad;
+    float lr_hist[PHIP_KL_HIST];    /* the rate each decided step's Adam used */
 } PhipKlRec;
 /* Σ (expm1(x) − x) and the clipped-row count of one policy minibatch (x = log-prob − old log-prob, rows of
  * μ [m, A]) into rec->sums; one launch, deterministic (no floating-point atomics, grid a function of m), no
@@ -460,6 +481,8 @@ void phip_policy_kl(const float* mu, const float* log_std, const float* action, 
  * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so
  * that all ranks issue the same order of collectives */
 void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global);
+/* rec->lr_v = lr_V · (rec->lr / base) in fp32, one thread (value-rate coupling of the adaptive schedule) */
+void phip_lr_couple(PhipKlRec* rec, float lr_V, float base);
 /* the host waits for the launches issued so far on the current stream only (an event recorded there) */
 void phip_stream_wait(void);
 

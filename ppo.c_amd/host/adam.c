@@ -184,8 +184,9 @@ void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NUL
  * device stop word of target-KL early stopping (PhipKlRec.stopped): while it is set the kernel takes no step
  * and only clears the gradient where zero_g asks.  The host step counter advances either way; ppo_update
  * sets it back by the steps the device skipped. */
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
-                         const unsigned* skip) {
+/* d_lr != NULL: the rate comes from that device word, read by the kernels' pointer variants (lr is unused) */
+static int adam_update_dev(Adam* adam, float lr, const float* d_lr, unsigned short* w16, long n16, int zero_g,
+                           const float* coef, const unsigned* skip) {
     if (coef && !adam->flat) die("adam_update_cuda_w16: gradient clipping needs a flat Adam span");
     if (skip && !adam->flat) die("adam_update_cuda_w16: target-KL early stopping needs a flat Adam span");
     float bc1, bc2;
@@ -196,9 +197,17 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
         const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
                              (uintptr_t)adam->v;
         if (al & 15u) zero_g = 0;
-        phip_adam_flat_w16(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                           adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef, skip);
+        if (d_lr)
+            phip_adam_flat_w16_lrp(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, d_lr,
+                                   adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g,
+                                   coef, skip);
+        else
+            phip_adam_flat_w16(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
+                               adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef, skip);
         return (w16 != NULL) | (zero_g ? 2 : 0);
+    } else if (d_lr) {
+        phip_adam_multi_lrp(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v,
+                            d_lr, adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale);
     } else {
         phip_adam_multi(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v, lr,
                         adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale);
@@ -206,13 +215,35 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
     return 0;
 }
 
+int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
+                         const unsigned* skip) {
+    return adam_update_dev(adam, lr, NULL, w16, n16, zero_g, coef, skip);
+}
+
+/* the same step with the learning rate in a device word (the KL-adaptive schedule's, or a coupled value rate) */
+int adam_update_cuda_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, const float* coef,
+                         const unsigned* skip) {
+    if (!d_lr) die("adam_update_cuda_lrp: NULL rate");
+    return adam_update_dev(adam, 0.f, d_lr, w16, n16, zero_g, coef, skip);
+}
+
+/* ppo_ext.h (a test entry): one adam_update_cuda step through the pointer variants */
+int ppo_adam_update_lr_device(void* vadam, const float* d_lr) {
+    Adam* adam = (Adam*)vadam;
+    if (!adam || !adam->on_device || !d_lr) return -1;
+    adam_update_cuda_lrp(adam, d_lr, NULL, 0, 0, NULL, NULL);
+    return 0;
+}
+
 /* a network's flat Adam (16-B aligned span) and a small flat side Adam (the entropy Adam's log σ) in
  * one launch; the side's step runs first in the step counters (ppo.cu:440-442 order; the spans are
  * independent).  Returns bit 0: shadow refreshed, bit 1: network gradients cleared, bit 2: side
  * gradients cleared; −1 (nothing done) when the pair does not qualify.  coef as in adam_update_cuda_w16:
- * one coefficient for both spans; skip likewise: one stop word for both. */
-int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side, const float* coef, const unsigned* skip) {
+ * one coefficient for both spans; skip likewise: one stop word for both.  d_lr / d_lr_side != NULL (both or
+ * neither): the two rates from device words (the pair kernel's pointer variant; lr and lr_side are unused). */
+static int adam_update_pair_dev(Adam* adam, float lr, const float* d_lr, unsigned short* w16, long n16, int zero_g,
+                                Adam* side, float lr_side, const float* d_lr_side, int zero_side, const float* coef,
+                                const unsigned* skip) {
     const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
                          (uintptr_t)adam->v;
     if (!adam->flat || !side->flat || (al & 15u) || side->span > 256 || side->span < 1 || adam->span < 1 ||
@@ -223,11 +254,28 @@ int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
     bias_corrections(adam, &bc1, &bc2);
     nn_note_device_update(adam->weights[0]);
     nn_note_device_update(side->weights[0]);
-    phip_adam_flat_pair(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                        adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, side->weights[0],
-                        side->grad_weights[0], side->m, side->v, (int)side->span, lr_side, bc1s, bc2s,
-                        side->grad_scale, zero_side, coef, skip);
+    if (d_lr)
+        phip_adam_flat_pair_lrp(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, d_lr,
+                                adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g,
+                                side->weights[0], side->grad_weights[0], side->m, side->v, (int)side->span, d_lr_side,
+                                bc1s, bc2s, side->grad_scale, zero_side, coef, skip);
+    else
+        phip_adam_flat_pair(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
+                            adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, side->weights[0],
+                            side->grad_weights[0], side->m, side->v, (int)side->span, lr_side, bc1s, bc2s,
+                            side->grad_scale, zero_side, coef, skip);
     return (w16 != NULL) | (zero_g ? 2 : 0) | (zero_side ? 4 : 0);
+}
+
+int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
+                         int zero_side, const float* coef, const unsigned* skip) {
+    return adam_update_pair_dev(adam, lr, NULL, w16, n16, zero_g, side, lr_side, NULL, zero_side, coef, skip);
+}
+
+int adam_update_pair_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, Adam* side,
+                         const float* d_lr_side, int zero_side, const float* coef, const unsigned* skip) {
+    if (!d_lr || !d_lr_side) die("adam_update_pair_lrp: NULL rate");
+    return adam_update_pair_dev(adam, 0.f, d_lr, w16, n16, zero_g, side, 0.f, d_lr_side, zero_side, coef, skip);
 }
 
 /* ---------------- checkpoint (adam.cu:172-264 byte layout) ---------------- */

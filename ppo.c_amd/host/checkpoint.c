@@ -89,12 +89,15 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     const size_t S = (size_t)tb->state_size, A = (size_t)tb->action_size;
     const int with_buffer = (flags & PPO_CKPT_BUFFER) != 0;
     const int with_rollout = d->ro_cont != NULL && d->ro_E > 0;
+    /* a schedule other than the constant one: with it off the image is what it always was, byte for byte */
+    const int with_lr = d->lr_kind != PPO_LR_CONSTANT;
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
     put_u32(img, CKPT_VERSION);
-    put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u));
-    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer);
+    put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
+                     (with_lr ? CKPT_F_LRSCHED : 0u));
+    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -190,6 +193,20 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_pad(&s, 4);
         if (W) put_dev(&s, d->mask, sizeof(uint32_t) * n * W);
         put_section(img, CKPT_TAG_BUFFER, &s);
+        free(s.p);
+    }
+
+    if (with_lr) {
+        const int adaptive = d->lr_kind == PPO_LR_ADAPTIVE;
+        memset(&s, 0, sizeof(s));
+        put_u32(&s, (uint32_t)d->lr_kind);
+        for (int i = 0; i < 3; i++) put_f32(&s, d->lr_p[i]);
+        put_u32(&s, (uint32_t)(d->lr_couple != 0));
+        put_u32(&s, 0);
+        put_u64(&s, d->lr_u);
+        put_dev(&s, adaptive ? &d->kl->lr : NULL, 2 * sizeof(float));               /* lr, lr_v */
+        put_dev(&s, adaptive ? &d->kl->lr_raised : NULL, 2 * sizeof(unsigned));     /* raised, lowered */
+        put_section(img, CKPT_TAG_LRSCHED, &s);
         free(s.p);
     }
     return 0;
@@ -375,6 +392,20 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
             if (W) phip_h2d(ppo_action_mask_buffer(ppo), p, sizeof(uint32_t) * n * W);
         }
         buffer_point_device(tb);
+    }
+
+    /* the learning-rate schedule through its setter, then the state the setter restarted */
+    if (ix->sec[CKPT_TAG_LRSCHED].present) {
+        const uint8_t* lr = img + ix->sec[CKPT_TAG_LRSCHED].off;
+        const int kind = (int)ckpt_rd32(lr);
+        if (ppo_set_lr_schedule(ppo, kind, get_f32(lr + 4), get_f32(lr + 8), get_f32(lr + 12)) != 0)
+            return "a learning-rate schedule ppo_set_lr_schedule declines";
+        ppo_lr_couple_value(ppo, (int)ckpt_rd32(lr + 16));
+        d->lr_u = ckpt_rd64(lr + 24);
+        if (kind == PPO_LR_ADAPTIVE) {
+            phip_h2d(&d->kl->lr, lr + 32, 2 * sizeof(float));
+            phip_h2d(&d->kl->lr_raised, lr + 40, 2 * sizeof(unsigned));
+        }
     }
     phip_sync();
     return NULL;

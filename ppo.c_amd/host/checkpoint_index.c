@@ -6,6 +6,7 @@
  */
 #include "checkpoint.h"
 
+#include <math.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -39,6 +40,13 @@ static int fail_tag(CkptIndex* ix, const char* what, uint32_t tag) {
 
 static int is01(uint32_t v) { return v <= 1u; }
 
+static float rd_f32(const uint8_t* p) {
+    const uint32_t u = ckpt_rd32(p);
+    float v;
+    memcpy(&v, &u, 4);
+    return v;
+}
+
 /* every known section's length and fields against the shapes of the legacy header (all sizes in uint64: S and A
  * are bounded below so that no product can wrap) */
 static int check_sections(const uint8_t* img, CkptIndex* ix) {
@@ -49,6 +57,8 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         return fail(ix, "the header's buffer flag and the Buffer section disagree");
     if (((ix->flags & CKPT_F_ROLLOUT) != 0) != (s[CKPT_TAG_ROLLOUT].present != 0))
         return fail(ix, "the header's rollout flag and the Rollout section disagree");
+    if (((ix->flags & CKPT_F_LRSCHED) != 0) != (s[CKPT_TAG_LRSCHED].present != 0))
+        return fail(ix, "the header's schedule flag and the learning-rate schedule section disagree");
 
     /* Legacy: five floats, then state size, action size, capacity */
     if (s[CKPT_TAG_LEGACY].len < 32) return fail_tag(ix, "shorter than the legacy header", CKPT_TAG_LEGACY);
@@ -121,6 +131,31 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
                               4ull * limit * W;
         if (s[CKPT_TAG_BUFFER].len != want) return fail_tag(ix, "length contradicts its shapes", CKPT_TAG_BUFFER);
     }
+
+    /* the learning-rate schedule: a kind other than constant, its parameters inside the setter's ranges, rates the
+     * rule could have left (inside [lr_min, lr_max]; zeros for the linear kind, which keeps none) */
+    if (s[CKPT_TAG_LRSCHED].present) {
+        if (s[CKPT_TAG_LRSCHED].len != CKPT_LRSCHED_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_LRSCHED);
+        const uint8_t* lr = img + s[CKPT_TAG_LRSCHED].off;
+        const uint32_t kind = ckpt_rd32(lr);
+        const float p0 = rd_f32(lr + 4), p1 = rd_f32(lr + 8), p2 = rd_f32(lr + 12);
+        const float w = rd_f32(lr + 32), wv = rd_f32(lr + 36);
+        if (!is01(ckpt_rd32(lr + 16)) || ckpt_rd32(lr + 20) != 0)
+            return fail_tag(ix, "a flag out of range", CKPT_TAG_LRSCHED);
+        if (kind == (uint32_t)CKPT_LR_LINEAR) {
+            if (!(p0 >= 1.f) || isinf(p0) || !(p1 >= 0.f && p1 <= 1.f) || p2 != 0.f)
+                return fail_tag(ix, "parameters outside the linear schedule's ranges", CKPT_TAG_LRSCHED);
+            if (ckpt_rd64(lr + 32) != 0 || ckpt_rd64(lr + 40) != 0)
+                return fail_tag(ix, "rate words or counters with the linear schedule", CKPT_TAG_LRSCHED);
+        } else if (kind == (uint32_t)CKPT_LR_ADAPTIVE) {
+            if (!(p0 > 0.f) || isinf(p0) || !(p1 > 0.f) || !(p2 >= p1) || isinf(p2))
+                return fail_tag(ix, "parameters outside the adaptive schedule's ranges", CKPT_TAG_LRSCHED);
+            if (!(w >= p1 && w <= p2) || !(wv >= 0.f) || isinf(wv))
+                return fail_tag(ix, "a rate outside [lr_min, lr_max]", CKPT_TAG_LRSCHED);
+        } else {
+            return fail_tag(ix, "unknown schedule kind", CKPT_TAG_LRSCHED);
+        }
+    }
     return 0;
 }
 
@@ -133,7 +168,7 @@ int ckpt_index(const void* buf, size_t len, CkptIndex* ix) {
     ix->flags = ckpt_rd32(img + 12);
     ix->count = ckpt_rd32(img + 16);
     if (ix->version != CKPT_VERSION) return fail(ix, "unsupported version (this reader knows version 1)");
-    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT)) return fail(ix, "unknown header flags");
+    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED)) return fail(ix, "unknown header flags");
     if (ix->count > (len - CKPT_HEADER_BYTES) / CKPT_SECTION_BYTES)
         return fail(ix, "more sections than the file could hold");
     size_t pos = CKPT_HEADER_BYTES;

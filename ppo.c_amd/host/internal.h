@@ -90,6 +90,12 @@ int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, in
                          const unsigned* skip);
 int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
                          int zero_side, const float* coef, const unsigned* skip);
+/* the same two steps with the learning rate(s) read from device words by the kernels' pointer variants (the
+ * KL-adaptive schedule's policy rate, a coupled value rate: csrc/kl.hip PhipKlRec.lr / lr_v) */
+int adam_update_cuda_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, const float* coef,
+                         const unsigned* skip);
+int adam_update_pair_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, Adam* side,
+                         const float* d_lr_side, int zero_side, const float* coef, const unsigned* skip);
 
 /* checkpoint Adam with a known tensor count (n_expected < 0: unknown); rejects mismatches */
 Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda);

@@ -88,6 +88,27 @@ static PPODev* dev_ws(PPO* ppo, int B) {
 
 PPODev* ppo_dev(PPO* ppo) { return dev_ws(ppo, 1); }
 
+/* learning-rate schedules (ppo_ext.h ppo_set_lr_schedule) */
+static int lr_adaptive(const PPODev* d) { return d && d->lr_kind == PPO_LR_ADAPTIVE; }
+/* the KL monitor's setting: the caller's target_kl, or — while the adaptive schedule is on and target KL is off —
+ * +inf: measure every policy step, never stop */
+static float kl_target(const PPODev* d) {
+    return d->target_kl > 0.f ? d->target_kl : lr_adaptive(d) ? INFINITY : 0.f;
+}
+static float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
+/* linear decay: (float)(base · (1 − (1 − f)·(min(u, N)/N))) in double, rounded once; the quotient first, so that
+ * u >= N gives exactly (float)(base · f) for every N */
+static float lr_linear(float base, const PPODev* d) {
+    const double N = (double)d->lr_p[0], f = (double)d->lr_p[1];
+    const double u = (double)d->lr_u < N ? (double)d->lr_u : N;
+    return (float)((double)base * (1.0 - (1.0 - f) * (u / N)));
+}
+void ppo_dev_lr_now(PPO* ppo, PPODev* d, float* out2) {
+    const int lin = d->lr_kind == PPO_LR_LINEAR;
+    out2[0] = lin ? lr_linear(ppo->lr_policy, d) : ppo->lr_policy;
+    out2[1] = lin ? lr_linear(ppo->lr_V, d) : ppo->lr_V;
+}
+
 static void free_dev_ws(PPO* ppo) {
     PPODev* d = (PPODev*)ppo->dev;
     if (!d) return;
@@ -493,12 +514,15 @@ static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
  * zero_grads: the same pass clears the gradients it read (the next backward skips its memset);
  * coef: NULL, or the step's device clip coefficient; skip: NULL, or the device stop word of target-KL
  * early stopping */
-static int adam_update_net(Adam* adam, float lr, NeuralNetwork* nn, int zero_grads, const float* coef,
-                           const unsigned* skip) {
+static int adam_update_net(Adam* adam, float lr, const float* d_lr, NeuralNetwork* nn, int zero_grads,
+                           const float* coef, const unsigned* skip) {
     const int own = adam->flat && adam->weights[0] == nn->d_params && adam->grad_weights[0] == nn->d_grads;
     const int fused = nn->dtype == 1 && own;
-    const int r = adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own, coef,
-                                       skip);
+    /* d_lr (NULL: lr by value, the kernels and bits as ever): the rate in a device word (the adaptive schedule) */
+    const int r = d_lr ? adam_update_cuda_lrp(adam, d_lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own,
+                                              coef, skip)
+                       : adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own,
+                                              coef, skip);
     /* a skipped step left the parameters, hence their shadow, as they were: the refresh rewrites the same bits */
     if (!(r & 1) && nn->dtype == 1) nn_sync_w16(nn);
     return (r & 2) != 0;                 /* the network's gradients are zero again */
@@ -571,7 +595,7 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
      * with gradient clipping on, the update takes the multi-launch loop */
     if (d->max_grad_norm > 0.f) return -1;
     /* … and they neither measure the KL nor read a stop word: target-KL early stopping takes that loop too */
-    if (d->target_kl > 0.f) return -1;
+    if (kl_target(d) > 0.f) return -1;
     /* … and their value heads are plain MSE: value-loss clipping takes that loop as well */
     if (d->value_clip > 0.f) return -1;
     /* … and their policy heads are Gaussian: a categorical policy takes that loop too */
@@ -624,7 +648,7 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
         pv.n_epochs = n_epochs_value;
         pv.max_steps = cap_v;
         pv.perms = tiny_perms(ppo, d, shuffle_mode, n_epochs_value, limit, &pv);
-        pv.steps = tiny_steps(d, 0, ppo->adam_V, ppo->lr_V, (int)cap_v);
+        pv.steps = tiny_steps(d, 0, ppo->adam_V, d->lr_use[1], (int)cap_v);
     } else if (n_epochs_value > 0) {
         for (int j = 0; j < n_epochs_value; j++) { uint64_t key; next_perm(ppo, d, shuffle_mode, &key); }
     }
@@ -635,8 +659,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
         pp.perms = tiny_perms(ppo, d, shuffle_mode, n_epochs_policy, limit, &pp);
         /* per step the entropy Adam steps before the policy Adam (ppo.cu:440-442); their step
          * counters are independent, so the two sequences can be generated one after the other */
-        pp.steps_ls = tiny_steps(d, 1, ppo->adam_entropy, ppo->lr_policy, (int)cap_p);
-        pp.steps = tiny_steps(d, 2, ppo->adam_policy, ppo->lr_policy, (int)cap_p);
+        pp.steps_ls = tiny_steps(d, 1, ppo->adam_entropy, d->lr_use[0], (int)cap_p);
+        pp.steps = tiny_steps(d, 2, ppo->adam_policy, d->lr_use[0], (int)cap_p);
     } else if (n_epochs_policy > 0) {
         for (int j = 0; j < n_epochs_policy; j++) { uint64_t key; next_perm(ppo, d, shuffle_mode, &key); }
     }
@@ -748,8 +772,10 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
         adam_net_tab(ppo->adam_V, V, d, 0, 0);
         return 1;
     }
-    return adam_update_net(ppo->adam_V, ppo->lr_V, V, iv + 1 < c->nv,
-                           clip_coef(d, 0, ppo->adam_V, NULL, 0), NULL);
+    /* the value rate: by value (the schedule's, d->lr_use), or — the adaptive schedule with coupling — the word the
+     * coupling launch wrote ahead of the loops */
+    return adam_update_net(ppo->adam_V, d->lr_use[1], lr_adaptive(d) && d->lr_couple ? &d->kl->lr_v : NULL, V,
+                           iv + 1 < c->nv, clip_coef(d, 0, ppo->adam_V, NULL, 0), NULL);
 }
 
 static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab) {
@@ -829,10 +855,11 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
      * same stream and communicator, and a one-workgroup launch decides from the global sums after the join:
      * every rank decides from the same bits.  The extra collective is a function of the setting only, so
      * the fixed order of collectives (comm.hip) holds as long as every rank holds the same target_kl. */
-    const int kl_on = !tab && d->target_kl > 0.f;
+    const float target_kl = kl_target(d);
+    const int kl_on = !tab && target_kl > 0.f;
     const long kl_rows = (long)B * phip_comm_world();
     if (kl_on && c->comm) {
-        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
+        phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
                        0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
@@ -851,10 +878,12 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const float* coef = clip_coef(d, 1, ap, pol->d_log_std_grad, A);
     const unsigned* skip = NULL;
     if (kl_on) {
-        if (!ap->flat || !ppo->adam_entropy->flat) die("ppo_update: target-KL early stopping needs flat Adam spans");
-        if (c->comm) phip_kl_decide(d->kl, d->target_kl, kl_rows);
+        if (!ap->flat || !ppo->adam_entropy->flat)
+            die(d->target_kl > 0.f ? "ppo_update: target-KL early stopping needs flat Adam spans"
+                                   : "ppo_update: the adaptive learning-rate schedule needs flat Adam spans");
+        if (c->comm) phip_kl_decide(d->kl, target_kl, kl_rows);
         else
-            phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, d->target_kl, kl_rows,
+            phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
                            1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
         skip = &d->kl->stopped;
     }
@@ -865,18 +894,23 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const int own = ap->flat && ap->weights[0] == mu->d_params && ap->grad_weights[0] == mu->d_grads;
     const int fused = mu->dtype == 1 && own;
     const int ls_own = ppo->adam_entropy->flat && ppo->adam_entropy->grad_weights[0] == pol->d_log_std_grad;
-    const int r = adam_update_pair_w16(ap, ppo->lr_policy, fused ? mu->d_w16 : NULL, mu->num_params,
-                                         clear && own, ppo->adam_entropy, ppo->lr_policy,
-                                         clear && ls_own, coef, skip);
+    /* the policy rate, shared by both Adams as ever: by value, or — the adaptive schedule — the record's word, which
+     * this step's decision has just written */
+    const float lr = d->lr_use[0];
+    const float* d_lr = lr_adaptive(d) ? &d->kl->lr : NULL;
+    const int r = d_lr ? adam_update_pair_lrp(ap, d_lr, fused ? mu->d_w16 : NULL, mu->num_params, clear && own,
+                                              ppo->adam_entropy, d_lr, clear && ls_own, coef, skip)
+                       : adam_update_pair_w16(ap, lr, fused ? mu->d_w16 : NULL, mu->num_params, clear && own,
+                                              ppo->adam_entropy, lr, clear && ls_own, coef, skip);
     if (r >= 0) {
         if (!(r & 1) && mu->dtype == 1) nn_sync_w16(mu);
         *ls_zero = ls_own && (r & 4);
         *p_zero = (r & 2) != 0;
         return;
     }
-    *ls_zero = ls_own &&
-               (adam_update_cuda_w16(ppo->adam_entropy, ppo->lr_policy, NULL, 0, clear, coef, skip) & 2);
-    *p_zero = adam_update_net(ppo->adam_policy, ppo->lr_policy, mu, clear, coef, skip);
+    *ls_zero = ls_own && ((d_lr ? adam_update_cuda_lrp(ppo->adam_entropy, d_lr, NULL, 0, clear, coef, skip)
+                                : adam_update_cuda_w16(ppo->adam_entropy, lr, NULL, 0, clear, coef, skip)) & 2);
+    *p_zero = adam_update_net(ppo->adam_policy, lr, d_lr, mu, clear, coef, skip);
 }
 
 /* target-KL early stopping, at a policy-epoch boundary: the host waits for the policy loop's stream only
@@ -898,7 +932,7 @@ static int step_graphs_ok(const StepCtx* c) {
     const char* e = getenv("PPO_GRAPH");
     if (!(e && *e && *e != '0') || c->comm || phip_comm_world() > 1 || c->B > 2048 || c->A > 32) return 0;
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
-    if (c->d->target_kl > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
+    if (kl_target(c->d) > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
     if (cat_on(c->d)) return 0;                   /* … and a captured policy step's head is the Gaussian one */
     PPO* ppo = c->ppo;
@@ -969,10 +1003,12 @@ static void capture_steps(StepCtx* c, int ph) {
         if (!perms) phip_step_feistel(e, keys[j], c->limit);
         e->offset = k * c->B;
         if (ph) {
-            adam_next_step(ppo->adam_entropy, ppo->lr_policy, &e->step_ls, &e->bc2_ls);   /* ppo.cu:440-442 */
-            adam_next_step(ppo->adam_policy, ppo->lr_policy, &e->step, &e->bc2);
+            /* the rates this update passes by value (d->lr_use: the struct's, or their linear decay), as the eager
+             * first and last steps of the phase take them */
+            adam_next_step(ppo->adam_entropy, d->lr_use[0], &e->step_ls, &e->bc2_ls);     /* ppo.cu:440-442 */
+            adam_next_step(ppo->adam_policy, d->lr_use[0], &e->step, &e->bc2);
         } else {
-            adam_next_step(ppo->adam_V, ppo->lr_V, &e->step, &e->bc2);
+            adam_next_step(ppo->adam_V, d->lr_use[1], &e->step, &e->bc2);
         }
     }
     phip_h2d(d->tab[ph], d->h_tab, sizeof(PhipStepArgs) * (size_t)n);
@@ -1047,9 +1083,9 @@ static void replica_hash(PPO* ppo) {
     PPODev* d = (PPODev*)ppo->dev;
     const int obs = obs_on(d);
     if (obs) obs_ws(ppo, d);      /* on but never folded or set: the zero triple, hashed like a peer's zeros */
-    const float* spans[5] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params, obs ? (const float*)d->obs_run : NULL,
+    const float* spans[6] = {pol->mu->d_params, pol->d_log_std, ppo->V->d_params, obs ? (const float*)d->obs_run : NULL,
                              NULL};
-    long lens[5] = {pol->mu->num_params, pol->action_size, ppo->V->num_params,
+    long lens[6] = {pol->mu->num_params, pol->action_size, ppo->V->num_params,
                     obs ? 2 * (1 + 2L * ppo->buffer->state_size) : 0, 0};
     int n_spans = obs ? 4 : 3;
     /* … and, while reward normalisation is on, the returns' running triple (3 doubles), likewise */
@@ -1057,6 +1093,11 @@ static void replica_hash(PPO* ppo) {
         rew_ws(d);
         spans[n_spans] = (const float*)d->rew_run;
         lens[n_spans++] = 6;
+    }
+    /* … and, while the adaptive learning-rate schedule is on, the record's two rate words (lr, lr_v) */
+    if (lr_adaptive(d)) {
+        spans[n_spans] = &d->kl->lr;
+        lens[n_spans++] = 2;
     }
     phip_param_hash(spans, lens, n_spans);
 }
@@ -1092,6 +1133,7 @@ void ppo_update(void* vppo, float gamma, int batch_size, int n_epochs_policy, in
                 unsigned long long seed) {
     PPO* ppo = (PPO*)vppo;
     ppo_update_body(ppo, gamma, batch_size, n_epochs_policy, n_epochs_value, shuffle_mode, seed);
+    if (ppo->dev && ((PPODev*)ppo->dev)->lr_kind != PPO_LR_CONSTANT) ((PPODev*)ppo->dev)->lr_u += 1;
     ppo->V->dev_version++;               /* HBM parameters moved (also by the single-workgroup path) */
     ppo->policy->mu->dev_version++;
     /* replicated Adam must leave every rank with the same parameters; a rank that drifted
@@ -1115,6 +1157,9 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const int S = buf->state_size, A = buf->action_size, B = batch_size;
     const int limit = buf->full ? buf->capacity : buf->idx;
     const int num_batches = buf->capacity / B;                           /* D13 */
+    /* the learning rates this update passes by value: the struct's, or their linear decay at this update's number
+     * (the adaptive schedule's policy rate, and its coupled value rate, are device words instead) */
+    ppo_dev_lr_now(ppo, d, d->lr_use);
     const int world = phip_comm_world();
     const float gscale = 1.0f / (float)world;
     const int comm = phip_comm_active();
@@ -1179,11 +1224,16 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     if (!graphs) phase_gather(&c);
     /* target-KL early stopping: the stop word, the stop step and the step counter start afresh with every
      * update (stream-ordered, ahead of the fork: the policy loop's stream sees them) */
-    const int kl_on = d->target_kl > 0.f && np > 0;
+    const int kl_on = kl_target(d) > 0.f && np > 0;
     if (kl_on) {
         phip_memset(&d->kl->stopped, 0, 2 * sizeof(unsigned));          /* stopped, step */
         phip_memset(&d->kl->stop_step, 0xFF, sizeof(int));              /* −1 */
     }
+    /* the adaptive schedule's value-rate coupling: one one-thread launch, likewise ahead of the fork, fixes the
+     * value Adam's word for the whole update from the policy rate as the last update left it — the value loop
+     * never reads a word the policy loop writes */
+    if (lr_adaptive(d) && d->lr_couple)
+        phip_lr_couple(d->kl, ppo->lr_V, clampf(ppo->lr_policy, d->lr_p[1], d->lr_p[2]));
     long kl_issued = 0, kl_applied = 0;
     if (concurrent) phip_side_fork();
     long iv = 0, ip = 0;
@@ -1262,6 +1312,7 @@ void ppo_reset_stats(void* vppo) {
     /* norm, coef and the clipped-step counter (the 16 bytes ahead of the ticket) */
     for (int i = 0; i < 2; i++) phip_memset(d->clip[i], 0, offsetof(PhipClipRec, ticket));
     phip_memset(d->kl, 0, offsetof(PhipKlRec, ticket));      /* the head: KL, clip fraction, stop state, applied */
+    phip_memset(&d->kl->lr_raised, 0, 2 * sizeof(unsigned)); /* the adaptive schedule's raises and lowerings */
     phip_memset(d->vclip_counts, 0, 2 * sizeof(unsigned long long));
     d->n_v = d->n_p = d->n_graph = 0;
 }
@@ -1272,8 +1323,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[25] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[29] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1282,7 +1333,7 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[11 + i] = (double)r.clipped;
         }
     }
-    if (n > 13 && d->target_kl > 0.f) {         /* target-KL early stopping: zeros while it is off */
+    if (n > 13 && kl_target(d) > 0.f) {         /* target-KL early stopping (or the adaptive rate's monitor): zeros while off */
         PhipKlRec r;
         phip_d2h(&r, d->kl, offsetof(PhipKlRec, ticket));
         v[13] = r.kl;
@@ -1315,7 +1366,19 @@ void ppo_read_stats(void* vppo, double* out, int n) {
         phip_d2h(&h, d->cat_ent, sizeof(float));
         v[4] = d->cat_rows > 0 ? (double)h / d->cat_rows : 0.0;
     }
-    for (int i = 0; i < n && i < 25; i++) out[i] = v[i];
+    if (n > 25) {            /* the learning rates in use, and the adaptive schedule's raises and lowerings */
+        double lr[2];
+        ppo_get_lr(ppo, lr);
+        v[25] = lr[0];
+        v[26] = lr[1];
+        if (lr_adaptive(d)) {
+            unsigned cnt[2];
+            phip_d2h(cnt, &d->kl->lr_raised, sizeof(cnt));
+            v[27] = (double)cnt[0];
+            v[28] = (double)cnt[1];
+        }
+    }
+    for (int i = 0; i < n && i < 29; i++) out[i] = v[i];
 }
 
 /* ppo_ext.h: running return-based reward normalisation */
@@ -1655,11 +1718,89 @@ float ppo_get_target_kl(void* vppo) {
     return ppo->dev ? ((PPODev*)ppo->dev)->target_kl : 0.f;
 }
 
+/* ppo_ext.h: learning-rate schedules */
+int ppo_set_lr_schedule(void* vppo, int kind, float p0, float p1, float p2) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || isnan(p0) || isnan(p1) || isnan(p2)) return -1;
+    if (kind == PPO_LR_LINEAR) {
+        if (!(p0 >= 1.f) || isinf(p0) || !(p1 >= 0.f && p1 <= 1.f)) return -1;
+    } else if (kind == PPO_LR_ADAPTIVE) {
+        if (!(p0 > 0.f) || isinf(p0) || !(p1 > 0.f) || isinf(p1) || !(p2 >= p1) || isinf(p2)) return -1;
+    } else if (kind != PPO_LR_CONSTANT) {
+        return -1;
+    }
+    PPODev* d = dev_ws(ppo, 1);
+    const int on = kind == PPO_LR_ADAPTIVE;
+    /* the record's share: the rate, the coupled value rate (the base until the first coupling launch), the rule's
+     * parameters (lr_kl = 0 turns the rule off inside decide()) and the counters — stream-ordered, like every write
+     * to the record */
+    const float words[5] = {on ? clampf(ppo->lr_policy, p1, p2) : 0.f, on ? ppo->lr_V : 0.f, on ? p0 : 0.f,
+                            on ? p1 : 0.f, on ? p2 : 0.f};
+    phip_sync();
+    phip_h2d(&d->kl->lr, words, sizeof(words));
+    phip_memset(&d->kl->lr_raised, 0, 2 * sizeof(unsigned));
+    d->lr_kind = kind;
+    d->lr_p[0] = kind == PPO_LR_CONSTANT ? 0.f : p0;
+    d->lr_p[1] = kind == PPO_LR_CONSTANT ? 0.f : p1;
+    d->lr_p[2] = kind == PPO_LR_ADAPTIVE ? p2 : 0.f;
+    d->lr_u = 0;
+    return 0;
+}
+
+int ppo_get_lr_schedule(void* vppo, float* out4) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    if (out4) {
+        for (int i = 0; i < 3; i++) out4[i] = d ? d->lr_p[i] : 0.f;
+        out4[3] = d ? (float)d->lr_couple : 0.f;
+    }
+    return d ? d->lr_kind : PPO_LR_CONSTANT;
+}
+
+int ppo_lr_couple_value(void* vppo, int on) {
+    if (!vppo) return -1;
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    const int was = d->lr_couple;
+    d->lr_couple = on != 0;
+    return was;
+}
+
+int ppo_get_lr(void* vppo, double* out2) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !out2) return -1;
+    PPODev* d = dev_ws(ppo, 1);
+    float now[2];
+    ppo_dev_lr_now(ppo, d, now);
+    if (lr_adaptive(d)) {
+        float w[2];
+        phip_sync();
+        phip_d2h(w, &d->kl->lr, sizeof(w));
+        now[0] = w[0];
+        if (d->lr_couple) now[1] = w[1];
+    }
+    out2[0] = now[0];
+    out2[1] = now[1];
+    return 0;
+}
+
+int ppo_lr_history(void* vppo, float* out, int n) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !ppo->dev) return 0;
+    PPODev* d = (PPODev*)ppo->dev;
+    if (!lr_adaptive(d)) return 0;
+    unsigned steps = 0;
+    phip_sync();
+    phip_d2h(&steps, &d->kl->step, sizeof(unsigned));
+    const int have = (int)(steps < (unsigned)PHIP_KL_HIST ? steps : (unsigned)PHIP_KL_HIST);
+    if (out && n > 0 && have > 0) phip_d2h(out, d->kl->lr_hist, sizeof(float) * (size_t)(n < have ? n : have));
+    return (int)steps;
+}
+
 int ppo_kl_history(void* vppo, double* out, int n) {
     PPO* ppo = (PPO*)vppo;
     PPODev* d = dev_ws(ppo, 1);
     phip_sync();
-    if (!(d->target_kl > 0.f)) return 0;
+    if (!(kl_target(d) > 0.f)) return 0;
     unsigned steps = 0;
     phip_d2h(&steps, &d->kl->step, sizeof(unsigned));
     long have = steps < (unsigned)PHIP_KL_HIST ? (long)steps : PHIP_KL_HIST;

@@ -147,12 +147,24 @@ typedef struct {
      * hashed, no collective */
     int mask_on;
     uint32_t* mask;
+    /* learning-rate schedules (ppo_set_lr_schedule; 0 = constant: ppo->lr_policy / lr_V by value, as ever): the kind,
+     * its three parameters, the value-rate coupling of the adaptive kind and the updates since the setter.  The
+     * adaptive kind's rates, its parameters' device copy, its two counters and the per-step rate history live in the
+     * KL record (`kl`: lr, lr_v, lr_kl, lr_min, lr_max, lr_raised, lr_lowered, lr_hist).  lr_use: the rates this
+     * update passes by value {policy, value} */
+    int lr_kind;
+    float lr_p[3];
+    int lr_couple;
+    unsigned long long lr_u;
+    float lr_use[2];
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */
 PPODev* ppo_dev(PPO* ppo);
 /* ppo.c: the rollout's row map for E × T (rows[t·E + e] = e·T + t), as the rollouts build it; sets ro_T */
 void ppo_dev_ro_rows(PPODev* d, int E, int T);
+/* ppo.c: the rates an update starting now passes by value {policy, value} under the schedule as it stands */
+void ppo_dev_lr_now(PPO* ppo, PPODev* d, float* out2);
 /* ppo.c: save_ppo's byte stream into an open file, and load_ppo's read of it */
 void save_ppo_file(PPO* ppo, FILE* f);
 PPO* load_ppo_file(FILE* f, bool use_cuda);

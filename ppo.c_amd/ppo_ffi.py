@@ -155,6 +155,12 @@ _SIGS = {
     "ppo_get_target_kl": (C.c_float, [_P]),
     "ppo_kl_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "ppo_policy_kl_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double)]),
+    "ppo_set_lr_schedule": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_float]),
+    "ppo_get_lr_schedule": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ppo_lr_couple_value": (C.c_int, [_P, C.c_int]),
+    "ppo_get_lr": (C.c_int, [_P, C.POINTER(C.c_double)]),
+    "ppo_lr_history": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "ppo_adam_update_lr_device": (C.c_int, [_P, _P]),
     "ppo_policy_head_device": (C.c_int, [C.c_int] * 5 + [C.c_float] * 2 + [_P] * 13 + [C.POINTER(C.c_double)]),
     "ppo_set_action_dist": (C.c_int, [_P, C.c_int]),
     "ppo_get_action_dist": (C.c_int, [_P]),
