@@ -128,6 +128,9 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[25]=the policy learning rate in use, out[26]=the value learning rate in use (ppo_get_lr), out[27]=policy steps
  * that raised the rate, out[28]=policy steps that lowered it, both since the last reset (the adaptive schedule,
  * ppo_set_lr_schedule: both 0 under the other schedules; callers passing n <= 25 see no change).
+ * out[29]=the advantage-normalisation mode (ppo_set_adv_norm), out[30] / out[31]=the smallest / largest segment sd of
+ * the last update's per-minibatch normalisation (NaN if a segment's sd is NaN; under data parallelism THIS RANK's
+ * segments) (all three 0 while it is off; callers passing n <= 29 see no change).
  * With the categorical policy (ppo_set_action_dist 1) — or the multi-discrete one, its joint row entropy — out[4] is the
  * mean row entropy of the last policy step's
  * minibatch (Σ H / rows as the head accumulated it; 0 before the first policy step; under data parallelism THIS
@@ -181,6 +184,54 @@ int    ppo_kl_history(void* ppo, double* out, int n);
  * [m] → out2 = {approximate KL, clip fraction}; returns 0, −1 for bad arguments; synchronises */
 int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
                             int m, int A, float eps, double* out2);
+/* Per-minibatch advantage normalisation (off by default; not in the reference, whose gae normalises once per update
+ * over the whole buffer: A ← (A − μ)/(σ_pop + 1e-8), which libppo keeps doing in every mode; Stable-Baselines3
+ * normalize_advantage = True and CleanRL norm_adv = True, both their defaults).  With PPO_ADV_NORM_MINIBATCH every
+ * policy minibatch's advantages are normalised again over that minibatch alone before its head reads them.  The
+ * definition (csrc/advnorm.h, which this quotes): a segment x_0 … x_{B−1} — the B advantages of one policy
+ * minibatch, as GAE's global normalisation left them — becomes
+ *     p_t  = Σ_{i ≡ t (mod 256), i ascending} (double)x_i          t = 0 … 255
+ *     S    = pairwise tree over p (stride 1, 2, 4 … 128: p_t += p_{t+stride} for t a multiple of 2·stride)
+ *     mean = S / B                                                  (double)
+ *     q_t, Q likewise over d_i·d_i,  d_i = (double)x_i − mean       (product rounded, then added: no FMA)
+ *     sd   = (float)sqrt(Q / max(B − 1, 1))                         (the unbiased std of torch.Tensor.std)
+ *     m    = (float)mean
+ *     y_i  = (float)((double)(x_i − m) / ((double)sd + 1e-8))       (the form of gae.hip's normalize_kernel)
+ * A NaN propagates within its own segment only; a constant segment gives y = 0; B == 1 gives y = 0.  Because the map
+ * is invariant under the global affine map GAE applied first, y equals Stable-Baselines3's / CleanRL's
+ * (a − a.mean())/(a.std() + 1e-8) of the raw minibatch advantages a up to rounding and the two 1e-8 terms — it is not
+ * bit-equal to them.
+ * The work is one launch per ppo_update (csrc/advnorm.hip: one 256-thread workgroup per segment, no floating-point
+ * atomics, the outputs a function of (B, data) alone), ahead of the value and policy loops, over the copy of the
+ * policy phase's advantages the update gathers up front: the trajectory buffer's `advantage` array is never written,
+ * and every form of the policy head (fused, wide, plain, categorical, multi-discrete, masked; fp32 on both GEMM
+ * engines, bf16 mode) reads the rewritten segment unchanged.  While it is on, ppo_update runs the multi-launch loop
+ * (no single-workgroup / cluster phases, no graph replay — they gather for themselves), as with value-loss clipping,
+ * and works together with gradient clipping, target KL (segments normalised for steps it leaves unissued are never
+ * read), value clipping, both normalisers, the schedules and the step limit.  Under data parallelism each rank
+ * normalises its own minibatch shard (CleanRL under DDP does the same): no collective is added, the order of
+ * collectives does not depend on the setting, and the replicas stay identical because the gradients are still
+ * all-reduced; EVERY RANK SHOULD HOLD THE SAME SETTING, or the ranks train one model on differently scaled
+ * advantages.  With the mode global no launch is added, nothing is allocated and every path gives the bits it
+ * always gave.  Not part of a checkpoint (save_ppo's; ppo_save_state keeps it): set it again after load_ppo.
+ * Returns 0, or −1 (setting unchanged) for a NULL ppo or an unknown mode. */
+enum { PPO_ADV_NORM_GLOBAL = 0, PPO_ADV_NORM_MINIBATCH = 1 };
+int ppo_set_adv_norm(void* ppo, int mode);
+int ppo_get_adv_norm(void* ppo);             /* the mode; 0 for NULL */
+/* the update's kernel on caller-supplied device arrays: n_seg segments of B floats, segment s at [s·B, (s+1)·B);
+ * d_out may be d_in (no other overlap); d_stats (may be NULL) [n_seg][2] ← (m, sd).  Returns 0, or −1 for a NULL
+ * array, n_seg <= 0 (or above 2^31 − 1) or B <= 0; synchronises */
+int ppo_adv_normalize_device(const float* d_in, float* d_out, long n_seg, int B, float* d_stats);
+/* (m, sd) of every policy segment the last ppo_update normalised, in step order, into out[0, 2·min(n, steps));
+ * returns steps — the update's policy steps after ppo_set_step_limit's cap, those target KL left unissued
+ * included (0 while the mode is global); synchronises */
+int ppo_adv_norm_history(void* ppo, float* out, int n);
+/* host copies of policy step `step` of the last ppo_update: its B buffer row indices and the B advantages its head
+ * read — normalised while the mode is minibatch, the gathered ones while it is global (rows / adv may be NULL).
+ * Returns B, or −1 for a bad step, cap < B, or an update that kept no gather (the single-workgroup / cluster phases,
+ * graph replay); synchronises */
+int ppo_adv_norm_read(void* ppo, long step, int* rows, float* adv, int cap);
+
 /* Learning-rate schedules (constant by default; not in the reference).  kind picks one; p0 … p2 are its parameters.
  *   PPO_LR_CONSTANT  today's behaviour on today's code path, bit for bit: ppo->lr_policy and ppo->lr_V are read from
  *                    the struct by every update and passed to the Adam kernels by value.  p0 … p2 are ignored.
@@ -783,8 +834,9 @@ int ppo_nn_input_rows(void* nn, float* out, int m);
  * normaliser states and episode statistics as if it had never stopped (DESIGN.md §4 "Training-state checkpoints"
  * gives the file format).  A checkpoint is D2H / H2D copies between updates: no kernel, nothing on the update or
  * rollout path changes.
- * WHAT IS KEPT: save_ppo's byte stream itself; the settings — max_grad_norm, target_kl, value_clip, both normalisers'
- * clip and freeze flag, the episode tracker's gamma, the action distribution with nvec, masking, both networks'
+ * WHAT IS KEPT: save_ppo's byte stream itself; the settings — max_grad_norm, target_kl, value_clip, the
+ * advantage-normalisation mode (a section of its own, written only while the mode is not the global one, so images
+ * of PPOs that never set it are what they always were), both normalisers' clip and freeze flag, the episode tracker's gamma, the action distribution with nvec, masking, both networks'
  * compute dtype (applied on load through their setters: the distribution before the mask, the dtype last); both
  * normalisers' running triples (the fp32 pair and scale are refreshed on load as _set_state refreshes them); the
  * device shuffle's epoch key; and, once a rollout has run, the rollout's state — the built-in environments' device

@@ -184,6 +184,12 @@ void phip_episode_scan(const float* reward, const uint8_t* term, const uint8_t* 
                        double* row_disc, double* out, double* window);
 void phip_mean_action(const float* mu, float* action, long n);      /* action[0:n] ← mu[0:n], bit for bit */
 
+/* ---------------- per-minibatch advantage normalisation (advnorm.hip) ---------------- */
+/* The map of advnorm.h over n_seg segments of B floats, one launch, one 256-thread workgroup per segment: segment s
+ * is in[s·B, (s+1)·B) → out likewise (out == in is legal; any other overlap is not); stats (may be NULL)
+ * [n_seg][2] ← (m, sd).  n_seg <= 2^31 − 1. */
+void phip_adv_normalize(const float* in, float* out, long n_seg, int B, float* stats);
+
 /* ---------------- single-workgroup update phase for small networks (tiny.hip) ---------------- */
 typedef struct {
     int L;                          /* linear layers (≤ 8) */

@@ -91,13 +91,15 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     const int with_rollout = d->ro_cont != NULL && d->ro_E > 0;
     /* a schedule other than the constant one: with it off the image is what it always was, byte for byte */
     const int with_lr = d->lr_kind != PPO_LR_CONSTANT;
+    /* … and an advantage-normalisation mode other than the global one, likewise */
+    const int with_adv = d->adv_norm_mode != PPO_ADV_NORM_GLOBAL;
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
     put_u32(img, CKPT_VERSION);
     put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
-                     (with_lr ? CKPT_F_LRSCHED : 0u));
-    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr);
+                     (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u));
+    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -207,6 +209,14 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_dev(&s, adaptive ? &d->kl->lr : NULL, 2 * sizeof(float));               /* lr, lr_v */
         put_dev(&s, adaptive ? &d->kl->lr_raised : NULL, 2 * sizeof(unsigned));     /* raised, lowered */
         put_section(img, CKPT_TAG_LRSCHED, &s);
+        free(s.p);
+    }
+
+    if (with_adv) {
+        memset(&s, 0, sizeof(s));
+        put_u32(&s, (uint32_t)d->adv_norm_mode);
+        put_u32(&s, 0);
+        put_section(img, CKPT_TAG_ADVNORM, &s);
         free(s.p);
     }
     return 0;
@@ -407,6 +417,11 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
             phip_h2d(&d->kl->lr_raised, lr + 40, 2 * sizeof(unsigned));
         }
     }
+
+    /* the advantage-normalisation mode through its setter */
+    if (ix->sec[CKPT_TAG_ADVNORM].present &&
+        ppo_set_adv_norm(ppo, (int)ckpt_rd32(img + ix->sec[CKPT_TAG_ADVNORM].off)) != 0)
+        return "an advantage-normalisation mode ppo_set_adv_norm declines";
     phip_sync();
     return NULL;
 }

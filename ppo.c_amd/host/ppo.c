@@ -136,6 +136,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ev_cont); phip_free(d->ev_agg);
     phip_free(d->ext_obs); phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
     phip_free(d->mask);
+    phip_free(d->adv_stats);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -598,6 +599,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
     if (kl_target(d) > 0.f) return -1;
     /* … and their value heads are plain MSE: value-loss clipping takes that loop as well */
     if (d->value_clip > 0.f) return -1;
+    /* … and they gather their own advantages: per-minibatch advantage normalisation takes that loop too */
+    if (d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return -1;
     /* … and their policy heads are Gaussian: a categorical policy takes that loop too */
     if (cat_on(d)) return -1;
     PhipTinyNet nv, np;
@@ -935,6 +938,7 @@ static int step_graphs_ok(const StepCtx* c) {
     if (kl_target(c->d) > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
     if (cat_on(c->d)) return 0;                   /* … and a captured policy step's head is the Gaussian one */
+    if (c->d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return 0;   /* … and a captured policy step gathers for itself */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
     for (int i = 0; i < 3; i++) {
@@ -1149,6 +1153,8 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     if (!buf->on_device) die("ppo_update: buffer must be device-resident (buffer_to_device / ppo_fill_synthetic)");
     if (batch_size <= 0) die("ppo_update: batch_size must be positive");
     PPODev* d = dev_ws(ppo, batch_size);
+    d->gat_np = d->adv_np = 0;            /* what ppo_adv_norm_read / _history may read: this update's, once gathered */
+    d->gat_B = 0;
     if (shuffle_mode == PPO_SHUFFLE_DEVICE && (!d->seeded || d->seed != seed)) {
         d->seed = seed;
         d->key = splitmix64(seed);
@@ -1221,7 +1227,25 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const int graphs = step_graphs_ok(&c);
     /* eager steps: every step's gathered inputs up front (one launch per epoch instead of one per
      * step; on libppo's stream before the fork, so both loops see them) */
-    if (!graphs) phase_gather(&c);
+    if (!graphs) {
+        phase_gather(&c);
+        d->gat_np = np;
+        d->gat_B = B;
+        /* per-minibatch advantage normalisation (off: nothing launched, nothing allocated): one launch over the
+         * gathered copy of the policy phase's advantages, on libppo's stream ahead of the fork — segment ip is what
+         * policy step ip's head reads through its adv pointer, whichever form of the head it is; the buffer's
+         * advantage array is never written.  Target-KL early stopping may leave steps unissued: their segments are
+         * normalised and never read.  Per rank and element-wise across segments: no collective. */
+        if (d->adv_norm_mode == PPO_ADV_NORM_MINIBATCH && np > 0) {
+            if (np > d->adv_cap) {
+                phip_free(d->adv_stats);
+                d->adv_stats = (float*)phip_malloc(sizeof(float) * 2 * (size_t)np);
+                d->adv_cap = np;
+            }
+            phip_adv_normalize(d->ph_adv, d->ph_adv, np, B, d->adv_stats);
+            d->adv_np = np;
+        }
+    }
     /* target-KL early stopping: the stop word, the stop step and the step counter start afresh with every
      * update (stream-ordered, ahead of the fork: the policy loop's stream sees them) */
     const int kl_on = kl_target(d) > 0.f && np > 0;
@@ -1323,8 +1347,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[29] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[32] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1378,7 +1402,24 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[28] = (double)cnt[1];
         }
     }
-    for (int i = 0; i < n && i < 29; i++) out[i] = v[i];
+    if (n > 29 && d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) {    /* advantage normalisation: zeros while it is off */
+        v[29] = (double)d->adv_norm_mode;
+        if (d->adv_np > 0) {
+            float* h = (float*)xmalloc(sizeof(float) * 2 * (size_t)d->adv_np);
+            phip_d2h(h, d->adv_stats, sizeof(float) * 2 * (size_t)d->adv_np);
+            float lo = h[1], hi = h[1];
+            for (long i = 1; i < d->adv_np; i++) {
+                const float sd = h[2 * i + 1];
+                /* a NaN segment shows in both: the comparisons below are false for NaN, so it is carried by hand */
+                lo = isnan(lo) || isnan(sd) ? NAN : sd < lo ? sd : lo;
+                hi = isnan(hi) || isnan(sd) ? NAN : sd > hi ? sd : hi;
+            }
+            free(h);
+            v[30] = lo;
+            v[31] = hi;
+        }
+    }
+    for (int i = 0; i < n && i < 32; i++) out[i] = v[i];
 }
 
 /* ppo_ext.h: running return-based reward normalisation */
@@ -1703,6 +1744,48 @@ int ppo_value_clip_head_device(const float* d_y, const float* d_v_old, const int
     out3[1] = (double)c[0];
     out3[2] = (double)c[1];
     return 0;
+}
+
+/* ppo_ext.h: per-minibatch advantage normalisation */
+int ppo_set_adv_norm(void* vppo, int mode) {
+    if (!vppo || (mode != PPO_ADV_NORM_GLOBAL && mode != PPO_ADV_NORM_MINIBATCH)) return -1;
+    dev_ws((PPO*)vppo, 1)->adv_norm_mode = mode;
+    return 0;
+}
+
+int ppo_get_adv_norm(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo && ppo->dev ? ((PPODev*)ppo->dev)->adv_norm_mode : PPO_ADV_NORM_GLOBAL;
+}
+
+int ppo_adv_normalize_device(const float* d_in, float* d_out, long n_seg, int B, float* d_stats) {
+    if (!d_in || !d_out || n_seg <= 0 || n_seg > 0x7fffffffL || B <= 0) return -1;
+    phip_adv_normalize(d_in, d_out, n_seg, B, d_stats);
+    phip_sync();
+    return 0;
+}
+
+int ppo_adv_norm_history(void* vppo, float* out, int n) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !ppo->dev) return 0;
+    PPODev* d = (PPODev*)ppo->dev;
+    phip_sync();
+    if (d->adv_norm_mode == PPO_ADV_NORM_GLOBAL || d->adv_np <= 0) return 0;
+    const long have = d->adv_np < (long)n ? d->adv_np : (long)n;
+    if (out && have > 0) phip_d2h(out, d->adv_stats, sizeof(float) * 2 * (size_t)have);
+    return (int)d->adv_np;
+}
+
+int ppo_adv_norm_read(void* vppo, long step, int* rows, float* adv, int cap) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !ppo->dev) return -1;
+    PPODev* d = (PPODev*)ppo->dev;
+    if (step < 0 || step >= d->gat_np || cap < d->gat_B) return -1;
+    const size_t B = (size_t)d->gat_B;
+    phip_sync();
+    if (rows) phip_d2h(rows, d->ph_rows[1] + (size_t)step * B, sizeof(int) * B);
+    if (adv) phip_d2h(adv, d->ph_adv + (size_t)step * B, sizeof(float) * B);
+    return d->gat_B;
 }
 
 /* ppo_ext.h: target-KL early stopping */

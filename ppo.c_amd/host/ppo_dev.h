@@ -157,6 +157,17 @@ typedef struct {
     int lr_couple;
     unsigned long long lr_u;
     float lr_use[2];
+    /* per-minibatch advantage normalisation (ppo_set_adv_norm; 0 = GAE's global normalisation alone, as ever;
+     * csrc/advnorm.hip): the mode, and the (m, sd) pair of every policy segment of the last update ([adv_cap][2]
+     * floats; NULL until an update runs with the mode on).  gat_np / gat_B: the policy steps and the minibatch size
+     * of the last update's phase gather (ph_rows[1], ph_adv), 0 when that update kept none (single-workgroup /
+     * cluster phases, graph replay) — what ppo_adv_norm_read may read; adv_np: the segments the last update
+     * normalised (0 while off) */
+    int adv_norm_mode;
+    float* adv_stats;
+    long adv_cap;
+    long gat_np, adv_np;
+    int gat_B;
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

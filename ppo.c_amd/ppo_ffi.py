@@ -188,6 +188,11 @@ _SIGS = {
     "ppo_get_value_clip": (C.c_float, [_P]),
     "ppo_value_clip_old_values": (C.c_int, [_P, _P, C.c_long]),
     "ppo_value_clip_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, _P, C.POINTER(C.c_double)]),
+    "ppo_set_adv_norm": (C.c_int, [_P, C.c_int]),
+    "ppo_get_adv_norm": (C.c_int, [_P]),
+    "ppo_adv_normalize_device": (C.c_int, [_P, _P, C.c_long, C.c_int, _P]),
+    "ppo_adv_norm_history": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int]),
+    "ppo_adv_norm_read": (C.c_int, [_P, C.c_long, c_int_p, C.POINTER(C.c_float), C.c_int]),
     "ppo_set_obs_norm": (C.c_int, [_P, C.c_float]),
     "ppo_get_obs_norm": (C.c_float, [_P]),
     "ppo_obs_norm_freeze": (C.c_int, [_P, C.c_int]),
