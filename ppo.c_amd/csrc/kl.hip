@@ -56,7 +56,7 @@ __device__ __forceinline__ void decide(PhipKlRec* rec, float target_kl, double r
     const unsigned step = rec->step;
     /* the KL-adaptive learning rate (lr_kl = desired_kl; 0: the schedule is off and nothing here runs): rl_games' /
      * rsl_rl's rule on this step's kl, in fp32 with IEEE division and product, before the stop test; once the update
-     * has stopped the rate stays.  The step's Adam launches read rec->lr behind this launch (adam.hip, *_lrp). */
+     * has stopped the rate stays.  The step's Adam launches read rec->lr behind this launch (adam.hip, RateWord). */
     const float want = rec->lr_kl;
     if (want > 0.f) {
         float lr = rec->lr;

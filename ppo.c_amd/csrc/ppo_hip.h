@@ -361,10 +361,20 @@ void phip_gather(const int* perm, uint64_t key, int offset, int limit, int batch
                  float* states, float* actions, float* logprobs, float* advs, float* adv_targets);
 
 /* ---------------- Adam (adam.hip) ---------------- */
-void phip_adam_flat(float* p, const float* g, float* m, float* v, long n, float lr, float beta1,
-                    float beta2, float bias_correction1, float bias_correction2, float grad_scale);
-/* the same, also writing bf16(p) into w16[0, n16) (bf16 mode's parameter shadow); zero_g: g is
- * cleared once read (the next backward accumulates into it without a memset) */
+/* one flat span: p, g, m, v over n floats, the step's bias corrections 1 − β1^t and 1 − β2^t, the gradient
+ * scale; zero_g: g is cleared once read (the next backward accumulates into it without a memset) */
+typedef struct {
+    float *p, *g, *m, *v;
+    long n;
+    float bc1, bc2, grad_scale;
+    int zero_g;
+} PhipAdamSpan;
+/* the learning rate: by value, or — d_lr != NULL — read from that device word by the kernel (lr is then unused):
+ * step = *d_lr / bc1, the fp32 division the host does for a rate by value, so an equal rate gives equal bits */
+typedef struct {
+    float lr;
+    const float* d_lr;
+} PhipAdamRate;
 /* ---- launch-free minibatch steps (hipGraph replay with a device step table) ----
  * One minibatch step is captured once as a graph whose per-step arguments — the gather's
  * permutation offset / Feistel round keys and row offset, the Adam step sizes — live in a device
@@ -383,10 +393,10 @@ void phip_gather_rows_tab(const PhipStepArgs* tab, const int* ctr, const int* pe
                           const float* action, const float* logprob, const float* advantage,
                           const float* adv_target, float* actions, float* logprobs, float* advs, float* adv_targets,
                           int* rows);
-/* which = 0: the network's Adam (step / bc2; advances *ctr); 1: the entropy Adam (step_ls / bc2_ls) */
-void phip_adam_flat_tab(float* p, float* g, float* m, float* v, long n, const PhipStepArgs* tab, int* ctr,
-                        unsigned* ticket, int which, float beta1, float beta2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g);
+/* which = 0: the network's Adam (step / bc2; advances *ctr); 1: the entropy Adam (step_ls / bc2_ls);
+ * span->bc1 / bc2 are unused (the table holds the step's), the span is 16-B aligned */
+void phip_adam_flat_tab(const PhipAdamSpan* span, const PhipStepArgs* tab, int* ctr, unsigned* ticket, int which,
+                        float beta1, float beta2, unsigned short* w16, long n16);
 int  phip_graph_begin(void);                 /* capture the current stream's launches (returns 0 on success) */
 void* phip_graph_end(void);                  /* → instantiated executable graph (NULL on failure) */
 void phip_graph_launch(void* exec);          /* replay on the current stream */
@@ -394,38 +404,24 @@ void phip_graph_destroy(void* exec);
 const char* phip_graph_error(void);         /* why the last capture failed (warning text) */
 int  phip_capturing(void);                   /* 1 while a capture is open (profiling scopes stay out) */
 
-/* coef (both kernels below; NULL: off, the arithmetic is g · grad_scale as before): the device clip
- * coefficient of this step (clip.hip, PhipClipRec.coef) — the gradient is scaled by fl32(grad_scale · *coef).
- * skip (both kernels; NULL: off, arithmetic and launch shape as before): the device stop word of target-KL
- * early stopping (kl.hip, PhipKlRec.stopped) — while *skip != 0 the step is not taken: p, m, v and w16 stay
- * untouched (both spans of the pair kernel), the gradients are still cleared where zero_g / zero_g2 ask */
-void phip_adam_flat_w16(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                        float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                        long n16, int zero_g, const float* coef, const unsigned* skip);
-/* the same for a network span (16-B aligned) plus a small second span (≤ 256 floats, any alignment:
- * the policy step's entropy Adam) with its own step size, in one launch */
-void phip_adam_flat_pair(float* p, float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
-                         float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                         long n16, int zero_g, float* p2, float* g2, float* m2, float* v2, int n2, float lr2,
-                         float bias_correction1_2, float bias_correction2_2, float grad_scale2, int zero_g2,
+/* One launch over a span: float4 where p, g, m, v are 16-B aligned (and w16 8-B), else scalar (then without
+ * shadow or clear).  w16 != NULL: bf16(p) is also written into w16[0, n16) (bf16 mode's parameter shadow).
+ * coef (NULL: off, the arithmetic is g · grad_scale): the device clip coefficient of this step (clip.hip,
+ * PhipClipRec.coef) — the gradient is scaled by fl32(grad_scale · *coef).
+ * skip (NULL: off): the device stop word of target-KL early stopping (kl.hip, PhipKlRec.stopped) — while
+ * *skip != 0 the step is not taken: p, m, v and w16 stay untouched (both spans of the pair), the gradients are
+ * still cleared where zero_g asks */
+void phip_adam_flat(const PhipAdamSpan* span, PhipAdamRate rate, float beta1, float beta2, unsigned short* w16,
+                    long n16, const float* coef, const unsigned* skip);
+/* the same for a network span (16-B aligned) plus a small second span (≤ 256 floats, any alignment: the policy
+ * step's entropy Adam) with its own rate, in one launch; both rates by value or both through device words */
+void phip_adam_flat_pair(const PhipAdamSpan* span, PhipAdamRate rate, const PhipAdamSpan* side_span,
+                         PhipAdamRate side_rate, float beta1, float beta2, unsigned short* w16, long n16,
                          const float* coef, const unsigned* skip);
-/* the three launchers with the learning rate(s) read from device words: step = *lr / bias_correction1 computed by
- * the kernel (the *_lrp kernels; the same fp32 division, so an equal rate gives equal bits) */
-void phip_adam_flat_w16_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1, float beta2,
-                            float bias_correction1, float bias_correction2, float grad_scale, unsigned short* w16,
-                            long n16, int zero_g, const float* coef, const unsigned* skip);
-void phip_adam_flat_pair_lrp(float* p, float* g, float* m, float* v, long n, const float* lr, float beta1,
-                             float beta2, float bias_correction1, float bias_correction2, float grad_scale,
-                             unsigned short* w16, long n16, int zero_g, float* p2, float* g2, float* m2, float* v2,
-                             int n2, const float* lr2, float bias_correction1_2, float bias_correction2_2,
-                             float grad_scale2, int zero_g2, const float* coef, const unsigned* skip);
-void phip_adam_multi_lrp(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
-                         float* v, const float* lr, float beta1, float beta2, float bias_correction1,
-                         float bias_correction2, float grad_scale);
 /* multi-tensor: ptrs/lengths are HOST arrays describing device tensors; m/v are flat */
-void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors,
-                     float* m, float* v, float lr, float beta1, float beta2,
-                     float bias_correction1, float bias_correction2, float grad_scale);
+void phip_adam_multi(float* const* params, float* const* grads, const int* lengths, int num_tensors, float* m,
+                     float* v, PhipAdamRate rate, float beta1, float beta2, float bias_correction1,
+                     float bias_correction2, float grad_scale);
 
 /* ---------------- global gradient-norm clipping (clip.hip) ---------------- */
 #define PHIP_CLIP_PARTS 256

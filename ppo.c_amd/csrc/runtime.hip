@@ -341,7 +341,7 @@ void ppo_synchronize(void) { phip_sync(); }
 const char* ppo_build_info(void) {
     return "libppo: hand-written HIP for gfx950 (MI355X); fp32 MFMA v_mfma_f32_32x32x2_f32 GEMMs; "
            "kernels: gemm{NT,NN,TN}, relu, mse, policy_head, log_prob, gae_scan, welford, normalize, "
-           "gather, adam_flat/multi (+ _lrp), grad_norm, policy_kl, lr_couple, obs_stats, obs_fold, obs_affine, obs_norm, obs_norm_rows, "
+           "gather, adam_flat/multi (rate by value or device word),grad_norm, policy_kl, lr_couple, obs_stats, obs_fold, obs_affine, obs_norm, obs_norm_rows, "
            "ret_scan, ret_finish, ret_scale, sample, synthetic fill, cat_head_lane, cat_head_wave, disc_head, "
            "disc_sample, disc_argmax, cartpole_step, cartpole_eval; comm: RCCL";
 }

@@ -120,7 +120,8 @@ void adam_update(Adam* adam, float lr) {
         phip_h2d(dg + off, adam->grad_weights[i], sizeof(float) * (size_t)adam->lengths[i]);
         off += adam->lengths[i];
     }
-    phip_adam_flat(dp, dg, dm, dv, total, lr, adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale);
+    const PhipAdamSpan s = {dp, dg, dm, dv, total, bc1, bc2, adam->grad_scale, 0};
+    phip_adam_flat(&s, (PhipAdamRate){lr, NULL}, adam->beta1, adam->beta2, NULL, 0, NULL, NULL);
     off = 0;
     for (int i = 0; i < n; i++) {
         phip_d2h(adam->weights[i], dp + off, sizeof(float) * (size_t)adam->lengths[i]);
@@ -175,7 +176,12 @@ void free_adam_cuda(Adam* adam) {
     free(adam);
 }
 
-void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NULL, 0, 0, NULL, NULL); }
+void adam_update_cuda(Adam* adam, float lr) { adam_update_dev(adam, (PhipAdamRate){lr, NULL}, NULL, 0, 0, NULL, NULL); }
+
+/* the Adam's flat span with this step's bias corrections, as the launchers take it */
+static PhipAdamSpan flat_span_of(const Adam* a, float bc1, float bc2, int zero_g) {
+    return (PhipAdamSpan){a->weights[0], a->grad_weights[0], a->m, a->v, a->span, bc1, bc2, a->grad_scale, zero_g};
+}
 
 /* w16 != NULL: also refresh the bf16 shadow of the first n16 parameters (flat spans only).
  * zero_g: clear the gradient span once read (flat spans only).  Returns bit 0: shadow refreshed,
@@ -183,99 +189,55 @@ void adam_update_cuda(Adam* adam, float lr) { adam_update_cuda_w16(adam, lr, NUL
  * (PhipClipRec.coef), multiplied into the gradient scale by the kernel.  skip != NULL (flat spans only): the
  * device stop word of target-KL early stopping (PhipKlRec.stopped): while it is set the kernel takes no step
  * and only clears the gradient where zero_g asks.  The host step counter advances either way; ppo_update
- * sets it back by the steps the device skipped. */
-/* d_lr != NULL: the rate comes from that device word, read by the kernels' pointer variants (lr is unused) */
-static int adam_update_dev(Adam* adam, float lr, const float* d_lr, unsigned short* w16, long n16, int zero_g,
-                           const float* coef, const unsigned* skip) {
-    if (coef && !adam->flat) die("adam_update_cuda_w16: gradient clipping needs a flat Adam span");
-    if (skip && !adam->flat) die("adam_update_cuda_w16: target-KL early stopping needs a flat Adam span");
+ * sets it back by the steps the device skipped.  rate.d_lr != NULL: the rate comes from that device word (the
+ * KL-adaptive schedule's, or a coupled value rate), read by the kernels' device-word instantiations. */
+int adam_update_dev(Adam* adam, PhipAdamRate rate, unsigned short* w16, long n16, int zero_g, const float* coef,
+                    const unsigned* skip) {
+    if (coef && !adam->flat) die("adam_update_dev: gradient clipping needs a flat Adam span");
+    if (skip && !adam->flat) die("adam_update_dev: target-KL early stopping needs a flat Adam span");
     float bc1, bc2;
     bias_corrections(adam, &bc1, &bc2);
     nn_note_device_update(adam->weights[0]);          /* the network's host mirrors are now stale */
-    if (adam->flat) {
-        /* the clearing pass is the vectorised kernel's: 16-B aligned spans only */
-        const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
-                             (uintptr_t)adam->v;
-        if (al & 15u) zero_g = 0;
-        if (d_lr)
-            phip_adam_flat_w16_lrp(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, d_lr,
-                                   adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g,
-                                   coef, skip);
-        else
-            phip_adam_flat_w16(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                               adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, coef, skip);
-        return (w16 != NULL) | (zero_g ? 2 : 0);
-    } else if (d_lr) {
-        phip_adam_multi_lrp(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v,
-                            d_lr, adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale);
-    } else {
-        phip_adam_multi(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v, lr,
+    if (!adam->flat) {
+        phip_adam_multi(adam->weights, adam->grad_weights, adam->lengths, adam->num_layers, adam->m, adam->v, rate,
                         adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale);
+        return 0;
     }
-    return 0;
+    /* the clearing pass is the vectorised kernel's: 16-B aligned spans only */
+    if (!adam_span_aligned(adam)) zero_g = 0;
+    const PhipAdamSpan s = flat_span_of(adam, bc1, bc2, zero_g);
+    phip_adam_flat(&s, rate, adam->beta1, adam->beta2, w16, w16 ? n16 : 0, coef, skip);
+    return (w16 != NULL) | (zero_g ? 2 : 0);
 }
 
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
-                         const unsigned* skip) {
-    return adam_update_dev(adam, lr, NULL, w16, n16, zero_g, coef, skip);
-}
-
-/* the same step with the learning rate in a device word (the KL-adaptive schedule's, or a coupled value rate) */
-int adam_update_cuda_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, const float* coef,
-                         const unsigned* skip) {
-    if (!d_lr) die("adam_update_cuda_lrp: NULL rate");
-    return adam_update_dev(adam, 0.f, d_lr, w16, n16, zero_g, coef, skip);
-}
-
-/* ppo_ext.h (a test entry): one adam_update_cuda step through the pointer variants */
+/* ppo_ext.h (a test entry): one adam_update_cuda step with the rate through a device word */
 int ppo_adam_update_lr_device(void* vadam, const float* d_lr) {
     Adam* adam = (Adam*)vadam;
     if (!adam || !adam->on_device || !d_lr) return -1;
-    adam_update_cuda_lrp(adam, d_lr, NULL, 0, 0, NULL, NULL);
+    adam_update_dev(adam, (PhipAdamRate){0.f, d_lr}, NULL, 0, 0, NULL, NULL);
     return 0;
 }
 
 /* a network's flat Adam (16-B aligned span) and a small flat side Adam (the entropy Adam's log σ) in
  * one launch; the side's step runs first in the step counters (ppo.cu:440-442 order; the spans are
  * independent).  Returns bit 0: shadow refreshed, bit 1: network gradients cleared, bit 2: side
- * gradients cleared; −1 (nothing done) when the pair does not qualify.  coef as in adam_update_cuda_w16:
- * one coefficient for both spans; skip likewise: one stop word for both.  d_lr / d_lr_side != NULL (both or
- * neither): the two rates from device words (the pair kernel's pointer variant; lr and lr_side are unused). */
-static int adam_update_pair_dev(Adam* adam, float lr, const float* d_lr, unsigned short* w16, long n16, int zero_g,
-                                Adam* side, float lr_side, const float* d_lr_side, int zero_side, const float* coef,
-                                const unsigned* skip) {
-    const uintptr_t al = (uintptr_t)adam->weights[0] | (uintptr_t)adam->grad_weights[0] | (uintptr_t)adam->m |
-                         (uintptr_t)adam->v;
-    if (!adam->flat || !side->flat || (al & 15u) || side->span > 256 || side->span < 1 || adam->span < 1 ||
-        adam->beta1 != side->beta1 || adam->beta2 != side->beta2 || ((uintptr_t)w16 & 7u))
+ * gradients cleared; −1 (nothing done) when the pair does not qualify.  coef as in adam_update_dev: one
+ * coefficient for both spans; skip likewise: one stop word for both.  The two rates come both by value or both
+ * from device words. */
+int adam_update_pair_dev(Adam* adam, PhipAdamRate rate, unsigned short* w16, long n16, int zero_g, Adam* side,
+                         PhipAdamRate side_rate, int zero_side, const float* coef, const unsigned* skip) {
+    if (!rate.d_lr != !side_rate.d_lr) die("adam_update_pair_dev: one rate by value, the other in a device word");
+    if (!adam->flat || !side->flat || !adam_span_aligned(adam) || side->span > 256 || side->span < 1 ||
+        adam->span < 1 || adam->beta1 != side->beta1 || adam->beta2 != side->beta2 || ((uintptr_t)w16 & 7u))
         return -1;
     float bc1s, bc2s, bc1, bc2;
     bias_corrections(side, &bc1s, &bc2s);
     bias_corrections(adam, &bc1, &bc2);
     nn_note_device_update(adam->weights[0]);
     nn_note_device_update(side->weights[0]);
-    if (d_lr)
-        phip_adam_flat_pair_lrp(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, d_lr,
-                                adam->beta1, adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g,
-                                side->weights[0], side->grad_weights[0], side->m, side->v, (int)side->span, d_lr_side,
-                                bc1s, bc2s, side->grad_scale, zero_side, coef, skip);
-    else
-        phip_adam_flat_pair(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, lr, adam->beta1,
-                            adam->beta2, bc1, bc2, adam->grad_scale, w16, w16 ? n16 : 0, zero_g, side->weights[0],
-                            side->grad_weights[0], side->m, side->v, (int)side->span, lr_side, bc1s, bc2s,
-                            side->grad_scale, zero_side, coef, skip);
+    const PhipAdamSpan s = flat_span_of(adam, bc1, bc2, zero_g), s2 = flat_span_of(side, bc1s, bc2s, zero_side);
+    phip_adam_flat_pair(&s, rate, &s2, side_rate, adam->beta1, adam->beta2, w16, w16 ? n16 : 0, coef, skip);
     return (w16 != NULL) | (zero_g ? 2 : 0) | (zero_side ? 4 : 0);
-}
-
-int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side, const float* coef, const unsigned* skip) {
-    return adam_update_pair_dev(adam, lr, NULL, w16, n16, zero_g, side, lr_side, NULL, zero_side, coef, skip);
-}
-
-int adam_update_pair_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, Adam* side,
-                         const float* d_lr_side, int zero_side, const float* coef, const unsigned* skip) {
-    if (!d_lr || !d_lr_side) die("adam_update_pair_lrp: NULL rate");
-    return adam_update_pair_dev(adam, 0.f, d_lr, w16, n16, zero_g, side, 0.f, d_lr_side, zero_side, coef, skip);
 }
 
 /* ---------------- checkpoint (adam.cu:172-264 byte layout) ---------------- */

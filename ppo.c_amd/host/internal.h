@@ -83,19 +83,23 @@ void nn_sync_w16(NeuralNetwork* nn);       /* bf16 mode: refresh the bf16 weight
 
 /* adam.c */
 void adam_next_step(Adam* a, float lr, float* step, float* bc2);
-/* device Adam that also writes the bf16 shadow w16[0, n16) in the same pass; returns 1 when it did;
+/* device Adam step, and a network's Adam with a small side Adam in one launch (adam.c has the return bits);
+ * rate: by value, or through a device word (the KL-adaptive schedule's policy rate, a coupled value rate:
+ * csrc/kl.hip PhipKlRec.lr / lr_v); w16: NULL, or the bf16 shadow w16[0, n16) written in the same pass;
  * coef: NULL, or the step's device clip coefficient (gradient clipping, csrc/clip.hip);
  * skip: NULL, or the device stop word of target-KL early stopping (csrc/kl.hip) */
-int adam_update_cuda_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, const float* coef,
-                         const unsigned* skip);
-int adam_update_pair_w16(Adam* adam, float lr, unsigned short* w16, long n16, int zero_g, Adam* side, float lr_side,
-                         int zero_side, const float* coef, const unsigned* skip);
-/* the same two steps with the learning rate(s) read from device words by the kernels' pointer variants (the
- * KL-adaptive schedule's policy rate, a coupled value rate: csrc/kl.hip PhipKlRec.lr / lr_v) */
-int adam_update_cuda_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, const float* coef,
-                         const unsigned* skip);
-int adam_update_pair_lrp(Adam* adam, const float* d_lr, unsigned short* w16, long n16, int zero_g, Adam* side,
-                         const float* d_lr_side, int zero_side, const float* coef, const unsigned* skip);
+int adam_update_dev(Adam* adam, PhipAdamRate rate, unsigned short* w16, long n16, int zero_g, const float* coef,
+                    const unsigned* skip);
+int adam_update_pair_dev(Adam* adam, PhipAdamRate rate, unsigned short* w16, long n16, int zero_g, Adam* side,
+                         PhipAdamRate side_rate, int zero_side, const float* coef, const unsigned* skip);
+/* the Adam's span is flat, updates these gradients and — params != NULL — starts at these parameters */
+static inline int adam_owns(const Adam* a, const float* params, const float* grads) {
+    return a->flat && (!params || a->weights[0] == params) && a->grad_weights[0] == grads;
+}
+/* p, g, m and v of the span start on 16-B boundaries (the float4 kernels' condition) */
+static inline int adam_span_aligned(const Adam* a) {
+    return (((uintptr_t)a->weights[0] | (uintptr_t)a->grad_weights[0] | (uintptr_t)a->m | (uintptr_t)a->v) & 15u) == 0;
+}
 
 /* checkpoint Adam with a known tensor count (n_expected < 0: unknown); rejects mismatches */
 Adam* load_adam_ex(FILE* file, float** weights, float** grad_weights, int* length, int n_expected, bool cuda);

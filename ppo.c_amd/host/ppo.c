@@ -478,9 +478,7 @@ static const int* next_perm(PPO* ppo, PPODev* d, int shuffle_mode, uint64_t* key
  * cluster kernel checks its own shapes) */
 static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
     const int L = nn->num_layers - 1;
-    if (nn->dtype != 0 || L < 1 || L > 8 || !adam->flat || adam->weights[0] != nn->d_params ||
-        adam->grad_weights[0] != nn->d_grads)
-        return -1;
+    if (nn->dtype != 0 || L < 1 || L > 8 || !adam_owns(adam, nn->d_params, nn->d_grads)) return -1;
     if (nn_has_tanh(nn)) return -1;      /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
     for (int i = 0; i < L; i++)
         if (nn->layers[i].input_size > max_w || nn->layers[i].output_size > max_w) return -1;
@@ -513,17 +511,13 @@ static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
 /* Adam step of a network's flat span; in bf16 mode the same pass refreshes the bf16 parameter
  * shadow when the span starts at the network's parameters, else a separate conversion does.
  * zero_grads: the same pass clears the gradients it read (the next backward skips its memset);
- * coef: NULL, or the step's device clip coefficient; skip: NULL, or the device stop word of target-KL
- * early stopping */
-static int adam_update_net(Adam* adam, float lr, const float* d_lr, NeuralNetwork* nn, int zero_grads,
-                           const float* coef, const unsigned* skip) {
-    const int own = adam->flat && adam->weights[0] == nn->d_params && adam->grad_weights[0] == nn->d_grads;
+ * rate: by value, or in a device word (the adaptive schedule); coef: NULL, or the step's device clip
+ * coefficient; skip: NULL, or the device stop word of target-KL early stopping */
+static int adam_update_net(Adam* adam, PhipAdamRate rate, NeuralNetwork* nn, int zero_grads, const float* coef,
+                           const unsigned* skip) {
+    const int own = adam_owns(adam, nn->d_params, nn->d_grads);
     const int fused = nn->dtype == 1 && own;
-    /* d_lr (NULL: lr by value, the kernels and bits as ever): the rate in a device word (the adaptive schedule) */
-    const int r = d_lr ? adam_update_cuda_lrp(adam, d_lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own,
-                                              coef, skip)
-                       : adam_update_cuda_w16(adam, lr, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own,
-                                              coef, skip);
+    const int r = adam_update_dev(adam, rate, fused ? nn->d_w16 : NULL, nn->num_params, zero_grads && own, coef, skip);
     /* a skipped step left the parameters, hence their shadow, as they were: the refresh rewrites the same bits */
     if (!(r & 1) && nn->dtype == 1) nn_sync_w16(nn);
     return (r & 2) != 0;                 /* the network's gradients are zero again */
@@ -534,9 +528,10 @@ static int adam_update_net(Adam* adam, float lr, const float* d_lr, NeuralNetwor
  * the step's last kernel), 1 reads the entropy entry */
 static void adam_net_tab(Adam* adam, NeuralNetwork* nn, PPODev* d, int ph, int which) {
     const int fused = nn && nn->dtype == 1;
-    phip_adam_flat_tab(adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, d->tab[ph], d->ctr + ph,
-                       (unsigned*)(d->ctr + 2 + ph), which, adam->beta1, adam->beta2,
-                       adam->grad_scale, fused ? nn->d_w16 : NULL, fused ? nn->num_params : 0, 1);
+    const PhipAdamSpan s = {adam->weights[0], adam->grad_weights[0], adam->m, adam->v, adam->span, 0.f, 0.f,
+                            adam->grad_scale, 1};
+    phip_adam_flat_tab(&s, d->tab[ph], d->ctr + ph, (unsigned*)(d->ctr + 2 + ph), which, adam->beta1, adam->beta2,
+                       fused ? nn->d_w16 : NULL, fused ? nn->num_params : 0);
     nn_note_device_update(adam->weights[0]);
 }
 
@@ -613,7 +608,7 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
         cluster = 1;
     }
     int (*phase_fn)(const PhipTinyNet*, const PhipTinyPhase*) = cluster ? phip_cluster_update : phip_tiny_update;
-    if (!ppo->adam_entropy->flat || ppo->adam_entropy->grad_weights[0] != ppo->policy->d_log_std_grad) return -1;
+    if (!adam_owns(ppo->adam_entropy, NULL, ppo->policy->d_log_std_grad)) return -1;
     GaussianPolicy* pol = ppo->policy;
     np.log_std = pol->d_log_std;
     np.log_std_grad = pol->d_log_std_grad;
@@ -777,8 +772,8 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
     }
     /* the value rate: by value (the schedule's, d->lr_use), or — the adaptive schedule with coupling — the word the
      * coupling launch wrote ahead of the loops */
-    return adam_update_net(ppo->adam_V, d->lr_use[1], lr_adaptive(d) && d->lr_couple ? &d->kl->lr_v : NULL, V,
-                           iv + 1 < c->nv, clip_coef(d, 0, ppo->adam_V, NULL, 0), NULL);
+    const PhipAdamRate rate = {d->lr_use[1], lr_adaptive(d) && d->lr_couple ? &d->kl->lr_v : NULL};
+    return adam_update_net(ppo->adam_V, rate, V, iv + 1 < c->nv, clip_coef(d, 0, ppo->adam_V, NULL, 0), NULL);
 }
 
 static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab) {
@@ -894,26 +889,22 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
      * record behind it and may end the loop there, and a caller may read the last issued step's gradients
      * (the next step, if one follows, clears them itself) */
     const int clear = ip + 1 < c->np && !(kl_on && (ip + 1) % c->num_batches == 0);
-    const int own = ap->flat && ap->weights[0] == mu->d_params && ap->grad_weights[0] == mu->d_grads;
+    const int own = adam_owns(ap, mu->d_params, mu->d_grads);
     const int fused = mu->dtype == 1 && own;
-    const int ls_own = ppo->adam_entropy->flat && ppo->adam_entropy->grad_weights[0] == pol->d_log_std_grad;
+    const int ls_own = adam_owns(ppo->adam_entropy, NULL, pol->d_log_std_grad);
     /* the policy rate, shared by both Adams as ever: by value, or — the adaptive schedule — the record's word, which
      * this step's decision has just written */
-    const float lr = d->lr_use[0];
-    const float* d_lr = lr_adaptive(d) ? &d->kl->lr : NULL;
-    const int r = d_lr ? adam_update_pair_lrp(ap, d_lr, fused ? mu->d_w16 : NULL, mu->num_params, clear && own,
-                                              ppo->adam_entropy, d_lr, clear && ls_own, coef, skip)
-                       : adam_update_pair_w16(ap, lr, fused ? mu->d_w16 : NULL, mu->num_params, clear && own,
-                                              ppo->adam_entropy, lr, clear && ls_own, coef, skip);
+    const PhipAdamRate rate = {d->lr_use[0], lr_adaptive(d) ? &d->kl->lr : NULL};
+    const int r = adam_update_pair_dev(ap, rate, fused ? mu->d_w16 : NULL, mu->num_params, clear && own,
+                                       ppo->adam_entropy, rate, clear && ls_own, coef, skip);
     if (r >= 0) {
         if (!(r & 1) && mu->dtype == 1) nn_sync_w16(mu);
         *ls_zero = ls_own && (r & 4);
         *p_zero = (r & 2) != 0;
         return;
     }
-    *ls_zero = ls_own && ((d_lr ? adam_update_cuda_lrp(ppo->adam_entropy, d_lr, NULL, 0, clear, coef, skip)
-                                : adam_update_cuda_w16(ppo->adam_entropy, lr, NULL, 0, clear, coef, skip)) & 2);
-    *p_zero = adam_update_net(ppo->adam_policy, lr, d_lr, mu, clear, coef, skip);
+    *ls_zero = ls_own && (adam_update_dev(ppo->adam_entropy, rate, NULL, 0, clear, coef, skip) & 2);
+    *p_zero = adam_update_net(ppo->adam_policy, rate, mu, clear, coef, skip);
 }
 
 /* target-KL early stopping, at a policy-epoch boundary: the host waits for the policy loop's stream only
@@ -941,19 +932,14 @@ static int step_graphs_ok(const StepCtx* c) {
     if (c->d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return 0;   /* … and a captured policy step gathers for itself */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
-    for (int i = 0; i < 3; i++) {
-        Adam* a = ads[i];
-        const uintptr_t al = (uintptr_t)a->weights[0] | (uintptr_t)a->grad_weights[0] | (uintptr_t)a->m |
-                             (uintptr_t)a->v;
-        if (!a->flat || (al & 15u)) return 0;
-    }
+    for (int i = 0; i < 3; i++)
+        if (!ads[i]->flat || !adam_span_aligned(ads[i])) return 0;
     /* the table Adam always clears the gradient it read (the captured steps run their backward with
      * the gradients already zero), so every Adam must own its network's gradient span, as `own` in
      * adam_update_net requires on the eager path */
-    if (ppo->adam_V->weights[0] != ppo->V->d_params || ppo->adam_V->grad_weights[0] != ppo->V->d_grads ||
-        ppo->adam_policy->weights[0] != ppo->policy->mu->d_params ||
-        ppo->adam_policy->grad_weights[0] != ppo->policy->mu->d_grads ||
-        ppo->adam_entropy->grad_weights[0] != ppo->policy->d_log_std_grad)
+    if (!adam_owns(ppo->adam_V, ppo->V->d_params, ppo->V->d_grads) ||
+        !adam_owns(ppo->adam_policy, ppo->policy->mu->d_params, ppo->policy->mu->d_grads) ||
+        !adam_owns(ppo->adam_entropy, NULL, ppo->policy->d_log_std_grad))
         return 0;
     /* only the combination tests/test_gpu_update.py replays against eager launches: fp32 networks with
      * the fused output heads (value A = 1, policy A <= 6) */

@@ -1,4 +1,4 @@
-"""Learning-rate schedules on the GPU (ppo_set_lr_schedule, csrc/kl.hip decide(), the *_lrp kernels of csrc/adam.hip;
+"""Learning-rate schedules on the GPU (ppo_set_lr_schedule, csrc/kl.hip decide(), csrc/adam.hip's kernels over RateWord;
 DESIGN.md §4 "Learning-rate schedules").
 
 Everything here is bit for bit.  The adaptive rule is replayed from the update's own ppo_kl_history through the fp32
@@ -338,6 +338,55 @@ def test_with_target_kl_stop(lib, oracle):
     ap = b.contents.adam_policy.contents
     assert ap.time_step == s == b.contents.adam_entropy.contents.time_step
     lib.free_ppo(b)
+
+
+def test_pointer_pair_with_clip_and_stop(lib, oracle):
+    """The pair kernel with both rates through device words, a clip coefficient and the stop word together, against the
+    by-value pair kernel byte for byte over a whole update that stops part-way.  The adaptive range is the single rate
+    R (lr_min == lr_max), so decide() writes R at every step and a PPO on the constant schedule with lr_policy = R set
+    by hand takes the same steps: the steps before the stop scale their gradients by the step's coefficient, the stop
+    step and those behind it only clear them.  The value rate is coupled, so the value Adam (the vector kernel, with
+    its own coefficient) reads lr_V · (R / R) from its word.  Parameters, log σ, and m, v and the step count of all
+    three Adams."""
+    R, NORM = F32(5e-3), 1e-2
+
+    def run(adaptive, target):
+        ppo = fresh(lib, oracle)
+        if adaptive:
+            assert set_schedule(lib, ppo, lr.ADAPTIVE, 0.01, R, R) == 0 and get_lr(lib, ppo)[0] == R
+            assert lib.ppo_lr_couple_value(ppo, 1) == 0              # lr_v = lr_V · (R / R): the value Adam's word
+        else:
+            ppo.contents.lr_policy = float(R)
+        assert lib.ppo_set_max_grad_norm(ppo, NORM) == 0 and lib.ppo_set_target_kl(ppo, target) == 0
+        lib.ppo_reset_stats(ppo)
+        update(lib, ppo)
+        c = ppo.contents
+        out = dict(nets=nets(lib, ppo), kl=kl_hist(lib, ppo), lr=lr_hist(lib, ppo), st=stats(lib, ppo))
+        for k, ad in (("V", c.adam_V), ("mu", c.adam_policy), ("ls", c.adam_entropy)):
+            a = ad.contents
+            out[k] = (a.time_step, ppo_ffi.d2h(lib, a.m, F32, a.span).tobytes(),
+                      ppo_ffi.d2h(lib, a.v, F32, a.span).tobytes())
+        lib.free_ppo(ppo)
+        return out
+
+    kls = run(False, INF)["kl"]
+    assert len(kls) == STEPS
+    # a step that stops the update with at least one issued step behind it: its KL stands clear of all before it
+    cand = [s for s in range(1, STEPS) if s % NB != NB - 1 and kls[s] > 1.2 * max(float(kls[:s].max()), 1e-12)]
+    assert cand, f"no step rises 20 % above its predecessors: {kls}"
+    s = cand[-1]
+    target = float(np.sqrt(max(float(kls[:s].max()), 1e-12) * float(kls[s]))) / 1.5
+    a, b = run(True, target), run(False, target)
+    print(f"stop at {s} of {STEPS}, target {target:.3e}; clipped value / policy steps {b['st'][11]:.0f} / "
+          f"{b['st'][12]:.0f}, last norms {b['st'][9]:.3e} / {b['st'][10]:.3e}; kl {kls}")
+    for r in (a, b):
+        assert r["st"][16] == s and r["st"][15] == s and r["st"][3] == (s // NB + 1) * NB > s + 1
+        assert r["st"][12] >= s and r["st"][11] >= 1           # every policy step that ran was clipped (coef < 1)
+        assert r["st"][26] == float(LR_V) and r["V"][0] == NVE * NB
+        assert r["mu"][0] == s == r["ls"][0] and (r["kl"][:s + 1] == kls[:s + 1]).all()
+    assert len(a["lr"]) == a["st"][3] and (a["lr"] == R).all() and len(b["lr"]) == 0
+    for k in ("nets", "V", "mu", "ls"):
+        assert a[k] == b[k], f"{k} differs between the device-word and the by-value update"
 
 
 # ----------------------------------------------------------------------------- 6. linear

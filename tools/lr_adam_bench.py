@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """The flat Adam launch with the learning rate by value against the pointer variant (the adaptive schedule's),
-at the size of bench.py's C4 value network (376 -> 3x512 -> 1: one 16-B aligned span, adam_flat_vec_kernel against
-adam_flat_vec_lrp_kernel).
+at the size of bench.py's C4 value network (376 -> 3x512 -> 1: one 16-B aligned span, adam_flat_vec_kernel<RateValue>
+against adam_flat_vec_kernel<RateWord>).
 
 Two Adams over two networks of that shape, gradients of a fixed seed; per round 100 launches of each through
 ppo_prof_* (events around every launch, PPO_K_ADAM), alternating by value / pointer; six rounds, the first
