@@ -17,6 +17,7 @@
 // and the Makefile's -ffp-contract=off both forbid a fused multiply-add.
 #include "dev.h"
 #include "advnorm.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -25,16 +26,11 @@ namespace {
 constexpr int TPB = ADVNORM_LANES;
 constexpr int REG = ADVNORM_REG;
 
-// the tree of advnorm.h over s[0 … 255]; every thread gets s[0].  Ends with a barrier, so s may be rewritten
+// the tree of advnorm.h over s[0 … 255] (reduce.h's tree_fold under __dadd_rn); every thread gets s[0].  Ends with
+// a barrier, so s may be rewritten
 __device__ __forceinline__ double tree_sum(double* s, int t, double lane) {
     s[t] = lane;
-    __syncthreads();
-#pragma unroll
-    for (int stride = 1; stride < TPB; stride *= 2) {
-        if ((t & (2 * stride - 1)) == 0) s[t] = __dadd_rn(s[t], s[t + stride]);
-        __syncthreads();
-    }
-    const double total = s[0];
+    const double total = ppo::tree_fold<TPB>(s, t, ppo::DaddRn{});
     __syncthreads();
     return total;
 }

@@ -9,28 +9,18 @@
 // thread sums its grid-stride elements in double in index order, a workgroup folds its 256 sums by a
 // fixed LDS tree, and the last workgroup to arrive folds the ≤ 256 workgroup partials by the same fixed
 // tree — no floating-point atomic anywhere, so the same gradient bits give the same coef bits whatever
-// order the workgroups ran in.  No grid barrier: the hand-off is the ticket form — each workgroup's one
-// 8-byte partial is stored write-through at agent scope and drained before its ticket add (so it needs
-// no release fence, which would write back the whole L2 slice), and the last arriver acquires once and
-// reads the partials with agent-scope loads.
+// order the workgroups ran in.  No grid barrier: the tree (block_sum_halving) and the hand-off (ticket_publish /
+// ticket_load, one 8-byte partial per workgroup) are reduce.h's, which holds the ordering argument.
 #include "dev.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
 constexpr int UNROLL = 4;
 
-__device__ __forceinline__ double block_sum(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = TPB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
-}
+// reduce.h's halving tree over the workgroup's 256 doubles
+__device__ __forceinline__ double block_sum(double v, double* s) { return ppo::block_sum_halving<TPB>(v, s); }
 
 // vec: a is 16-B aligned (float4 body, scalar tail for n % 4); else every element takes the scalar loop
 __global__ void __launch_bounds__(TPB) grad_norm_kernel(const float* __restrict__ a, long n,
@@ -64,28 +54,11 @@ __global__ void __launch_bounds__(TPB) grad_norm_kernel(const float* __restrict_
         for (long j = threadIdx.x; j < nb; j += TPB) acc += (double)b[j] * (double)b[j];
     const double part = block_sum(acc, s);
 
-    if (threadIdx.x == 0) {
-        unsigned long long* slot = reinterpret_cast<unsigned long long*>(&rec->partial[blockIdx.x]);
-        __hip_atomic_store(slot, (unsigned long long)__double_as_longlong(part), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the write-through store has left this CU
-        const unsigned t = __hip_atomic_fetch_add(&rec->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = t == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        s[TPB] = last ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (s[TPB] == 0.0) return;                // uniform over the workgroup
+    const double part1[1] = {part};
+    if (!ppo::ticket_publish(&rec->partial[blockIdx.x], part1, &rec->ticket, &s[TPB])) return;
 
     // the last workgroup: every partial of this launch is visible; fold them in index order
-    double p = 0.0;
-    if (threadIdx.x < gridDim.x) {
-        const unsigned long long* slot = reinterpret_cast<const unsigned long long*>(&rec->partial[threadIdx.x]);
-        p = __longlong_as_double((long long)__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
+    const double p = threadIdx.x < gridDim.x ? ppo::ticket_load(&rec->partial[threadIdx.x]) : 0.0;
     const double total = block_sum(p, s);
     if (threadIdx.x == 0) {
         const double norm = (double)grad_scale * sqrt(total);

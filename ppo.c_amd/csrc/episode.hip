@@ -19,16 +19,16 @@
 //      reads at a time: bank (e + row) mod 64, no conflict either way.  2 × 64 × 65 × 4 B = 33 280 B of LDS per
 //      workgroup.  Emitted episodes are merged, in the order they end, into the environment's own aggregate
 //      (⊕ below with a one-episode right-hand side).
-//   2. episode_fold_kernel   one workgroup of 256 threads: thread i merges environments [i·per, (i+1)·per), per =
-//      ⌈E/256⌉, in index order; then a pairwise tree over the threads (stride 1, 2, 4, …: thread i takes thread
-//      i + stride, for i a multiple of 2·stride).  The batch aggregate goes to `out`; the running window (may be
-//      null) becomes window ⊕ batch.
-// ⊕ on aggregates {n, mean, M2, min, max, Σlen, mean disc} is Chan et al.'s combine:
+//   2. episode_fold_kernel   one workgroup of 256 threads folds the environments' aggregates in reduce.h's
+//      fold_runs_tree order (contiguous runs of ⌈E/256⌉ in index order, then the pairwise tree over the threads).
+//      The batch aggregate goes to `out`; the running window (may be null) becomes window ⊕ batch.
+// ⊕ on aggregates {n, mean, M2, min, max, Σlen, mean disc} is Chan et al.'s combine ((n, mean, M2): reduce.h's chan):
 //     n = na + nb;  f = nb / n;  δ = mean_b − mean_a;  mean = mean_a + δ·f;  M2 = (M2a + M2b) + δ·δ·(na·f);
 //     mdisc = mdisc_a + (mdisc_b − mdisc_a)·f;  min, max;  Σlen = Σlen_a + Σlen_b
 // an empty side leaves the other as it is, so a scan that emits nothing yields the zero aggregate.  No atomics;
 // the order is a function of E alone.
 #include "dev.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
@@ -47,14 +47,12 @@ struct Agg { double n, mean, m2, mn, mx, len, mdisc; };
 __device__ __forceinline__ void merge(Agg& a, const Agg& b) {
     if (!(b.n > 0.0)) return;
     if (!(a.n > 0.0)) { a = b; return; }
-    const double n = a.n + b.n, f = b.n / n, delta = b.mean - a.mean;
-    a.mean = a.mean + delta * f;
-    a.m2 = (a.m2 + b.m2) + delta * delta * (a.n * f);
+    const double f = b.n / (a.n + b.n);               // the nb / n of ppo::chan: the same operands, the same bits
     a.mdisc = a.mdisc + (b.mdisc - a.mdisc) * f;
     a.mn = b.mn < a.mn ? b.mn : a.mn;
     a.mx = b.mx > a.mx ? b.mx : a.mx;
     a.len = a.len + b.len;
-    a.n = n;
+    ppo::chan(a.n, a.mean, a.m2, b.n, b.mean, b.m2);
 }
 
 __device__ __forceinline__ Agg load_agg(const double* p) { return Agg{p[0], p[1], p[2], p[3], p[4], p[5], p[6]}; }
@@ -132,38 +130,27 @@ __global__ void __launch_bounds__(SCAN_TPB) episode_scan_kernel(
     part[(long)NPART * e + 7] = len > 0.0 ? 1.0 : 0.0;
 }
 
+// an aggregate and, in slot 7, the count of environments left mid-episode (an exact integer, a plain add)
+struct Slot { Agg a; double open; };
+static_assert(sizeof(Slot) == NPART * sizeof(double), "a slot of `part` and of the fold's LDS");
+struct SlotMerge {
+    __device__ Slot operator()(Slot x, const Slot& y) const { merge(x.a, y.a); x.open += y.open; return x; }
+};
+
 __global__ void __launch_bounds__(FOLD_TPB) episode_fold_kernel(const double* __restrict__ part, int E,
                                                                 double* __restrict__ out, double* __restrict__ window) {
-    __shared__ double s[FOLD_TPB * NPART];
-    const int t = threadIdx.x;
-    const int per = (E + FOLD_TPB - 1) / FOLD_TPB;
-    Agg a{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    double open = 0.0;                                                // an exact integer
-    for (int i = t * per; i < min(E, (t + 1) * per); ++i) {
-        merge(a, load_agg(part + (long)NPART * i));
-        open += part[(long)NPART * i + 7];
-    }
-    store_agg(s + NPART * t, a);
-    s[NPART * t + 7] = open;
-    __syncthreads();
-    for (int off = 1; off < FOLD_TPB; off <<= 1) {
-        if ((t & (2 * off - 1)) == 0) {
-            Agg x = load_agg(s + NPART * t);
-            merge(x, load_agg(s + NPART * (t + off)));
-            store_agg(s + NPART * t, x);
-            s[NPART * t + 7] += s[NPART * (t + off) + 7];
-        }
-        __syncthreads();
-    }
-    if (t != 0) return;
-    const Agg batch = load_agg(s);
-    store_agg(out, batch);
-    out[7] = s[7];
+    __shared__ Slot s[FOLD_TPB];
+    const Slot r = ppo::fold_runs_tree<FOLD_TPB>(
+        s, E, Slot{Agg{0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, 0.0},
+        [&](int i) { return Slot{load_agg(part + (long)NPART * i), part[(long)NPART * i + 7]}; }, SlotMerge{});
+    if (threadIdx.x != 0) return;
+    store_agg(out, r.a);
+    out[7] = r.open;
     if (window) {
         Agg wnd = load_agg(window);
-        merge(wnd, batch);
+        merge(wnd, r.a);
         store_agg(window, wnd);
-        window[7] = s[7];
+        window[7] = r.open;
     }
 }
 

@@ -16,7 +16,11 @@
 //                         per-workgroup Welford triple (n, mean, M2) in double
 // then welford_combine (Chan et al. parallel combine, double) and normalise:
 //   A ← (A − μ) / (σ_pop + 1e-8)                                        (ppo.cu:355-368)
+// The machinery is reduce.h's: the affine map and its block scan (here fp32, right to left), the per-workgroup
+// two-pass triple, and the combine — chan_ref_order, the reference's operation order, which is NOT the chan of
+// the other statistics kernels — folded by fold_runs_tree.
 #include "dev.h"
+#include "reduce.h"
 
 namespace {
 
@@ -24,11 +28,8 @@ constexpr int TPB = 256;
 constexpr int EPT = 8;                    // transitions per thread
 constexpr int CHUNK = TPB * EPT;          // transitions per workgroup
 
-struct Affine { float c, d; };            // x ↦ d + c·x
-
-__device__ __forceinline__ Affine compose(Affine a, Affine b) {   // a ∘ b  (b is applied first)
-    return Affine{a.c * b.c, a.d + a.c * b.d};
-}
+using ppo::compose;
+using Affine = ppo::Affine<float>;       // x ↦ d + c·x; compose(a, b): b is applied first
 
 __device__ __forceinline__ float delta_at(const float* v, const float* vn, const float* r, const uint8_t* term,
                                           float gamma, long t) {
@@ -51,29 +52,9 @@ __device__ __forceinline__ Affine thread_transform(const float* v, const float* 
     return T;
 }
 
-// Exclusive right-to-left scan of per-thread transforms inside the workgroup.
-// Returns the composition of all LATER threads of the block (identity for the last thread);
-// *block_total receives the composition of the whole block.
+// exclusive right-to-left scan inside the workgroup: all LATER threads composed; *block_total: the whole block
 __device__ __forceinline__ Affine block_suffix_exclusive(Affine T, Affine* wave_tot, Affine* block_total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // inclusive suffix within the wave: lane l ← T_l ∘ T_{l+1} ∘ … ∘ T_63
-    Affine inc = T;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        Affine other{__shfl_down(inc.c, o, 64), __shfl_down(inc.d, o, 64)};
-        if (lane + o < 64) inc = compose(inc, other);
-    }
-    Affine excl{__shfl_down(inc.c, 1, 64), __shfl_down(inc.d, 1, 64)};
-    if (lane == 63) excl = Affine{1.f, 0.f};
-    if (lane == 0) wave_tot[w] = inc;
-    __syncthreads();
-    // compositions of the waves after w
-    Affine after{1.f, 0.f};
-    for (int k = TPB / 64 - 1; k > w; --k) after = compose(wave_tot[k], after);
-    Affine tot{1.f, 0.f};
-    for (int k = TPB / 64 - 1; k >= 0; --k) tot = compose(wave_tot[k], tot);
-    *block_total = tot;
-    return compose(excl, after);
+    return ppo::block_scan_exclusive<ppo::RightToLeft, TPB>(T, wave_tot, block_total);
 }
 
 __global__ void gae_block_kernel(const float* __restrict__ v, const float* __restrict__ vn,
@@ -105,6 +86,7 @@ __global__ void gae_apply_kernel(const float* __restrict__ v, const float* __res
                                  float* __restrict__ adv_target, double* __restrict__ wpart) {
     __shared__ Affine wave_tot[TPB / 64];
     __shared__ double red[TPB / 64];
+    __shared__ int red_n[TPB / 64];
     const long t0 = (long)blockIdx.x * CHUNK + (long)threadIdx.x * EPT;
     const Affine T = thread_transform(v, vn, r, term, trunc, t0, n, gamma, gl);
     Affine tot;
@@ -127,70 +109,18 @@ __global__ void gae_apply_kernel(const float* __restrict__ v, const float* __res
             cnt++;
         }
     }
-    // per-workgroup Welford triple (n, mean, M2): two-pass over registers, double accumulation
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double s = sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    int c_tot = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c_tot += __shfl_xor(c_tot, o, 64);
-    __syncthreads();
-    if (lane == 0) { red[w] = s; wave_tot[w].c = (float)c_tot; }
-    __syncthreads();
-    double bs = 0.0; long bn = 0;
-    for (int k = 0; k < TPB / 64; ++k) { bs += red[k]; bn += (long)wave_tot[k].c; }
-    const double mean = bn > 0 ? bs / (double)bn : 0.0;
-    double m2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e)
-        if (t0 + e < n) { const double d = (double)a[e] - mean; m2 += d * d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-    __syncthreads();
-    if (lane == 0) red[w] = m2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double bm2 = 0.0;
-        for (int k = 0; k < TPB / 64; ++k) bm2 += red[k];
-        wpart[3 * blockIdx.x + 0] = (double)bn;
-        wpart[3 * blockIdx.x + 1] = mean;
-        wpart[3 * blockIdx.x + 2] = bm2;
-    }
+    ppo::block_two_pass_triple<TPB>(sum, cnt, a, n - t0, red, red_n, wpart + 3 * blockIdx.x);
 }
 
-// Chan/Golub/LeVeque pairwise combine of `count` triples (n, mean, M2), one thread (count ≤ a few 1000)
-// Chan et al. combine of two (n, mean, M2) triples; an empty side leaves the other as is
-__device__ __forceinline__ void chan(double& n, double& mean, double& m2, double nb, double mb, double m2b) {
-    if (nb <= 0.0) return;
-    if (n <= 0.0) { n = nb; mean = mb; m2 = m2b; return; }
-    const double nn = n + nb, d = mb - mean;
-    mean += d * nb / nn;
-    m2 += m2b + d * d * n * nb / nn;
-    n = nn;
-}
-
-// one 256-thread workgroup: each thread combines a contiguous run of parts in order, then a
-// pairwise tree over the threads (was one thread over every part: 116 µs for C4's 512 parts)
+// `count` triples (n, mean, M2) → one, by one 256-thread workgroup: ppo::fold_runs_tree under
+// ppo::chan_ref_order, the reference's operation order (was one thread over every part: 116 µs for C4's 512 parts)
 constexpr int WF_T = 256;
 __global__ __launch_bounds__(WF_T) void welford_combine_kernel(const double* __restrict__ parts, int count,
                                                                 double* __restrict__ out) {
-    __shared__ double sn[WF_T], sm[WF_T], s2[WF_T];
-    const int t = threadIdx.x;
-    const int per = (count + WF_T - 1) / WF_T;
-    double n = 0.0, mean = 0.0, m2 = 0.0;
-    for (int i = t * per; i < min(count, (t + 1) * per); ++i) chan(n, mean, m2, parts[3 * i], parts[3 * i + 1], parts[3 * i + 2]);
-    sn[t] = n; sm[t] = mean; s2[t] = m2;
-    __syncthreads();
-    for (int off = 1; off < WF_T; off <<= 1) {
-        if ((t & (2 * off - 1)) == 0) {
-            double a = sn[t], am = sm[t], a2 = s2[t];
-            chan(a, am, a2, sn[t + off], sm[t + off], s2[t + off]);
-            sn[t] = a; sm[t] = am; s2[t] = a2;
-        }
-        __syncthreads();
-    }
-    if (t == 0) { out[0] = sn[0]; out[1] = sm[0]; out[2] = s2[0]; }
+    __shared__ ppo::Triple s[WF_T];
+    const ppo::Triple r = ppo::fold_runs_tree<WF_T>(s, count, ppo::Triple{0.0, 0.0, 0.0}, ppo::TripleAt{parts},
+                                                    ppo::TripleMerge<ppo::chan_ref_order>{});
+    if (threadIdx.x == 0) { out[0] = r.n; out[1] = r.mean; out[2] = r.m2; }
 }
 
 __global__ void normalize_kernel(float* __restrict__ adv, long n, const double* __restrict__ wf,

@@ -20,32 +20,23 @@
 //
 // Deterministic by construction, as clip.hip: the grid is a function of m only, every thread sums its
 // grid-stride rows in index order in double, a workgroup folds its 256 sums by a fixed LDS tree, and the last
-// workgroup to arrive folds the ≤ 256 workgroup partials by the same tree — no floating-point atomic.  The
-// hand-off is clip.hip's ticket form: each workgroup's two 8-byte partials are stored write-through at agent
-// scope and drained before its ticket add; the last arriver acquires once and reads the partials with
-// agent-scope loads.
+// workgroup to arrive folds the ≤ 256 workgroup partials by the same tree — no floating-point atomic.  The tree
+// (block_sum_halving) and the hand-off (ticket_publish / ticket_load, two 8-byte partials per workgroup) are
+// reduce.h's, which holds the ordering argument.
 //
 // Without a communicator the last arriver takes the decision itself (one launch per step).  With one, it only
 // writes the local sums; the caller all-reduces those four floats and kl_decide_kernel decides from the global
 // sums, so every rank takes the same decision from the same bits.
 #include "dev.h"
 #include "ppo_math.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int TPB = 256;
 
-__device__ __forceinline__ double block_sum(double v, double* s) {
-    s[threadIdx.x] = v;
-    __syncthreads();
-    for (int w = TPB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
-        __syncthreads();
-    }
-    const double r = s[0];
-    __syncthreads();
-    return r;
-}
+// reduce.h's halving tree over the workgroup's 256 doubles
+__device__ __forceinline__ double block_sum(double v, double* s) { return ppo::block_sum_halving<TPB>(v, s); }
 
 // one thread, from rec->sums (local, or all-reduced over the ranks): the step's statistics and the decision
 __device__ __forceinline__ void decide(PhipKlRec* rec, float target_kl, double rows_global) {
@@ -104,30 +95,14 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
     const double part_kl = block_sum(kl, s);
     const double part_cnt = block_sum(cnt, s);
 
-    if (threadIdx.x == 0) {
-        unsigned long long* slot = reinterpret_cast<unsigned long long*>(&rec->partial[2 * blockIdx.x]);
-        __hip_atomic_store(slot, (unsigned long long)__double_as_longlong(part_kl), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(slot + 1, (unsigned long long)__double_as_longlong(part_cnt), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the write-through stores have left this CU
-        const unsigned t = __hip_atomic_fetch_add(&rec->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const bool last = t == gridDim.x - 1;
-        if (last) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        s[TPB] = last ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    if (s[TPB] == 0.0) return;                // uniform over the workgroup
+    const double part[2] = {part_kl, part_cnt};
+    if (!ppo::ticket_publish(&rec->partial[2 * blockIdx.x], part, &rec->ticket, &s[TPB])) return;
 
     // the last workgroup: every partial of this launch is visible; fold them in index order
     double pk = 0.0, pc = 0.0;
     if (threadIdx.x < gridDim.x) {
-        const unsigned long long* slot = reinterpret_cast<const unsigned long long*>(&rec->partial[2 * threadIdx.x]);
-        pk = __longlong_as_double((long long)__hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        pc = __longlong_as_double((long long)__hip_atomic_load(slot + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        pk = ppo::ticket_load(&rec->partial[2 * threadIdx.x]);
+        pc = ppo::ticket_load(&rec->partial[2 * threadIdx.x + 1]);
     }
     const double tk = block_sum(pk, s);
     const double tc = block_sum(pc, s);

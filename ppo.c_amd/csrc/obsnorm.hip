@@ -17,12 +17,13 @@
 //
 // Statistics are deterministic: no floating-point atomic anywhere.  A thread sums its rows in the shifted
 // form (K = its first element; Σ(x − K), Σ(x − K)² in double — never Σx²), the workgroup folds its row
-// threads by Chan's pairwise combine in thread order through LDS, each workgroup writes one partial
+// threads by Chan's pairwise combine (reduce.h's chan) in thread order through LDS, each workgroup writes one partial
 // (mean, M2) per column, and a second launch folds the ≤ 512 partials of a column in a fixed two-level order
 // (16 groups of consecutive partials in index order, then the groups in order).  The grid
 // is a function of (n, S, alignment) only, so the same rows give the same bits.  The clamped-element
 // counter is an integer atomic: exact in any order.
 #include "dev.h"
+#include "reduce.h"
 
 namespace {
 
@@ -46,15 +47,7 @@ Tile tile_for(int S, bool vec) {
     return t;
 }
 
-// (na, ma, Ma) ← (na, ma, Ma) ⊕ (nb, mb, Mb), Chan et al.; an empty b leaves a as it is
-__device__ __forceinline__ void chan(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-    if (!(nb > 0.0)) return;
-    if (!(na > 0.0)) { na = nb; ma = mb; Ma = Mb; return; }
-    const double n = na + nb, delta = mb - ma;
-    ma = ma + delta * (nb / n);
-    Ma = (Ma + Mb) + delta * delta * (na * (nb / n));
-    na = n;
-}
+using ppo::chan;                    // (na, ma, Ma) ← (na, ma, Ma) ⊕ (nb, mb, Mb), reduce.h
 
 template <int U> struct Vec;
 template <> struct Vec<4> { using T = float4; };

@@ -13,13 +13,15 @@
 //   3. ret_apply_kernel   recompute with the true carry; the returns themselves are written only when the
 //                         caller wants them; emits carry_out[e] = cont[e] ? R_{e·T+T−1} : 0 and the workgroup's
 //                         Welford triple (n, mean, M2), two passes over registers, in double
-// then ret_finish_kernel — one workgroup: the partials combined by Chan's combine in a fixed order (each thread a
-// contiguous run in index order, then a pairwise tree over the threads), folded into the running triple, the
+// (the affine map, its block scan — here double, left to right — and the two-pass triple are reduce.h's)
+// then ret_finish_kernel — one workgroup: the partials combined by reduce.h's chan in fold_runs_tree's fixed order
+// (each thread a contiguous run in index order, then a pairwise tree), folded into the running triple, the
 // fp32 scale s = (float)(1/sqrt(M2/n + 1e-8)) refreshed and the clamp counters cleared, in one launch — and
 // ret_scale_kernel: y = clamp(r·s, ±c) into a shadow of the rewards, counting clamped elements with integer
 // atomics.  The composition order is a function of (n, seg_len) only and there is no floating-point atomic, so
 // the same input gives the same bits.
 #include "dev.h"
+#include "reduce.h"
 
 namespace {
 
@@ -28,14 +30,9 @@ constexpr int EPT = 8;                    // rows per thread
 constexpr int CHUNK = TPB * EPT;          // rows per workgroup (ppo_ext.h PPO_RET_CHUNK)
 static_assert(CHUNK == PPO_RET_CHUNK, "ppo_ext.h PPO_RET_CHUNK is the scan's workgroup chunk");
 
-struct Aff { double a, d; };              // x ↦ d + a·x
-
-// `first` applied first, then `then`
-__device__ __forceinline__ Aff after(Aff then, Aff first) { return Aff{then.a * first.a, then.d + then.a * first.d}; }
-
-__device__ __forceinline__ Aff shfl_up_aff(Aff v, int o) {
-    return Aff{__shfl_up(v.a, o, 64), __shfl_up(v.d, o, 64)};
-}
+using ppo::compose;
+using ppo::LeftToRight;
+using Aff = ppo::Affine<double>;         // x ↦ d + c·x; compose(then, first): `first` is applied first
 
 // a thread's EPT rows [t0, t0 + EPT) ∩ [0, n): d[e] = r + g·c, a[e] = g·k_{row−1}; rows past n are the identity.
 // vec: the pointers are 16-/8-byte aligned (t0 is a multiple of 8), so a full thread reads two float4s and two
@@ -89,30 +86,13 @@ __device__ __forceinline__ Rows load_rows(const float* __restrict__ r, const uin
 __device__ __forceinline__ Aff thread_transform(const Rows& w) {
     Aff T{1.0, 0.0};
 #pragma unroll
-    for (int e = 0; e < EPT; ++e) T = after(Aff{w.a[e], w.d[e]}, T);
+    for (int e = 0; e < EPT; ++e) T = compose(Aff{w.a[e], w.d[e]}, T);
     return T;
 }
 
-// Exclusive left-to-right scan of the per-thread transforms inside the workgroup: returns the composition of
-// all EARLIER threads (the identity for thread 0); *block_total receives the composition of the whole block.
+// exclusive left-to-right scan inside the workgroup: all EARLIER threads composed; *block_total: the whole block
 __device__ __forceinline__ Aff block_prefix_exclusive(Aff T, Aff* wave_tot, Aff* block_total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    Aff inc = T;                          // lane l ← T_l after … after T_0
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const Aff other = shfl_up_aff(inc, o);
-        if (lane >= o) inc = after(inc, other);
-    }
-    Aff excl = shfl_up_aff(inc, 1);
-    if (lane == 0) excl = Aff{1.0, 0.0};
-    if (lane == 63) wave_tot[w] = inc;
-    __syncthreads();
-    Aff before{1.0, 0.0};
-    for (int k = 0; k < w; ++k) before = after(wave_tot[k], before);
-    Aff tot{1.0, 0.0};
-    for (int k = 0; k < TPB / 64; ++k) tot = after(wave_tot[k], tot);
-    *block_total = tot;
-    return after(excl, before);
+    return ppo::block_scan_exclusive<LeftToRight, TPB>(T, wave_tot, block_total);
 }
 
 __global__ void __launch_bounds__(TPB) ret_block_kernel(const float* __restrict__ r, const uint8_t* __restrict__ term,
@@ -124,7 +104,7 @@ __global__ void __launch_bounds__(TPB) ret_block_kernel(const float* __restrict_
     const Rows w = load_rows(r, term, trunc, t0, n, g, seg_len, carry_in, vec);
     Aff tot;
     block_prefix_exclusive(thread_transform(w), wave_tot, &tot);
-    if (threadIdx.x == 0) agg[blockIdx.x] = make_double2(tot.a, tot.d);
+    if (threadIdx.x == 0) agg[blockIdx.x] = make_double2(tot.c, tot.d);
 }
 
 // carry[b] = the return entering workgroup b from the left (carry[0] = 0): one wave scans the aggregates 64 at
@@ -137,16 +117,11 @@ __global__ void __launch_bounds__(64) ret_carry_kernel(const double2* __restrict
         const int b = base + lane;
         Aff inc{1.0, 0.0};
         if (b < nblocks) { const double2 v = agg[b]; inc = Aff{v.x, v.y}; }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const Aff other = shfl_up_aff(inc, o);
-            if (lane >= o) inc = after(inc, other);
-        }
-        Aff excl = shfl_up_aff(inc, 1);
-        if (lane == 0) excl = Aff{1.0, 0.0};
-        if (b < nblocks) carry[b] = excl.d + excl.a * x;
-        const double last_a = __shfl(inc.a, 63, 64), last_d = __shfl(inc.d, 63, 64);
-        x = last_d + last_a * x;
+        inc = ppo::wave_scan_inclusive<LeftToRight>(inc);
+        const Aff excl = ppo::wave_scan_exclusive<LeftToRight>(inc);
+        if (b < nblocks) carry[b] = excl.d + excl.c * x;
+        const double last_c = __shfl(inc.c, 63, 64), last_d = __shfl(inc.d, 63, 64);
+        x = last_d + last_c * x;
     }
 }
 
@@ -163,7 +138,7 @@ __global__ void __launch_bounds__(TPB) ret_apply_kernel(const float* __restrict_
     const Rows w = load_rows(r, term, trunc, t0, n, g, seg_len, carry_in, vec);
     Aff tot;
     const Aff P = block_prefix_exclusive(thread_transform(w), wave_tot, &tot);
-    double x = P.d + P.a * carry[blockIdx.x];         // the return of the row before this thread's first
+    double x = P.d + P.c * carry[blockIdx.x];         // the return of the row before this thread's first
     double R[EPT];
     int cnt = 0;
     double sum = 0.0;
@@ -187,46 +162,7 @@ __global__ void __launch_bounds__(TPB) ret_apply_kernel(const float* __restrict_
             cnt++;
         }
     }
-    // per-workgroup Welford triple (n, mean, M2): two passes over registers, fixed order
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    double s = sum;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    int c_tot = cnt;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c_tot += __shfl_xor(c_tot, o, 64);
-    if (lane == 0) { red[wv] = s; red_n[wv] = c_tot; }
-    __syncthreads();
-    double bs = 0.0;
-    long bn = 0;
-    for (int k = 0; k < TPB / 64; ++k) { bs += red[k]; bn += red_n[k]; }
-    const double mean = bn > 0 ? bs / (double)bn : 0.0;
-    double m2 = 0.0;
-#pragma unroll
-    for (int e = 0; e < EPT; ++e)
-        if (t0 + e < n) { const double dd = R[e] - mean; m2 += dd * dd; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m2 += __shfl_xor(m2, o, 64);
-    __syncthreads();
-    if (lane == 0) red[wv] = m2;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double bm2 = 0.0;
-        for (int k = 0; k < TPB / 64; ++k) bm2 += red[k];
-        wpart[3 * (long)blockIdx.x + 0] = (double)bn;
-        wpart[3 * (long)blockIdx.x + 1] = mean;
-        wpart[3 * (long)blockIdx.x + 2] = bm2;
-    }
-}
-
-// (na, ma, Ma) ← (na, ma, Ma) ⊕ (nb, mb, Mb), Chan et al., in obsnorm.hip's form; an empty b leaves a as it is
-__device__ __forceinline__ void chan(double& na, double& ma, double& Ma, double nb, double mb, double Mb) {
-    if (!(nb > 0.0)) return;
-    if (!(na > 0.0)) { na = nb; ma = mb; Ma = Mb; return; }
-    const double n = na + nb, delta = mb - ma;
-    ma = ma + delta * (nb / n);
-    Ma = (Ma + Mb) + delta * delta * (na * (nb / n));
-    na = n;
+    ppo::block_two_pass_triple<TPB>(sum, cnt, R, n - t0, red, red_n, wpart + 3 * (long)blockIdx.x);
 }
 
 // One workgroup.  `count` triples (workgroup partials, or rank triples in rank order; count may be 0) combined
@@ -235,28 +171,16 @@ __device__ __forceinline__ void chan(double& na, double& ma, double& Ma, double 
 __global__ void __launch_bounds__(TPB) ret_finish_kernel(const double* __restrict__ parts, int count,
                                                          double* __restrict__ batch, double* __restrict__ run,
                                                          float* __restrict__ scale, unsigned long long* counts) {
-    __shared__ double sn[TPB], sm[TPB], s2[TPB];
-    const int t = threadIdx.x;
-    const int per = (count + TPB - 1) / TPB;
-    double n = 0.0, mean = 0.0, m2 = 0.0;
-    for (int i = t * per; i < min(count, (t + 1) * per); ++i) chan(n, mean, m2, parts[3 * i], parts[3 * i + 1], parts[3 * i + 2]);
-    sn[t] = n; sm[t] = mean; s2[t] = m2;
-    __syncthreads();
-    for (int off = 1; off < TPB; off <<= 1) {
-        if ((t & (2 * off - 1)) == 0) {
-            double a = sn[t], am = sm[t], a2 = s2[t];
-            chan(a, am, a2, sn[t + off], sm[t + off], s2[t + off]);
-            sn[t] = a; sm[t] = am; s2[t] = a2;
-        }
-        __syncthreads();
-    }
-    if (t != 0) return;
-    if (batch) { batch[0] = sn[0]; batch[1] = sm[0]; batch[2] = s2[0]; }
+    __shared__ ppo::Triple s[TPB];
+    const ppo::Triple b = ppo::fold_runs_tree<TPB>(s, count, ppo::Triple{0.0, 0.0, 0.0}, ppo::TripleAt{parts},
+                                                   ppo::TripleMerge<ppo::chan>{});
+    if (threadIdx.x != 0) return;
+    if (batch) { batch[0] = b.n; batch[1] = b.mean; batch[2] = b.m2; }
     if (counts) { counts[0] = 0ull; counts[1] = 0ull; }
     if (!run) return;
     double nr = run[0], mr = run[1], Mr = run[2];
     if (count > 0) {
-        chan(nr, mr, Mr, sn[0], sm[0], s2[0]);
+        ppo::chan(nr, mr, Mr, b.n, b.mean, b.m2);
         run[0] = nr; run[1] = mr; run[2] = Mr;
     }
     if (scale) scale[0] = nr > 0.0 ? (float)(1.0 / sqrt(Mr / nr + 1e-8)) : 1.f;

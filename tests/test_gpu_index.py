@@ -11,7 +11,8 @@
   in test_gpu_dp_shards.py);
 * PPO_COMM_LOOPBACK=k (k identical ranks in one process): grad_scale 1/k, the Welford all-gather +
   combine, the empty-shard agreement and the comm stream reproduce the one-GPU update;
-* the Welford combine on unequal triples against the numpy Chan combine.
+* the Welford combine on unequal triples against the numpy Chan combine, and bit for bit against gae_ref.py's
+  restatement of its operation order and fold order.
 """
 import ctypes as C
 
@@ -236,3 +237,41 @@ def test_welford_combine_unequal(lib):
     assert abs(m2 - ((allx - allx.mean()) ** 2).sum()) <= 1e-10 * m2
     d_parts.free()
     d_out.free()
+
+
+def _welford_parts(count, empty=()):
+    """`count` triples of unequal sizes with non-dyadic means (so the two Chan forms round differently), the ones
+    at `empty` zeroed."""
+    rng = np.random.default_rng(1004 + count)          # chosen on the CPU: every case from two triples on separates
+    parts = np.stack([rng.integers(1, 4000, count).astype(np.float64), rng.normal(0.1, 3.0, count),
+                      rng.uniform(0.0, 50.0, count)], axis=1).reshape(count, 3)
+    parts[list(empty)] = 0.0
+    return parts
+
+
+WELFORD_CASES = [(0, ()), (1, ()), (2, ()), (3, ()), (256, ()), (257, ()), (513, ()), (300, (1, 2, 100, 150, 151, 298))]
+
+
+@pytest.mark.parametrize("count,empty", WELFORD_CASES, ids=[f"{c}" + ("-gaps" if e else "") for c, e in WELFORD_CASES])
+def test_welford_combine_bits(lib, count, empty):
+    """ppo_welford_combine against the numpy restatement of gae.hip's combine (gae_ref.py: the d·nb/nn operation
+    order, runs of ⌈count/256⌉ per thread, then the pairwise tree), all three doubles compared as uint64.  From two
+    triples on, the obsnorm-form combine (obsnorm_ref.chan) in the same fold order must give other bits in at least
+    one component: that is what shows the comparison can tell the two forms apart.  (Zero or one triple is never
+    combined, so there both forms return their input.)"""
+    import gae_ref
+    import obsnorm_ref
+
+    parts = _welford_parts(count, empty)
+    want = gae_ref.fold_runs_tree([tuple(p) for p in parts], gae_ref.chan_ref_order)
+    if count >= 2:
+        other = gae_ref.fold_runs_tree([tuple(p) for p in parts], lambda a, b: tuple(obsnorm_ref.chan(a, b)))
+        assert (other.view(np.uint64) != want.view(np.uint64)).any(), "the inputs do not separate the two Chan forms"
+    d_parts = ppo_ffi.DeviceArray.from_numpy(lib, parts.ravel() if count else np.zeros(3, np.float64))
+    d_out = ppo_ffi.DeviceArray.from_numpy(lib, np.full(3, np.nan, np.float64))
+    lib.ppo_welford_combine(d_parts.ptr, count, d_out.ptr)
+    got = d_out.to_numpy(np.float64, 3)
+    d_parts.free()
+    d_out.free()
+    print(count, got.view(np.uint64), want.view(np.uint64))
+    np.testing.assert_array_equal(got.view(np.uint64), want.view(np.uint64))

@@ -1,5 +1,6 @@
 """The per-row PPO arithmetic and the Feistel order are written once in ppo.c_amd ("One definition
-per arithmetic"): csrc/ppo_math.h, csrc/feistel.h and csrc/ppo_hip.h hold them, and no kernel restates them.
+per arithmetic"): csrc/ppo_math.h, csrc/feistel.h and csrc/ppo_hip.h hold them, and no kernel restates them.  So are
+the fixed-order reductions of the statistics kernels, in csrc/reduce.h.
 
 Each token below marks one of those definitions — a constant or an expression that a pasted copy would carry
 with it — and has to occur on exactly one line of exactly one file under ppo.c_amd/csrc and ppo.c_amd/host.
@@ -19,6 +20,14 @@ TOKENS = [
     "(1 + log(2 * M_PI))",          # entropy_start
     "while ((1ULL << bits)",        # feistel_domain
     "0x9E3779B97F4A7C15",           # splitmix64
+    "delta * delta * (na * (nb / n))",                  # reduce.h chan
+    "d * d * n * nb / nn",                              # reduce.h chan_ref_order (gae.hip's other order)
+    "min(count, (t + 1) * per)",                        # reduce.h fold_runs_tree: the runs
+    "(t & (2 * stride - 1)) == 0",                      # reduce.h tree_fold: the pairwise tree
+    "bs / (double)bn",                                  # reduce.h block_two_pass_triple
+    "a.d + a.c * b.d",                                  # reduce.h compose of two affine maps
+    "w > 0; w >>= 1",                                   # reduce.h block_sum_halving
+    '__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")',  # reduce.h ticket_publish
 ]
 
 
