@@ -131,6 +131,9 @@ void ppo_update(void* ppo, float gamma, int batch_size, int n_epochs_policy, int
  * out[29]=the advantage-normalisation mode (ppo_set_adv_norm), out[30] / out[31]=the smallest / largest segment sd of
  * the last update's per-minibatch normalisation (NaN if a segment's sd is NaN; under data parallelism THIS RANK's
  * segments) (all three 0 while it is off; callers passing n <= 29 see no change).
+ * out[32]=the KL monitor's estimator (ppo_set_kl_estimator; out[13] is the DECIDING estimator's value), out[33]=the
+ * other estimator's value of the same step — k3 while the closed-form estimator decides; 0 while the monitor is off
+ * and 0 under PPO_KL_K3, which does not evaluate the closed form (callers passing n <= 32 see no change).
  * With the categorical policy (ppo_set_action_dist 1) — or the multi-discrete one, its joint row entropy — out[4] is the
  * mean row entropy of the last policy step's
  * minibatch (Σ H / rows as the head accumulated it; 0 before the first policy step; under data parallelism THIS
@@ -184,6 +187,55 @@ int    ppo_kl_history(void* ppo, double* out, int n);
  * [m] → out2 = {approximate KL, clip fraction}; returns 0, −1 for bad arguments; synchronises */
 int    ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float* d_action, const float* d_old_lp,
                             int m, int A, float eps, double* out2);
+/* The KL monitor's estimator (PPO_KL_K3 by default: everything above, bit for bit, nothing allocated or launched).
+ * PPO_KL_EXACT: while the monitor runs (a target KL, or the adaptive schedule), the kl that stops the loop, moves the
+ * adaptive rate, fills ppo_kl_history and out[13] is the CLOSED-FORM KL(old ‖ new) between the behaviour distribution
+ * and the current one, averaged over the minibatch's rows — what rl_games and rsl_rl drive their adaptive rule with:
+ * non-negative, free of sampling variance, and defined for every policy here.  Per row, fp32 inputs, double arithmetic
+ * (csrc/ppo_math.h, which this quotes), j / k / d ascending:
+ *   Gaussian, old (μo, lso), new (μn, lsn), ls = log σ:    d = lso_j − lsn_j
+ *       KL = Σ_j (0.5·expm1(2d) − d) + 0.5·(μo_j − μn_j)²·exp(−2·lsn_j)
+ *     the textbook diagonal-Gaussian KL in a form that does not cancel near d = 0.  rsl_rl adds 1e-5 inside its log
+ *     (log(σn/σo + 1e-5)); libppo does not.
+ *   categorical / multi-discrete / masked, per component d over its EFFECTIVE allowed columns only (ppo_set_action_mask's
+ *     three rules: the stored bits; none set → all allowed; the chosen column OR-ed in):
+ *       lo_k = (zo_k − Mo) − log Σ_k exp(zo_k − Mo),  ln_k likewise from the new logits
+ *       s = Σ_k exp(lo_k)·(lo_k − ln_k),   KL_d = s < 0 ? 0 : s (a NaN stays NaN),   KL = Σ_d KL_d
+ *     A masked column is read in neither the old nor the new logits: a NaN or 1e30 there changes no output bit.
+ * The behaviour distribution needs no rollout plumbing: policy parameters do not change between a rollout and its
+ * ppo_update, so at the head of every update (only while PPO_KL_EXACT is set AND the monitor is on) μ is forwarded over
+ * state[0, limit) — the normalised shadow while observation normalisation is on — in chunks of at most 16384 rows into
+ * a PPO-owned device store [capacity, A] (means or logits; allocated on first use, freed with the PPO), and log σ is
+ * snapshotted.  That serves every way of filling the buffer (device and open rollouts, ppo_fill_synthetic, caller-laid
+ * rows).  The policy steps' one KL launch then reads the store in place through the step's row indices and sums the
+ * row KLs beside k3 and the clip fraction, which keep their bits (no launch added per step, no floating-point
+ * atomics).  A chunk's forward may pick another GEMM configuration than a minibatch's, so the first policy step's
+ * exact KL is tiny but NEED NOT BE 0.  The store is a function of (parameters, buffer): ppo_save_state keeps the
+ * setting alone (files and ppo_state_hash of PPOs that never set it are unchanged), save_ppo nothing.  Under data
+ * parallelism the sum rides in the monitor's existing 16-byte all-reduce: no collective is added and the order of
+ * collectives does not depend on the setting, but EVERY RANK MUST HOLD THE SAME ESTIMATOR, or the ranks decide from
+ * different numbers.  With PPO_KL_EXACT and the monitor off nothing is allocated or launched either.
+ * Returns 0, or −1 with the setting unchanged for a NULL ppo or an unknown estimator. */
+enum { PPO_KL_K3 = 0, PPO_KL_EXACT = 1 };
+int    ppo_set_kl_estimator(void* ppo, int estimator);
+int    ppo_get_kl_estimator(void* ppo);                   /* the estimator; 0 for NULL */
+/* ppo_kl_history for either estimator: the deciding one's values, or — while PPO_KL_EXACT decides — k3's of the same
+ * steps; returns 0 steps for PPO_KL_EXACT while the estimator is PPO_KL_K3 (never evaluated) and for an unknown
+ * estimator; synchronises */
+int    ppo_kl_history_est(void* ppo, int estimator, double* out, int n);
+/* the device store [limit, A] the last ppo_update filled (means or logits by buffer row) and, through d_log_std_old
+ * (may be NULL), its log σ snapshot [A] (Gaussian policy); NULL / NULL if no update has filled it */
+const float* ppo_kl_old_dist(void* ppo, const float** d_log_std_old);
+/* the update's KL launch on caller-supplied device arrays (a test entry): dist 0 = Gaussian (both log σ [A] needed,
+ * nvec / D / d_mask unused), 1 = categorical (nvec = {A}), 2 = multi-discrete over nvec[D].  d_new [m, A]; minibatch row
+ * i reads d_old[d_rows[i]·A] (d_rows NULL: i) and, under a mask (dist 1 / 2, d_mask not NULL), its (A + 31) / 32 words
+ * at d_mask[d_rows[i]·W] as ppo_masked_head_device does; d_action [m, A] is needed only under a mask (rule 3).
+ * d_row_kl (may be NULL) [m] ← every row's KL in double; *out_mean = (double)(float)Σ / m, the sum as the record keeps
+ * it.  Returns 0, or −1 with nothing launched for bad arguments; synchronises */
+int    ppo_policy_kl_exact_device(int dist, const float* d_new, const float* d_log_std_new, const float* d_old,
+                                  const float* d_log_std_old, const int* d_rows, const float* d_action,
+                                  const uint32_t* d_mask, int m, int A, const int* nvec, int D, double* d_row_kl,
+                                  double* out_mean);
 /* Per-minibatch advantage normalisation (off by default; not in the reference, whose gae normalises once per update
  * over the whole buffer: A ← (A − μ)/(σ_pop + 1e-8), which libppo keeps doing in every mode; Stable-Baselines3
  * normalize_advantage = True and CleanRL norm_adv = True, both their defaults).  With PPO_ADV_NORM_MINIBATCH every
@@ -254,9 +306,11 @@ int ppo_adv_norm_read(void* ppo, long step, int* rows, float* adv, int cap);
  *                    A NaN kl changes nothing; once target-KL early stopping has stopped the update, the rate no
  *                    longer changes.  The step's own policy and entropy Adams read the new word through a pointer
  *                    (step = lr / bias_correction1 computed by the kernel: the fp32 division the host does otherwise,
- *                    so an equal rate gives equal bits); the host never reads the rate inside an epoch.  kl is the k3
- *                    estimator of ppo_set_target_kl above — mean(expm1(x) − x) over the minibatch — NOT the
- *                    closed-form Gaussian KL rsl_rl evaluates, so a desired_kl tuned there carries over only roughly.
+ *                    so an equal rate gives equal bits); the host never reads the rate inside an epoch.  kl is the
+ *                    monitor's estimator (ppo_set_kl_estimator): by default k3 of ppo_set_target_kl above —
+ *                    mean(expm1(x) − x) over the minibatch — which is NOT the closed-form KL rsl_rl evaluates, so a
+ *                    desired_kl tuned there carries over only roughly; with PPO_KL_EXACT it is that closed-form KL,
+ *                    and an rsl_rl desired_kl carries over up to the 1e-5 rsl_rl adds inside its log.
  *                    The value rate stays ppo->lr_V by value unless coupled (below).  As target KL, the schedule
  *                    takes the multi-launch loop (no single-workgroup / cluster phases, no graph replay) and works
  *                    with clipping, both normalisers, the discrete policies and bf16 mode.  Under data parallelism

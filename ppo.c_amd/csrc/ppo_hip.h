@@ -448,7 +448,8 @@ void phip_grad_norm(const float* g, long n, const float* side, long n_side, floa
  * Everything ahead of `ticket` is the head the host reads at policy-epoch boundaries. */
 typedef struct {
     float sums[4];                  /* [0] Σ KL terms, [1] clipped rows of this rank's minibatch (16-B aligned:
-                                     * all-reduced under data parallelism), [2..3] zero */
+                                     * all-reduced under data parallelism), [2] Σ closed-form KL of its rows (zero
+                                     * without that estimator), [3] zero */
     float kl, clip_frac;            /* of the last decided step, over the global minibatch */
     unsigned stopped;               /* sticky within one update: the Adam kernels take no step while set */
     unsigned step;                  /* policy steps decided in this update */
@@ -466,7 +467,24 @@ typedef struct {
     unsigned lr_raised, lr_lowered; /* steps that raised / lowered the rate since the counters were cleared */
     unsigned lr_pad;
     float lr_hist[PHIP_KL_HIST];    /* the rate each decided step's Adam used */
+    /* the closed-form estimator (ppo_set_kl_estimator, PPO_KL_EXACT), behind everything the record held before: a
+     * launch without it neither reads nor writes anything below */
+    double partial_x[3 * PHIP_KL_PARTS]; /* its launches' three partials per workgroup (`partial` keeps the two) */
+    float hist_other[PHIP_KL_HIST]; /* the estimator that did NOT decide (k3), per decided step */
+    float kl_other;                 /* … and of the last decided step */
+    unsigned x_pad;
 } PhipKlRec;
+/* the closed-form estimator's inputs of one launch (by value; NULL at phip_policy_kl: the k3 launch and its bits) */
+typedef struct {
+    const float* old_dist;          /* the behaviour distribution's A outputs per row: minibatch row i reads
+                                     * old_dist[rows[i]·A] (rows NULL: i) — means (Gaussian) or logits (discrete) */
+    const float* old_log_std;       /* Gaussian: the behaviour log σ [A]; unread otherwise */
+    const int* rows;
+    const int* off;                 /* discrete: device offsets (D + 1) of the components, the categorical policy as */
+    int D;                          /* {0, A}; NULL: Gaussian */
+    int wide;                       /* discrete: some component is wider than 32 — a wave walks each row */
+    double* row_kl;                 /* NULL, or [m] ← every row's KL (the test entry) */
+} PhipKlExact;
 /* Σ (expm1(x) − x) and the clipped-row count of one policy minibatch (x = log-prob − old log-prob, rows of
  * μ [m, A]) into rec->sums; one launch, deterministic (no floating-point atomics, grid a function of m), no
  * host read.  decide_here != 0: the same launch also decides (below) from the local sums */
@@ -475,14 +493,20 @@ typedef struct {
  * the joint one (md_off and D are unread otherwise).  mask (NULL: today's path and bits; needs dist 2, the
  * categorical policy passing the offsets {0, A}): minibatch row i reads its (A + 31) / 32 words at mask[rows[i]·W]
  * (rows NULL: i) and lp is the masked joint log-prob (ppo_math.h md_log_prob_row over MaskRow) */
+/* ex (NULL: the launch above, bit for bit): the same launch also sums the closed-form KL(old ‖ new) of every row
+ * (ppo_math.h kl_gauss_row / kl_cat_row under the launch's mask) into rec->sums[2], a third partial per workgroup
+ * through the same tree and ticket; the k3 sum and the clipped count keep their bits.  The decision then takes
+ * sums[2] and keeps k3 in hist_other / kl_other.  old_lp NULL (with ex only: the test entry): k3 and the count are
+ * skipped and left 0, action is read under a mask alone */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
-                    const int* md_off, int D, const uint32_t* mask, const int* rows);
-/* kl = sums[0] / rows_global, clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
+                    const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex);
+/* kl = sums[0] / rows_global (exact != 0: sums[2] / rows_global, and kl_other = hist_other[step] = the former),
+ * clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
  * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the
  * all-reduce of rec->sums, with rows_global = m · world: every rank must hold the same target_kl setting, so
  * that all ranks issue the same order of collectives */
-void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global);
+void phip_kl_decide(PhipKlRec* rec, float target_kl, long rows_global, int exact);
 /* rec->lr_v = lr_V · (rec->lr / base) in fp32, one thread (value-rate coupling of the adaptive schedule) */
 void phip_lr_couple(PhipKlRec* rec, float lr_V, float base);
 /* the host waits for the launches issued so far on the current stream only (an event recorded there) */

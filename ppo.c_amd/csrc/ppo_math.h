@@ -230,6 +230,70 @@ __device__ __forceinline__ auto mask_row(const uint32_t* w) {
     else return NoMask{};
 }
 
+// ---- Closed-form KL(old ‖ new) of one row (ppo_set_kl_estimator, PPO_KL_EXACT; the KL monitor, kl.hip; no
+// counterpart in the reference): fp32 inputs, every operation in double, j / k / d ascending.
+// Diagonal Gaussian, old (μo, lso) and new (μn, lsn) with ls = log σ, per column j:
+//     d      = lso_j − lsn_j
+//     term_j = (0.5·expm1(2d) − d) + 0.5·(μo_j − μn_j)²·exp(−2·lsn_j)          kl_gauss_term
+//     KL     = Σ_j term_j
+// the textbook log(σn/σo) + (σo² + Δμ²)/(2σn²) − ½ with σo²/(2σn²) − ½ written as ½·expm1(2d), which does not cancel
+// near d = 0; identical inputs give exactly 0.  rsl_rl adds 1e-5 inside its log (log(σn/σo + 1e-5)); this does not.
+// Categorical / multi-discrete / masked, per component over its EFFECTIVE allowed columns only ("Action masking"
+// above: the stored bits; none set → all; the chosen column OR-ed in), zo the old logits and zn the new:
+//     e_k  = exp(z_k − M),  M = max_k z_k (fp32, exact)                       kl_cat_exp
+//     lo_k = (zo_k − Mo) − log Σ_k exp(zo_k − Mo),  ln_k likewise from zn    kl_cat_logp
+//     s    = Σ_k exp(lo_k)·(lo_k − ln_k)                                      kl_cat_term
+//     KL_d = s < 0 ? 0 : s   (a NaN stays NaN)                                kl_cat_clamp
+//     KL   = Σ_d KL_d
+// A masked column is read in neither zo nor zn.  One thread walks a component k ascending (kl_cat_component); a
+// kernel that spreads a wide component over a wave sums each lane's k ascending and combines the lanes by its fixed
+// tree, through the same atoms.  tests/kl_exact_ref.py restates it.
+__device__ __forceinline__ double kl_gauss_term(float mo, float lso, float mn, float lsn) {
+    const double d = (double)lso - (double)lsn;
+    const double dm = (double)mo - (double)mn;
+    return (0.5 * expm1(2.0 * d) - d) + 0.5 * (dm * dm) * exp(-2.0 * (double)lsn);
+}
+__device__ __forceinline__ double kl_gauss_row(const float* mo, const float* lso, const float* mn, const float* lsn,
+                                               int A) {
+    double kl = 0.0;
+    for (int j = 0; j < A; ++j) kl += kl_gauss_term(mo[j], lso[j], mn[j], lsn[j]);
+    return kl;
+}
+__device__ __forceinline__ double kl_cat_exp(float z, float M) { return exp((double)z - (double)M); }
+__device__ __forceinline__ double kl_cat_logp(float z, float M, double ls) { return ((double)z - (double)M) - ls; }
+__device__ __forceinline__ double kl_cat_term(double lo, double ln) { return exp(lo) * (lo - ln); }
+__device__ __forceinline__ double kl_cat_clamp(double s) { return s < 0.0 ? 0.0 : s; }
+// one thread, one component zo / zn[0 … n) under its effective mask mk
+template <class Mask>
+__device__ __forceinline__ double kl_cat_component(const float* zo, const float* zn, int n, const Mask& mk) {
+    const float Mo = cat_row_max(zo, n, mk), Mn = cat_row_max(zn, n, mk);
+    double so = 0.0, sn = 0.0;
+    for (int k = 0; k < n; ++k) {
+        if (!mk.allowed(k)) continue;
+        so += kl_cat_exp(zo[k], Mo);
+        sn += kl_cat_exp(zn[k], Mn);
+    }
+    const double lso = log(so), lsn = log(sn);
+    double s = 0.0;
+    for (int k = 0; k < n; ++k) {
+        if (!mk.allowed(k)) continue;
+        s += kl_cat_term(kl_cat_logp(zo[k], Mo, lso), kl_cat_logp(zn[k], Mn, lsn));
+    }
+    return kl_cat_clamp(s);
+}
+// one thread, one row of D components; action (NULL without a mask) holds the chosen indices for rule 3
+template <class RowMask>
+__device__ __forceinline__ double kl_cat_row(const float* zo, const float* zn, const int* off, int D,
+                                             const float* action, const RowMask& rm) {
+    double kl = 0.0;
+    for (int d = 0; d < D; ++d) {
+        const int o = off[d], n = off[d + 1] - o;
+        const int a = action ? cat_index(action[d], n) : -1;
+        kl += kl_cat_component(zo + o, zn + o, n, rm.component(o, n, a));
+    }
+    return kl;
+}
+
 // ---- Gaussian entropy (policy.cu:171-193): this constant, then += log σ_j for j ascending, at the call site
 // (the sum inside a helper compiled to other code than the kernels' own loops)
 __device__ __forceinline__ float entropy_start(int A) { return (float)(A * 0.5 * (1 + log(2 * M_PI))); }

@@ -93,13 +93,17 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     const int with_lr = d->lr_kind != PPO_LR_CONSTANT;
     /* … and an advantage-normalisation mode other than the global one, likewise */
     const int with_adv = d->adv_norm_mode != PPO_ADV_NORM_GLOBAL;
+    /* … and a KL estimator other than k3, likewise */
+    const int with_klest = d->kl_est != PPO_KL_K3;
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
     put_u32(img, CKPT_VERSION);
     put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
-                     (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u));
-    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv);
+                     (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u) |
+                     (with_klest ? CKPT_F_KLEST : 0u));
+    put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv +
+                     (uint32_t)with_klest);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -217,6 +221,14 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_u32(&s, (uint32_t)d->adv_norm_mode);
         put_u32(&s, 0);
         put_section(img, CKPT_TAG_ADVNORM, &s);
+        free(s.p);
+    }
+
+    if (with_klest) {
+        memset(&s, 0, sizeof(s));
+        put_u32(&s, (uint32_t)d->kl_est);
+        put_u32(&s, 0);
+        put_section(img, CKPT_TAG_KLEST, &s);
         free(s.p);
     }
     return 0;
@@ -422,6 +434,10 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
     if (ix->sec[CKPT_TAG_ADVNORM].present &&
         ppo_set_adv_norm(ppo, (int)ckpt_rd32(img + ix->sec[CKPT_TAG_ADVNORM].off)) != 0)
         return "an advantage-normalisation mode ppo_set_adv_norm declines";
+    /* the KL monitor's estimator through its setter */
+    if (ix->sec[CKPT_TAG_KLEST].present &&
+        ppo_set_kl_estimator(ppo, (int)ckpt_rd32(img + ix->sec[CKPT_TAG_KLEST].off)) != 0)
+        return "a KL estimator ppo_set_kl_estimator declines";
     phip_sync();
     return NULL;
 }

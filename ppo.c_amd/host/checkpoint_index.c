@@ -59,6 +59,8 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         return fail(ix, "the header's rollout flag and the Rollout section disagree");
     if (((ix->flags & CKPT_F_LRSCHED) != 0) != (s[CKPT_TAG_LRSCHED].present != 0))
         return fail(ix, "the header's schedule flag and the learning-rate schedule section disagree");
+    if (((ix->flags & CKPT_F_KLEST) != 0) != (s[CKPT_TAG_KLEST].present != 0))
+        return fail(ix, "header flags and the KL-estimator section disagree");
     if (((ix->flags & CKPT_F_ADVNORM) != 0) != (s[CKPT_TAG_ADVNORM].present != 0))
         return fail(ix, "the header's advantage-normalisation flag and its section disagree");
 
@@ -167,6 +169,15 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         if (ckpt_rd32(an) > CKPT_ADVNORM_MAX_MODE) return fail_tag(ix, "unknown advantage-normalisation mode", CKPT_TAG_ADVNORM);
         if (ckpt_rd32(an + 4) != 0) return fail_tag(ix, "reserved word not zero", CKPT_TAG_ADVNORM);
     }
+
+    /* the KL monitor's estimator: one other than k3 (the writer leaves the section out for that) that this version
+     * knows, and a zero word */
+    if (s[CKPT_TAG_KLEST].present) {
+        if (s[CKPT_TAG_KLEST].len != CKPT_KLEST_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_KLEST);
+        const uint8_t* ke = img + s[CKPT_TAG_KLEST].off;
+        if (ckpt_rd32(ke) > CKPT_KLEST_MAX) return fail_tag(ix, "unknown KL estimator", CKPT_TAG_KLEST);
+        if (ckpt_rd32(ke + 4) != 0) return fail_tag(ix, "reserved word not zero", CKPT_TAG_KLEST);
+    }
     return 0;
 }
 
@@ -179,7 +190,7 @@ int ckpt_index(const void* buf, size_t len, CkptIndex* ix) {
     ix->flags = ckpt_rd32(img + 12);
     ix->count = ckpt_rd32(img + 16);
     if (ix->version != CKPT_VERSION) return fail(ix, "unsupported version (this reader knows version 1)");
-    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM)) return fail(ix, "unknown header flags");
+    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST)) return fail(ix, "unknown header flags");
     if (ix->count > (len - CKPT_HEADER_BYTES) / CKPT_SECTION_BYTES)
         return fail(ix, "more sections than the file could hold");
     size_t pos = CKPT_HEADER_BYTES;

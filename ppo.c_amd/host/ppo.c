@@ -95,6 +95,8 @@ static int lr_adaptive(const PPODev* d) { return d && d->lr_kind == PPO_LR_ADAPT
 static float kl_target(const PPODev* d) {
     return d->target_kl > 0.f ? d->target_kl : lr_adaptive(d) ? INFINITY : 0.f;
 }
+/* the closed-form estimator decides (ppo_set_kl_estimator): it is selected AND the monitor runs */
+static int kl_exact(const PPODev* d) { return d->kl_est == PPO_KL_EXACT && kl_target(d) > 0.f; }
 static float clampf(float x, float lo, float hi) { return fminf(hi, fmaxf(lo, x)); }
 /* linear decay: (float)(base · (1 − (1 − f)·(min(u, N)/N))) in double, rounded once; the quotient first, so that
  * u >= N gives exactly (float)(base · f) for every N */
@@ -137,6 +139,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->ext_obs); phip_free(d->act_obsn); phip_free(d->act_lp); phip_free(d->act_rows);
     phip_free(d->mask);
     phip_free(d->adv_stats);
+    phip_free(d->kl_old); phip_free(d->kl_old_ls);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -856,9 +859,14 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const float target_kl = kl_target(d);
     const int kl_on = !tab && target_kl > 0.f;
     const long kl_rows = (long)B * phip_comm_world();
+    /* the closed-form estimator: the same launch reads the behaviour distribution the update stored at its head, in
+     * place through this step's row indices (they exist in every form of the step); its sum rides in sums[2] */
+    const int kl_x = kl_on && kl_exact(d);
+    const PhipKlExact kl_ex = {d->kl_old, d->kl_old_ls, rows, cat ? disc_off(d) : NULL, cat ? disc_D(d) : 0,
+                               cat && disc_max_n(d, A) > 32, NULL};
     if (kl_on && c->comm) {
         phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
+                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -879,10 +887,10 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (!ap->flat || !ppo->adam_entropy->flat)
             die(d->target_kl > 0.f ? "ppo_update: target-KL early stopping needs flat Adam spans"
                                    : "ppo_update: the adaptive learning-rate schedule needs flat Adam spans");
-        if (c->comm) phip_kl_decide(d->kl, target_kl, kl_rows);
+        if (c->comm) phip_kl_decide(d->kl, target_kl, kl_rows, kl_x);
         else
             phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL);
+                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -905,6 +913,31 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     }
     *ls_zero = ls_own && (adam_update_dev(ppo->adam_entropy, rate, NULL, 0, clear, coef, skip) & 2);
     *p_zero = adam_update_net(ppo->adam_policy, rate, mu, clear, coef, skip);
+}
+
+/* the closed-form estimator's behaviour distribution, at the head of an update (stream-ordered on libppo's stream,
+ * behind the observation shadow and ahead of the loops' fork): policy parameters do not change between the rollout
+ * and the update, so μ forwarded over state[0, limit) — the array the policy loop reads — IS what the rollout acted
+ * with, however the buffer was filled.  Forwarded in chunks of at most KL_OLD_CHUNK contiguous rows, so that μ's
+ * activation workspaces grow to max(B, min(limit, KL_OLD_CHUNK)) rows and never to the buffer's; 16384 rows keep the
+ * GEMMs at full-size tiles (64 chunks per 2^20 rows).  A chunk's forward may pick another GEMM configuration than a
+ * minibatch's, so the first policy step's exact KL is tiny but need not be 0. */
+#define KL_OLD_CHUNK 16384
+static void kl_old_prepare(PPO* ppo, PPODev* d, const float* state, int limit) {
+    TrajectoryBuffer* buf = ppo->buffer;
+    NeuralNetwork* mu = ppo->policy->mu;
+    const int S = buf->state_size, A = buf->action_size;
+    if (!d->kl_old) {
+        d->kl_old = (float*)phip_malloc(sizeof(float) * (size_t)buf->capacity * A);
+        d->kl_old_ls = (float*)phip_malloc(sizeof(float) * (size_t)A);
+    }
+    for (long r0 = 0; r0 < limit; r0 += KL_OLD_CHUNK) {
+        const int rows = (int)(limit - r0 < KL_OLD_CHUNK ? limit - r0 : KL_OLD_CHUNK);
+        nn_forward_dev(mu, state + r0 * S, rows);
+        phip_d2d(d->kl_old + r0 * A, mu->d_output, sizeof(float) * (size_t)rows * A);
+    }
+    if (!cat_on(d)) phip_d2d(d->kl_old_ls, ppo->policy->d_log_std, sizeof(float) * (size_t)A);
+    d->kl_old_rows = limit;
 }
 
 /* target-KL early stopping, at a policy-epoch boundary: the host waits for the policy loop's stream only
@@ -1238,6 +1271,8 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     if (kl_on) {
         phip_memset(&d->kl->stopped, 0, 2 * sizeof(unsigned));          /* stopped, step */
         phip_memset(&d->kl->stop_step, 0xFF, sizeof(int));              /* −1 */
+        /* the closed-form estimator (off: nothing launched, nothing allocated): the behaviour distribution */
+        if (kl_exact(d)) kl_old_prepare(ppo, d, state, limit);
     }
     /* the adaptive schedule's value-rate coupling: one one-thread launch, likewise ahead of the fork, fixes the
      * value Adam's word for the whole update from the policy rate as the last update left it — the value loop
@@ -1323,6 +1358,7 @@ void ppo_reset_stats(void* vppo) {
     for (int i = 0; i < 2; i++) phip_memset(d->clip[i], 0, offsetof(PhipClipRec, ticket));
     phip_memset(d->kl, 0, offsetof(PhipKlRec, ticket));      /* the head: KL, clip fraction, stop state, applied */
     phip_memset(&d->kl->lr_raised, 0, 2 * sizeof(unsigned)); /* the adaptive schedule's raises and lowerings */
+    if (d->kl_est == PPO_KL_EXACT) phip_memset(&d->kl->kl_other, 0, sizeof(float));
     phip_memset(d->vclip_counts, 0, 2 * sizeof(unsigned long long));
     d->n_v = d->n_p = d->n_graph = 0;
 }
@@ -1333,8 +1369,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[32] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[34] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1405,7 +1441,15 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[31] = hi;
         }
     }
-    for (int i = 0; i < n && i < 32; i++) out[i] = v[i];
+    if (n > 32) {            /* the KL monitor's estimator, and the other estimator's value of the last decided step */
+        v[32] = (double)d->kl_est;
+        if (kl_exact(d)) {
+            float o = 0.f;
+            phip_d2h(&o, &d->kl->kl_other, sizeof(float));
+            v[33] = o;
+        }
+    }
+    for (int i = 0; i < n && i < 34; i++) out[i] = v[i];
 }
 
 /* ppo_ext.h: running return-based reward normalisation */
@@ -1787,6 +1831,26 @@ float ppo_get_target_kl(void* vppo) {
     return ppo->dev ? ((PPODev*)ppo->dev)->target_kl : 0.f;
 }
 
+/* ppo_ext.h: the KL monitor's estimator */
+int ppo_set_kl_estimator(void* vppo, int estimator) {
+    if (!vppo || (estimator != PPO_KL_K3 && estimator != PPO_KL_EXACT)) return -1;
+    dev_ws((PPO*)vppo, 1)->kl_est = estimator;
+    return 0;
+}
+
+int ppo_get_kl_estimator(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo && ppo->dev ? ((PPODev*)ppo->dev)->kl_est : PPO_KL_K3;
+}
+
+const float* ppo_kl_old_dist(void* vppo, const float** d_log_std_old) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    const int have = d && d->kl_old && d->kl_old_rows > 0;
+    if (d_log_std_old) *d_log_std_old = have ? d->kl_old_ls : NULL;
+    return have ? d->kl_old : NULL;
+}
+
 /* ppo_ext.h: learning-rate schedules */
 int ppo_set_lr_schedule(void* vppo, int kind, float p0, float p1, float p2) {
     PPO* ppo = (PPO*)vppo;
@@ -1866,17 +1930,26 @@ int ppo_lr_history(void* vppo, float* out, int n) {
 }
 
 int ppo_kl_history(void* vppo, double* out, int n) {
+    return ppo_kl_history_est(vppo, ppo_get_kl_estimator(vppo), out, n);
+}
+
+int ppo_kl_history_est(void* vppo, int estimator, double* out, int n) {
     PPO* ppo = (PPO*)vppo;
+    if (!ppo) return 0;
     PPODev* d = dev_ws(ppo, 1);
     phip_sync();
     if (!(kl_target(d) > 0.f)) return 0;
+    /* the deciding estimator's values are in hist; under the closed-form one k3's are kept beside them */
+    const float* src = estimator == d->kl_est ? d->kl->hist
+                       : estimator == PPO_KL_K3 && d->kl_est == PPO_KL_EXACT ? d->kl->hist_other : NULL;
+    if (!src) return 0;
     unsigned steps = 0;
     phip_d2h(&steps, &d->kl->step, sizeof(unsigned));
     long have = steps < (unsigned)PHIP_KL_HIST ? (long)steps : PHIP_KL_HIST;
     if (have > n) have = n;
     if (out && have > 0) {
         float* h = (float*)xmalloc(sizeof(float) * (size_t)have);
-        phip_d2h(h, d->kl->hist, sizeof(float) * (size_t)have);
+        phip_d2h(h, src, sizeof(float) * (size_t)have);
         for (long i = 0; i < have; i++) out[i] = (double)h[i];
         free(h);
     }
@@ -1889,7 +1962,7 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
     if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
     phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
-    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL);
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, NULL);
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
     out2[0] = (double)sums[0] / m;
@@ -2159,6 +2232,37 @@ int ppo_masked_argmax_device(const float* d_logits, const uint32_t* d_mask, int 
     if (!d_off) return -1;
     phip_disc_argmax(d_logits, d_mask, d_off, d_action, m, A, D);
     phip_sync();
+    return 0;
+}
+
+/* ppo_ext.h: the closed-form KL launch of the update on caller-supplied device arrays (a test entry) */
+int ppo_policy_kl_exact_device(int dist, const float* d_new, const float* d_log_std_new, const float* d_old,
+                               const float* d_log_std_old, const int* d_rows, const float* d_action,
+                               const uint32_t* d_mask, int m, int A, const int* nvec, int D, double* d_row_kl,
+                               double* out_mean) {
+    static PhipKlRec* rec = NULL;
+    if (!d_new || !d_old || !out_mean || m <= 0 || A <= 0 || dist < 0 || dist > 2) return -1;
+    if (dist == 0 && (!d_log_std_new || !d_log_std_old || d_mask)) return -1;
+    if (d_mask && !d_action) return -1;
+    const int* d_off = NULL;
+    int max_n = 0;
+    if (dist != 0) {
+        const int one[1] = {A};
+        if (dist == 2 && (!nvec || D < 1)) return -1;
+        d_off = md_test_offsets(dist == 1 ? one : nvec, dist == 1 ? 1 : D, A, &max_n);
+        if (!d_off) return -1;
+    }
+    const int Dc = dist == 1 ? 1 : dist == 2 ? D : 0;
+    if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+    phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
+    const PhipKlExact ex = {d_old, d_log_std_old, d_rows, d_off, Dc, max_n > 32, d_row_kl};
+    /* a mask takes the multi-discrete form of the launch, the categorical policy as nvec = {A} */
+    phip_policy_kl(d_new, d_log_std_new, d_action, NULL, m, A, dist == 0 ? 0 : 2, 0.f, INFINITY, m, 1, rec, d_off, Dc,
+                   d_mask, d_mask ? d_rows : NULL, &ex);
+    phip_sync();
+    float sums[4];
+    phip_d2h(sums, rec->sums, sizeof(sums));
+    *out_mean = (double)sums[2] / m;
     return 0;
 }
 

@@ -168,6 +168,14 @@ typedef struct {
     long adv_cap;
     long gat_np, adv_np;
     int gat_B;
+    /* the KL monitor's estimator (ppo_set_kl_estimator; 0 = k3, as ever; 1 = the closed-form KL(old ‖ new)): while
+     * it is 1 and the monitor is on, every ppo_update forwards μ over the buffer at its head into kl_old
+     * [capacity, A] (means or logits, row r at r·A) and snapshots log σ into kl_old_ls [A]; the policy steps' KL
+     * launch reads both in place.  kl_old_rows: the rows the last update filled (0: none).  All NULL until first
+     * used; a function of (parameters, buffer), so no checkpoint keeps the store — only the setting */
+    int kl_est;
+    float *kl_old, *kl_old_ls;
+    long kl_old_rows;
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

@@ -155,6 +155,12 @@ _SIGS = {
     "ppo_get_target_kl": (C.c_float, [_P]),
     "ppo_kl_history": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int]),
     "ppo_policy_kl_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_double)]),
+    "ppo_set_kl_estimator": (C.c_int, [_P, C.c_int]),
+    "ppo_get_kl_estimator": (C.c_int, [_P]),
+    "ppo_kl_history_est": (C.c_int, [_P, C.c_int, C.POINTER(C.c_double), C.c_int]),
+    "ppo_kl_old_dist": (_P, [_P, C.POINTER(_P)]),
+    "ppo_policy_kl_exact_device": (C.c_int, [C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, c_int_p, C.c_int,
+                                             _P, C.POINTER(C.c_double)]),
     "ppo_set_lr_schedule": (C.c_int, [_P, C.c_int, C.c_float, C.c_float, C.c_float]),
     "ppo_get_lr_schedule": (C.c_int, [_P, C.POINTER(C.c_float)]),
     "ppo_lr_couple_value": (C.c_int, [_P, C.c_int]),

@@ -10,6 +10,12 @@ the PPO_K_ADAM class: the Adam kernel's us per launch from the off update, the K
 extra time and extra launches in monitor mode, and the class's launches in the stopped update.
 
     python tools/kl_bench.py [--rounds 3] [--updates 2] > profiles/kl_c4.txt
+
+--estimators times, instead, the same update with the monitor on (target_kl = +inf) under the k3 estimator and under
+the closed-form one (ppo_set_kl_estimator), alternating on the same build: the cost of the whole-buffer μ forward at
+the head of the update plus the wider per-step KL launch.
+
+    python tools/kl_bench.py --estimators > profiles/kl_exact_c4.txt
 """
 import argparse
 import ctypes as C
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3, help="off / +inf / stop alternations")
     ap.add_argument("--updates", type=int, default=2, help="timed updates per measurement")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--estimators", action="store_true", help="time k3 against the closed-form estimator instead")
     args = ap.parse_args()
     lib = ppo_ffi.load()
     if lib.ppo_device_count() < 1:
@@ -62,6 +69,10 @@ def main():
     rollout()
     update()                                              # warm-up
     lib.ppo_synchronize()
+    if args.estimators:
+        estimators(lib, ppo, args, rollout, update)
+        lib.free_ppo(ppo)
+        return
 
     # the target: from a monitor run, the first step of the second policy epoch or later whose KL stands above
     # every earlier step's; 1.5 x target at the geometric middle of that gap
@@ -132,6 +143,60 @@ def main():
     print(f"PPO_K_ADAM, stop: {l2} launches, {t2:.3f} ms; all classes {n2} launches, {all2:.2f} ms; stop step "
           f"{st2[16]:.0f}, policy steps issued {st2[3]:.0f} of {4 * NB}, applied {st2[15]:.0f}")
     lib.free_ppo(ppo)
+
+
+def estimators(lib, ppo, args, rollout, update):
+    """monitor on (+inf), k3 against the closed-form estimator, alternating; then one profiled update of each"""
+    names = {0: "k3", 1: "exact"}
+    lib.ppo_set_target_kl(ppo, float("inf"))
+    ms = {0: [], 1: []}
+    last = {}
+    for _ in range(args.rounds):
+        for est in (0, 1):
+            assert lib.ppo_set_kl_estimator(ppo, est) == 0
+            rollout()
+            update()                                      # settle into the mode (the store is allocated here)
+            lib.ppo_synchronize()
+            total = 0.0
+            for _ in range(args.updates):
+                rollout()
+                lib.ppo_reset_stats(ppo)
+                t0 = time.perf_counter()
+                update()
+                lib.ppo_synchronize()
+                total += time.perf_counter() - t0
+            ms[est].append(1e3 * total / args.updates)
+            st = (C.c_double * 34)()
+            lib.ppo_read_stats(ppo, st, 34)
+            last[est] = (st[13], st[33])
+    med = {}
+    for est in (0, 1):
+        xs = sorted(ms[est])
+        med[est] = xs[len(xs) // 2]
+        print(f"monitor on, estimator {names[est]:5s}: {med[est]:.2f} ms per update (median of {len(xs)}; "
+              + ", ".join(f"{x:.2f}" for x in ms[est]) + f"); last step: deciding KL {last[est][0]:.4e}"
+              + (f", k3 beside it {last[est][1]:.4e}" if est else ""))
+    print(f"exact − k3: {med[1] - med[0]:+.2f} ms per update ({100 * (med[1] / med[0] - 1):+.2f} %)")
+    os.environ["PPO_SERIAL"] = "1"
+    prof = {}
+    for est in (0, 1):
+        lib.ppo_set_kl_estimator(ppo, est)
+        rollout()
+        lib.ppo_prof_enable(1)
+        lib.ppo_prof_reset()
+        update()
+        t_ms, work, launches = (C.c_double * 7)(), (C.c_double * 7)(), (C.c_long * 7)()
+        lib.ppo_prof_read(t_ms, work, launches)
+        lib.ppo_prof_enable(0)
+        prof[est] = (list(t_ms), list(launches))
+    del os.environ["PPO_SERIAL"]
+    for est in (0, 1):
+        t, n = prof[est]
+        print(f"profiled (serial), estimator {names[est]:5s}: all classes {sum(n)} launches, {sum(t):.2f} ms; "
+              f"PPO_K_ADAM (Adam + KL) {n[K_ADAM]} launches, {t[K_ADAM]:.3f} ms")
+    dn = [a - b for a, b in zip(prof[1][1], prof[0][1])]
+    dt = [a - b for a, b in zip(prof[1][0], prof[0][0])]
+    print("exact − k3 by class (launches, ms): " + ", ".join(f"[{k}] {dn[k]:+d}, {dt[k]:+.3f}" for k in range(7)))
 
 
 if __name__ == "__main__":
