@@ -875,6 +875,58 @@ int ppo_env_step_device(int env_kind, float* d_env_state, const float* d_action,
                         float* d_reward, unsigned char* d_term, unsigned char* d_trunc, int E, int S, int A,
                         int categorical, unsigned long long seed, unsigned long long step);
 
+/* ---------------- the state-dependent-σ Gaussian policy (csrc/gauss_sd.hip) ----------------
+ * A diagonal Gaussian whose standard deviation is an output of the policy network (RLlib's free_log_std = False,
+ * Brax's PPO, rl_games' fixed_sigma: False).  A = action_size, the width of μ's output and of a stored action row,
+ * does not change; A must be even and Aa = A / 2 <= 32 is the action dimension.  Columns 0 … Aa−1 of a row z of μ's
+ * output are the mean, columns Aa … A−1 the raw log σ.  It is action distribution 3, behind its own setter, as the
+ * multi-discrete policy is 2.  Per row, fp32, j ascending (csrc/ppo_math.h, the sd_* atoms over the Gaussian ones):
+ *     ls_j  = t < ls_min ? ls_min : (t > ls_max ? ls_max : t),   t = z_{Aa+j}      (NaN propagates)
+ *     in_j  = !(t < ls_min) && !(t > ls_max)                                        (NaN counts as inside)
+ *     lp    = log_prob_start(Aa), then lp = log_prob_sub(lp, log_prob_term(ls_j, (a_j − μ_j)/expf(ls_j)))
+ *             — the Gaussian atoms, so a row whose ls equals a fixed log σ vector gets the Gaussian head's bits
+ *     H     = the Gaussian entropy expression over this row's ls (the constant for Aa, then += ls_j ascending)
+ *     g     = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)
+ *     ∂loss/∂z_j      = the Gaussian head's grad_μ expression with this row's ls_j                 j < Aa
+ *     ∂loss/∂z_{Aa+j} = in_j ? (the Gaussian head's per-row ∂/∂log σ term with this row's ls_j) − ent_coeff/m : +0
+ *     loss  = −Σ_rows surrogate/m − ent_coeff·(Σ_rows H)/m
+ * A clamped column's gradient is +0, written.  A stored action row stays A floats: columns 0 … Aa−1 hold the action,
+ * columns Aa … A−1 are +0; the stored log-prob is lp.  Sampling: a_j = μ_j + normal_at(e·Aa + j, kNoise + step, key)
+ * ·expf(ls_j), key and offset those of the Gaussian sampler at each call site; the deterministic action is the mean
+ * half with zeros after it.  Under PPO_KL_EXACT the row KL is the Gaussian closed form over the clamped halves of the
+ * old and the new row.  The recommended bounds are (−20, 2), RLlib's and the SAC implementations'; there is no default.
+ *
+ * While it is on a policy step is forward → this head → backward in the multi-launch loop (no fused head, wide pass,
+ * single-workgroup or cluster phase, no graph replay); the log σ vector gets no gradient and stays bit-identical.
+ * ppo_rollout_device, ppo_rollout_act, ppo_act_device, ppo_eval_device and ppo_fill_synthetic sample through it;
+ * Pendulum is accepted with A == 2, the synthetic environment reads column j mod Aa, CartPole declines;
+ * ppo_env_step_device is not extended.  train_ppo_epoch and eval_ppo end the process with a message.
+ * ppo_read_stats: out[4] is the mean row entropy of the last policy step's minibatch, out[34] its clamped log-σ
+ * elements and out[35] its elements m·Aa (exact integers, THIS RANK's rows under data parallelism; 0 while off).
+ * ppo_save_state keeps the setting and the bounds in a section written only while the distribution is 3; save_ppo
+ * keeps nothing.
+ * Out of scope: Aa > 32, bf16 compute mode, a tanh squash of the action, an additive log-σ offset, and the fused,
+ * cluster and graph paths.
+ *
+ * The setter returns 0, or −1 with the setting unchanged: NULL ppo, A odd, Aa > 32, NaN, ls_min >= ls_max, either
+ * outside [−20, 20], or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).  While it is on
+ * ppo_get_action_dist returns 3; ppo_set_action_dist(ppo, 0 | 1) switches away, ppo_set_action_dist(ppo, 3) returns −1
+ * and ppo_set_action_mask returns −1.  The getter returns 1 while on (out2 = {ls_min, ls_max}, may be NULL), else 0. */
+int ppo_set_action_gaussian_sd(void* ppo, float ls_min, float ls_max);
+int ppo_get_action_gaussian_sd(void* ppo, float* out2);
+/* test entries: the head, the sampler and the closed-form KL launch on caller-supplied device arrays.  Each
+ * synchronises; each returns −1 with nothing launched and nothing recorded for ppo_last_error on bad arguments.
+ * Head: d_grad [m, A], d_lp / d_ent [m], *loss the launch's loss, clamped2 = {clamped log-σ elements, m·Aa}.
+ * Sampler: counter e·Aa + j at `offset` under `key`.  KL: row i of d_new against row d_rows[i] (NULL: i) of d_old,
+ * d_row_kl (may be NULL) [m] ← every row's KL, *out_mean their mean. */
+int ppo_gauss_sd_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp,
+                             int m, int A, float ls_min, float ls_max, float eps, float ent_coeff,
+                             float* d_grad, float* d_lp, float* d_ent, double* loss, long long* clamped2);
+int ppo_gauss_sd_sample_device(const float* d_z, int m, int A, float ls_min, float ls_max, unsigned long long key,
+                               unsigned long long offset, float* d_action, float* d_log_prob);
+int ppo_gauss_sd_kl_exact_device(const float* d_new, const float* d_old, const int* d_rows, int m, int A,
+                                 float ls_min, float ls_max, double* d_row_kl, double* out_mean);
+
 /* layer 0's input of the last device forward of a NeuralNetwork*, m rows × input_size fp32, to the
  * host: the gathered minibatch rows the GEMMs read (NeuralNetwork.d_x0) — for parity tests;
  * synchronises.  bf16 copies (x0_dtype 1) are not converted: returns −1 for them and for m beyond the

@@ -152,14 +152,15 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
                                                      float eps, float target_kl, double rows_global, int decide_here,
                                                      PhipKlRec* rec, const int* __restrict__ md_off, int D,
                                                      const uint32_t* __restrict__ mask, const int* __restrict__ rows,
-                                                     PhipKlExact ex) {
+                                                     PhipKlExact ex, float sd_lo, float sd_hi) {
     __shared__ double s[TPB + 1];             // s[TPB]: "this workgroup drew the last ticket"
     double kl = 0.0, cnt = 0.0, klx = 0.0;
     const int W = (A + 31) / 32;
     for (long base = blockIdx.x * (long)TPB; base < m; base += (long)gridDim.x * TPB) {
         const long i = base + threadIdx.x;
         if (i < m && (!EXACT || old_lp)) {
-            const float lp = mask      ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A,
+            const float lp = dist == 3 ? ppo::sd_row(mu + i * A, action + i * A, A >> 1, sd_lo, sd_hi).lp
+                             : mask    ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A,
                                                               ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
                              : dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A, ppo::NoMask{})
                              : dist  ? ppo::cat_log_prob_row(mu + i * A, A, ppo::cat_index(action[i * A], A))
@@ -173,7 +174,8 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
                 if (i < m) {
                     const float* zo = ex.old_dist + (ex.rows ? (long)ex.rows[i] : i) * A;
                     const float* act = mask ? action + i * A : nullptr;
-                    const double r = !ex.off ? ppo::kl_gauss_row(zo, ex.old_log_std, mu + i * A, log_std, A)
+                    const double r = dist == 3 ? ppo::sd_kl_row(zo, mu + i * A, A >> 1, sd_lo, sd_hi)
+                                     : !ex.off ? ppo::kl_gauss_row(zo, ex.old_log_std, mu + i * A, log_std, A)
                                      : mask  ? ppo::kl_cat_row(zo, mu + i * A, ex.off, ex.D, act,
                                                                ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
                                              : ppo::kl_cat_row(zo, mu + i * A, ex.off, ex.D, act, ppo::NoMask{});
@@ -253,23 +255,28 @@ extern "C" {
 
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
-                    const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex) {
+                    const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex,
+                    const float* sd) {
     static_assert(PHIP_KL_PARTS <= TPB, "the last workgroup folds one pair of partials per thread");
     PPO_REQUIRE(m > 0 && A > 0 && rows_global > 0 && rec, "phip_policy_kl: shape");
     PPO_REQUIRE(dist != 2 || (md_off && D >= 1 && 2 * D <= A), "phip_policy_kl: multi-discrete offsets");
     PPO_REQUIRE(!mask || dist == 2, "phip_policy_kl: a mask needs the multi-discrete form (dist 1 as nvec = {A})");
     PPO_REQUIRE(ex || old_lp, "phip_policy_kl: the k3 launch needs the old log-probs");
-    PPO_REQUIRE(!ex || (ex->old_dist && (ex->off ? ex->D >= 1 && dist != 0 : dist == 0 && ex->old_log_std && !ex->wide)),
+    PPO_REQUIRE(dist != 3 || (sd && !mask && (A & 1) == 0 && A / 2 <= PHIP_SD_MAX_AA),
+                "phip_policy_kl: the state-dependent-σ form needs its bounds and an even A <= 64");
+    PPO_REQUIRE(!ex || (ex->old_dist && (ex->off ? ex->D >= 1 && dist != 0 && dist != 3
+                                                 : (dist == 3 || (dist == 0 && ex->old_log_std)) && !ex->wide)),
                 "phip_policy_kl: the closed-form estimator's inputs");
+    const float sd_lo = dist == 3 ? sd[0] : 0.f, sd_hi = dist == 3 ? sd[1] : 0.f;
     ppo::ProfScope ps(PPO_K_ADAM, (ex ? 12.0 : 8.0) * (double)m * A + 4.0 * m);
     if (ex)
         hipLaunchKernelGGL(kl_sum_kernel<true>, dim3(grid_for(m)), dim3(TPB), 0, ppo::stream(), mu, log_std, action,
                            old_lp, m, A, dist, eps, target_kl, (double)rows_global, decide_here, rec, md_off, D, mask,
-                           rows, *ex);
+                           rows, *ex, sd_lo, sd_hi);
     else
         hipLaunchKernelGGL(kl_sum_kernel<false>, dim3(grid_for(m)), dim3(TPB), 0, ppo::stream(), mu, log_std, action,
                            old_lp, m, A, dist, eps, target_kl, (double)rows_global, decide_here, rec, md_off, D, mask,
-                           rows, PhipKlExact{});
+                           rows, PhipKlExact{}, sd_lo, sd_hi);
     PPO_LAUNCH_CHECK();
 }
 

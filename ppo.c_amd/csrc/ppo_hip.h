@@ -149,16 +149,19 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
                       int A, uint64_t seed, uint64_t step);
 /* cont (may be NULL) [E], written at t = T − 1: 1 when the environment was not reset after that step — the next
  * rollout's first observation continues the episode — 0 otherwise.  t addresses the row and ends the segment;
- * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h) */
+ * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h).
+ * Au (phip_env_step, phip_env_step_eval): the action columns in use — A, or A / 2 under the state-dependent-σ
+ * Gaussian, whose rows hold zeros after them: kind 0 then takes A = 2 and reads column 0, kind 1 reads column
+ * j mod Au and averages the action term over Au columns */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat, const int* md_off, int D);
+                   uint64_t seed, int cat, const int* md_off, int D, int Au);
 /* the evaluation's step (ppo_eval_device): the same dynamics (shared __device__ functions) over compact arrays —
  * obs [E, S] is the current observation, read and replaced in place, action [E, A]; reward / term / trunc are
  * written at row e·T + t and cont as phip_env_step writes them; nothing else is kept */
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat, const int* md_off, int D);
+                        uint64_t seed, int cat, const int* md_off, int D, int Au);
 /* the dense step (ppo_env_step_device): the same dynamics again over [E, ·] arrays the caller owns — action in;
  * the transition's next observation, the observation the next step starts from (the reset one where the episode
  * ended), reward, terminated and the environment's own TimeLimit out.  No segment end, no cont */
@@ -327,6 +330,38 @@ void phip_disc_argmax(const float* logits, const uint32_t* mask, const int* d_of
                       int D);
 /* mask[rows[e]·W + j] ← all ones for e < E: the rows a step laid with the unmasked sampler */
 void phip_mask_fill_rows(uint32_t* mask, const int* rows, int E, int A);
+
+/* ---------------- state-dependent-σ Gaussian policy: head and sampler (gauss_sd.hip) ---------------- */
+#define PHIP_SD_MAX_AA 32
+#define PHIP_SD_PARTS 1024
+/* the head's record: zero-initialised (phip_malloc); the caller clears everything ahead of `ticket` before a launch,
+ * the kernel leaves the ticket at zero again */
+typedef struct {
+    double loss;                    /* −Σ surrogate/m − ent_coeff·Σ H/m of the last launch */
+    double ent_sum;                 /* Σ of its row entropies */
+    unsigned long long counts[2];   /* [0] clamped log-σ elements, [1] elements m·Aa of the last launch */
+    unsigned ticket;
+    unsigned pad;
+    double partial[2 * PHIP_SD_PARTS];
+} PhipSdRec;
+int phip_sd_shape_ok(int A);        /* A even, 1 <= A / 2 <= PHIP_SD_MAX_AA */
+/* the clipped-surrogate head over z [m, A]: columns 0 … Aa−1 the mean, Aa … A−1 the raw log σ, clamped to
+ * [ls_min, ls_max] on read (ppo_math.h sd_*); the action in columns 0 … Aa−1 of action [m, A].  grad [m, A] =
+ * ∂loss/∂z written (a clamped log-σ column: +0), lp_out / ent_out (may be NULL) [m] = the row's log-prob / entropy.
+ * rec: loss, Σ H and the two counters of this launch; d_loss_accum (may be NULL) += (float)loss by one thread.
+ * One launch, deterministic: no floating-point atomics, grid a function of m, no host read. */
+void phip_sd_head(const float* z, const float* action, const float* adv, const float* old_lp, int m, int A,
+                  float ls_min, float ls_max, float epsilon, float ent_coeff, float* grad, float* lp_out,
+                  float* ent_out, PhipSdRec* rec, float* d_loss_accum);
+/* a_j = μ_j + normal_at(e·Aa + j, offset, key)·expf(ls_j) for row e of z; the action row (zeros in columns Aa … A−1)
+ * and the log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
+void phip_sd_sample(const float* z, const int* rows, float* action, float* logprob, int m, int A, float ls_min,
+                    float ls_max, uint64_t key, uint64_t offset);
+/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
+void phip_sd_sample_rows(const float* z, const int* rows, float* action, float* logprob, int E, int A, float ls_min,
+                         float ls_max, uint64_t key, uint64_t step);
+/* the deterministic action: action [m, A] ← the mean half, zeros after it */
+void phip_sd_mean(const float* z, float* action, int m, int A);
 
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
@@ -498,9 +533,13 @@ typedef struct {
  * through the same tree and ticket; the k3 sum and the clipped count keep their bits.  The decision then takes
  * sums[2] and keeps k3 in hist_other / kl_other.  old_lp NULL (with ex only: the test entry): k3 and the count are
  * skipped and left 0, action is read under a mask alone */
+/* dist 3 = the state-dependent-σ Gaussian (gauss_sd.hip): μ holds [mean | raw log σ], sd (host, {ls_min, ls_max};
+ * unread otherwise) the clamp, lp is ppo_math.h's sd_row and, with ex, the row KL is sd_kl_row over old_dist's raw
+ * rows, clamped on read (old_log_std and off are unread); log σ is unread */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
-                    const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex);
+                    const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex,
+                    const float* sd);
 /* kl = sums[0] / rows_global (exact != 0: sums[2] / rows_global, and kl_other = hist_other[step] = the former),
  * clip_frac = sums[1] / rows_global; stop when kl > 1.5 · target_kl (NaN never
  * stops); hist[step] = kl, step += 1, applied += !stopped.  Under data parallelism it runs after the

@@ -298,6 +298,57 @@ __device__ __forceinline__ double kl_cat_row(const float* zo, const float* zn, c
 // (the sum inside a helper compiled to other code than the kernels' own loops)
 __device__ __forceinline__ float entropy_start(int A) { return (float)(A * 0.5 * (1 + log(2 * M_PI))); }
 
+// ---- State-dependent-σ Gaussian (ppo_set_action_gaussian_sd; csrc/gauss_sd.hip; no counterpart in the reference):
+// a row of μ's A outputs z is Aa = A / 2 means followed by Aa raw log σ, clamped to [ls_min, ls_max] on read.  Per
+// row, fp32, j ascending, through the Gaussian atoms above:
+//     ls_j = t < ls_min ? ls_min : (t > ls_max ? ls_max : t),   t = z_{Aa+j}          sd_clamp   (NaN propagates)
+//     in_j = !(t < ls_min) && !(t > ls_max)                                            sd_inside  (NaN counts as inside)
+//     lp   = log_prob_start(Aa), then lp = log_prob_sub(lp, log_prob_term(ls_j, (a_j − μ_j) / expf(ls_j)))   sd_lp_step
+//     H    = entropy_start(Aa), then += ls_j                                           sd_row
+//     g    = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)
+//     ∂loss/∂z_j      = (a_j − μ_j)·expf(−2·ls_j)·g                                    sd_grad_mu (the Gaussian head's)
+//     ∂loss/∂z_{Aa+j} = in_j ? (−1 + (a_j − μ_j)²·expf(−2·ls_j))·g − ent_coeff/m : +0  sd_grad_ls
+//     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+// A row whose ls equals a fixed log σ vector gets log_prob_row's and the Gaussian head's bits.  The closed-form
+// KL(old ‖ new) is kl_gauss_term over the clamped halves of both rows (sd_kl_row).  tests/gauss_sd_ref.py restates it.
+__device__ __forceinline__ float sd_clamp(float t, float lo, float hi) { return t < lo ? lo : (t > hi ? hi : t); }
+__device__ __forceinline__ bool sd_inside(float t, float lo, float hi) { return !(t < lo) && !(t > hi); }
+__device__ __forceinline__ float sd_lp_step(float lp, float a, float mu, float ls) {
+    const float z = (a - mu) / expf(ls);
+    return log_prob_sub(lp, log_prob_term(ls, z));
+}
+struct SdRow { float lp, H; int clamped; };
+// one thread walks one row: z its A = 2·Aa outputs, a its Aa actions
+__device__ __forceinline__ SdRow sd_row(const float* z, const float* a, int Aa, float lo, float hi) {
+    SdRow r;
+    r.lp = log_prob_start(Aa);
+    r.H = entropy_start(Aa);
+    r.clamped = 0;
+    for (int j = 0; j < Aa; ++j) {
+        const float t = z[Aa + j], ls = sd_clamp(t, lo, hi);
+        r.lp = sd_lp_step(r.lp, a[j], z[j], ls);
+        r.H += ls;
+        r.clamped += !sd_inside(t, lo, hi);
+    }
+    return r;
+}
+__device__ __forceinline__ float sd_grad_mu(float a, float mu, float ls, float g) {
+    const float d = a - mu;
+    return d * expf(-2 * ls) * g;
+}
+// t the raw log σ; cm = ent_coeff / m, formed once per launch by the caller
+__device__ __forceinline__ float sd_grad_ls(float a, float mu, float t, float lo, float hi, float g, float cm) {
+    if (!sd_inside(t, lo, hi)) return 0.f;
+    const float d = a - mu;
+    return (-1 + d * d * expf(-2 * t)) * g - cm;
+}
+__device__ __forceinline__ double sd_kl_row(const float* zo, const float* zn, int Aa, float lo, float hi) {
+    double kl = 0.0;
+    for (int j = 0; j < Aa; ++j)
+        kl += kl_gauss_term(zo[j], sd_clamp(zo[Aa + j], lo, hi), zn[j], sd_clamp(zn[Aa + j], lo, hi));
+    return kl;
+}
+
 // ---- Adam on one element (adam.cu:53-74): step = lr/bc1, ε added in double
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
                                           float bc2) {

@@ -36,6 +36,12 @@
 //   action masking (ppo_set_action_mask; discrete.hip): the same sampler under a mask reads the multi-discrete rows
 //   above, word for word (the categorical policy as D = 1) — ppo_rollout_act_masked / ppo_act_device_masked the policy-noise
 //   row, ppo_masked_sample_device(key, offset) the last one; only the CDF it inverts differs
+//   state-dependent-σ Gaussian (ppo_set_action_gaussian_sd; gauss_sd.hip; Aa = A / 2; tests/gauss_sd_ref.py): the
+//   Gaussian rows' key and offset at each call site, the counter over the Aa action columns
+//     ppo_fill_synthetic      action noise   key s0 ^ 5   counter i·Aa + j   offset 0   .x .y   N(0, 1)
+//     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
+//                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e·Aa + j   offset kNoise + g   .x .y   N(0, 1)
+//     ppo_gauss_sd_sample_device(key, offset)             counter i·Aa + j   offset `offset`   .x .y   N(0, 1)
 #pragma once
 
 #include <cmath>

@@ -101,13 +101,14 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
                                      const float* __restrict__ action, float* __restrict__ next_state,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
                                      uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
-                                     uint64_t step, uint64_t seed) {
+                                     uint64_t step, uint64_t seed, int A) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
     float th = es[3 * e], thdot = es[3 * e + 1];
     float steps = es[3 * e + 2];
-    const PendulumStep o = pendulum_advance(th, thdot, steps, action[row], (uint64_t)e, step, seed);
+    // the torque is column 0 of the action row (A = 2: the state-dependent-σ Gaussian's row, a zero after it)
+    const PendulumStep o = pendulum_advance(th, thdot, steps, action[row * A], (uint64_t)e, step, seed);
     next_state[3 * row] = o.next[0];
     next_state[3 * row + 1] = o.next[1];
     next_state[3 * row + 2] = o.next[2];
@@ -129,13 +130,13 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
 __global__ void pendulum_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
                                      uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
-                                     uint64_t step, uint64_t seed) {
+                                     uint64_t step, uint64_t seed, int A) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
     float th = es[3 * e], thdot = es[3 * e + 1];
     float steps = es[3 * e + 2];
-    const PendulumStep o = pendulum_advance(th, thdot, steps, action[e], (uint64_t)e, step, seed);
+    const PendulumStep o = pendulum_advance(th, thdot, steps, action[(long)e * A], (uint64_t)e, step, seed);
     reward[row] = o.reward;
     term[row] = 0;
     trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
@@ -159,6 +160,7 @@ __device__ __forceinline__ float md_centre(const float* __restrict__ ar, const i
     return 2.f * (float)ppo::cat_index(ar[d], n) / (float)(n - 1) - 1.f;
 }
 
+// A: the action columns in use (the state-dependent-σ Gaussian's row holds A / 2 of them and zeros after)
 __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restrict__ ar, long k, int e, int j, int A,
                                                    uint64_t step, uint64_t seed, int cat,
                                                    const int* __restrict__ md_off, int D) {
@@ -196,12 +198,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, A, step, seed, cat, md_off, D);
+    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, Au, step, seed, cat, md_off, D);
     next_state[row * S + j] = s.o2;
     if (j == 0) {
         reward[row] = s.reward;
@@ -217,12 +219,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
 __global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                   float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, A, step, seed, cat, md_off, D);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, Au, step, seed, cat, md_off, D);
     if (j == 0) {
         reward[row] = s.reward;
         term[row] = s.done ? 1 : 0;
@@ -488,13 +490,14 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat, const int* md_off, int D) {
+                   uint64_t seed, int cat, const int* md_off, int D, int Au) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
+    PPO_REQUIRE(Au == A || (!cat && 2 * Au == A), "phip_env_step: the action columns in use");
     PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step: multi-discrete offsets");
     if (kind == 0) {
-        PPO_REQUIRE(S == 3 && A == 1, "phip_env_step: Pendulum-v1 needs S = 3, A = 1");
+        PPO_REQUIRE(S == 3 && Au == 1, "phip_env_step: Pendulum-v1 needs S = 3 and one action column");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
-                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed);
+                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed, A);
     } else if (kind == 2) {
         PPO_REQUIRE(S == 4 && A == 2 && cat, "phip_env_step: CartPole-v1 needs S = 4, A = 2 and categorical actions");
         hipLaunchKernelGGL(cartpole_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
@@ -502,22 +505,23 @@ void phip_env_step(int kind, float* env_state, float* state, const float* action
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
-                           seed, cat, md_off, D);
+                           seed, cat, md_off, D, Au);
     }
     PPO_LAUNCH_CHECK();
 }
 
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat, const int* md_off, int D) {
+                        uint64_t seed, int cat, const int* md_off, int D, int Au) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * S + A + 2));
+    PPO_REQUIRE(Au == A || (!cat && 2 * Au == A), "phip_env_step_eval: the action columns in use");
     PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step_eval: multi-discrete offsets");
     PPO_REQUIRE(env_state && obs && action && reward && term && trunc && cont && E > 0 && t >= 0 && t < T,
                 "phip_env_step_eval: operands");
     if (kind == 0) {
-        PPO_REQUIRE(S == 3 && A == 1, "phip_env_step_eval: Pendulum-v1 needs S = 3, A = 1");
+        PPO_REQUIRE(S == 3 && Au == 1, "phip_env_step_eval: Pendulum-v1 needs S = 3 and one action column");
         hipLaunchKernelGGL(pendulum_eval_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state, obs,
-                           action, reward, term, trunc, cont, E, T, t, step, seed);
+                           action, reward, term, trunc, cont, E, T, t, step, seed, A);
     } else if (kind == 2) {
         PPO_REQUIRE(S == 4 && A == 2 && cat,
                     "phip_env_step_eval: CartPole-v1 needs S = 4, A = 2 and categorical actions");
@@ -526,7 +530,7 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
     } else {
         hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat, md_off,
-                           D);
+                           D, Au);
     }
     PPO_LAUNCH_CHECK();
 }

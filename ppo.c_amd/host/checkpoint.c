@@ -95,15 +95,17 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     const int with_adv = d->adv_norm_mode != PPO_ADV_NORM_GLOBAL;
     /* … and a KL estimator other than k3, likewise */
     const int with_klest = d->kl_est != PPO_KL_K3;
+    /* … and the state-dependent-σ Gaussian, likewise: its section exists only while the distribution is 3 */
+    const int with_sd = d->action_dist == 3;
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
     put_u32(img, CKPT_VERSION);
     put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
                      (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u) |
-                     (with_klest ? CKPT_F_KLEST : 0u));
+                     (with_klest ? CKPT_F_KLEST : 0u) | (with_sd ? CKPT_F_GAUSS_SD : 0u));
     put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv +
-                     (uint32_t)with_klest);
+                     (uint32_t)with_klest + (uint32_t)with_sd);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -231,6 +233,16 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_section(img, CKPT_TAG_KLEST, &s);
         free(s.p);
     }
+
+    if (with_sd) {
+        memset(&s, 0, sizeof(s));
+        put_u32(&s, 1);
+        put_u32(&s, 0);
+        put_f32(&s, d->sd_ls[0]);
+        put_f32(&s, d->sd_ls[1]);
+        put_section(img, CKPT_TAG_GAUSS_SD, &s);
+        free(s.p);
+    }
     return 0;
 }
 
@@ -321,6 +333,9 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
         int nvec[CKPT_MD_MAX_D];
         for (int i = 0; i < ix->md_D; i++) nvec[i] = (int)ckpt_rd32(st + 40 + 4 * (size_t)i);
         if (ppo_set_action_multidiscrete(ppo, nvec, ix->md_D) != 0) return "an nvec ppo_set_action_multidiscrete declines";
+    } else if (ix->action_dist == 3) {
+        if (ppo_set_action_gaussian_sd(ppo, ix->sd_ls[0], ix->sd_ls[1]) != 0)
+            return "bounds or an action size ppo_set_action_gaussian_sd declines";
     } else if (ppo_set_action_dist(ppo, ix->action_dist) != 0) {
         return "an action distribution ppo_set_action_dist declines";
     }

@@ -63,6 +63,8 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         return fail(ix, "header flags and the KL-estimator section disagree");
     if (((ix->flags & CKPT_F_ADVNORM) != 0) != (s[CKPT_TAG_ADVNORM].present != 0))
         return fail(ix, "the header's advantage-normalisation flag and its section disagree");
+    if (((ix->flags & CKPT_F_GAUSS_SD) != 0) != (s[CKPT_TAG_GAUSS_SD].present != 0))
+        return fail(ix, "the header's state-dependent-sigma flag and its section disagree");
 
     /* Legacy: five floats, then state size, action size, capacity */
     if (s[CKPT_TAG_LEGACY].len < 32) return fail_tag(ix, "shorter than the legacy header", CKPT_TAG_LEGACY);
@@ -78,13 +80,13 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
     if (s[CKPT_TAG_SETTINGS].len < CKPT_SETTINGS_FIXED) return fail_tag(ix, "too short", CKPT_TAG_SETTINGS);
     const uint8_t* st = img + s[CKPT_TAG_SETTINGS].off;
     const uint32_t dist = ckpt_rd32(st + 32), D = ckpt_rd32(st + 36);
-    if (dist > 2u || D > (uint32_t)CKPT_MD_MAX_D || (D != 0) != (dist == 2u))
+    if (dist > 3u || D > (uint32_t)CKPT_MD_MAX_D || (D != 0) != (dist == 2u))
         return fail_tag(ix, "bad action distribution or component count", CKPT_TAG_SETTINGS);
     if (s[CKPT_TAG_SETTINGS].len != CKPT_SETTINGS_FIXED + 4ull * D)
         return fail_tag(ix, "length contradicts its component count", CKPT_TAG_SETTINGS);
     const uint8_t* tail = st + 40 + 4u * D;
     const uint32_t mask_on = ckpt_rd32(tail);
-    if (!is01(ckpt_rd32(st + 16)) || !is01(ckpt_rd32(st + 24)) || !is01(mask_on) || (mask_on && dist == 0) ||
+    if (!is01(ckpt_rd32(st + 16)) || !is01(ckpt_rd32(st + 24)) || !is01(mask_on) || (mask_on && (dist == 0 || dist == 3)) ||
         !is01(ckpt_rd32(tail + 4)) || !is01(ckpt_rd32(tail + 8)))
         return fail_tag(ix, "a flag or dtype out of range", CKPT_TAG_SETTINGS);
     ix->action_dist = (int)dist;
@@ -178,6 +180,22 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         if (ckpt_rd32(ke) > CKPT_KLEST_MAX) return fail_tag(ix, "unknown KL estimator", CKPT_TAG_KLEST);
         if (ckpt_rd32(ke + 4) != 0) return fail_tag(ix, "reserved word not zero", CKPT_TAG_KLEST);
     }
+
+    /* the state-dependent-σ Gaussian: present exactly while the action distribution is 3, an even A with A / 2 <= 32,
+     * bounds the setter accepts */
+    if ((s[CKPT_TAG_GAUSS_SD].present != 0) != (dist == 3u))
+        return fail(ix, "the action distribution and the state-dependent-sigma section disagree");
+    if (s[CKPT_TAG_GAUSS_SD].present) {
+        if (s[CKPT_TAG_GAUSS_SD].len != CKPT_GAUSS_SD_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_GAUSS_SD);
+        const uint8_t* sd = img + s[CKPT_TAG_GAUSS_SD].off;
+        const float lo = rd_f32(sd + 8), hi = rd_f32(sd + 12);
+        if (ckpt_rd32(sd) != 1 || ckpt_rd32(sd + 4) != 0) return fail_tag(ix, "a word out of range", CKPT_TAG_GAUSS_SD);
+        if ((A & 1u) || A / 2 > CKPT_GAUSS_SD_MAX_AA)
+            return fail_tag(ix, "the action size is odd or wider than 64", CKPT_TAG_GAUSS_SD);
+        if (!(lo < hi) || !(lo >= -20.f) || !(hi <= 20.f)) return fail_tag(ix, "bounds outside [-20, 20]", CKPT_TAG_GAUSS_SD);
+        ix->sd_ls[0] = lo;
+        ix->sd_ls[1] = hi;
+    }
     return 0;
 }
 
@@ -190,7 +208,7 @@ int ckpt_index(const void* buf, size_t len, CkptIndex* ix) {
     ix->flags = ckpt_rd32(img + 12);
     ix->count = ckpt_rd32(img + 16);
     if (ix->version != CKPT_VERSION) return fail(ix, "unsupported version (this reader knows version 1)");
-    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST)) return fail(ix, "unknown header flags");
+    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST | CKPT_F_GAUSS_SD)) return fail(ix, "unknown header flags");
     if (ix->count > (len - CKPT_HEADER_BYTES) / CKPT_SECTION_BYTES)
         return fail(ix, "more sections than the file could hold");
     size_t pos = CKPT_HEADER_BYTES;

@@ -140,6 +140,7 @@ static void free_dev_ws(PPO* ppo) {
     phip_free(d->mask);
     phip_free(d->adv_stats);
     phip_free(d->kl_old); phip_free(d->kl_old_ls);
+    phip_free(d->sd_rec);
     free(d->h_tab);
     free(d);
     ppo->dev = NULL;
@@ -227,6 +228,8 @@ static int obs_on(const PPODev* d) { return d && d->obs_clip > 0.f; }
 /* a discrete policy: categorical (1) or multi-discrete (2) — μ's outputs are logits, log σ is unread */
 static int cat_on(const PPODev* d) { return d && (d->action_dist == 1 || d->action_dist == 2); }
 static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
+/* the state-dependent-σ Gaussian (3): μ's outputs are [mean | raw log σ], the log σ vector is unread */
+static int sd_on(const PPODev* d) { return d && d->action_dist == 3; }
 /* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
 static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
 
@@ -601,6 +604,8 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
     if (d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return -1;
     /* … and their policy heads are Gaussian: a categorical policy takes that loop too */
     if (cat_on(d)) return -1;
+    /* … as does the state-dependent-σ Gaussian, whose head reads half of μ's outputs as log σ */
+    if (sd_on(d)) return -1;
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -805,9 +810,10 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     }
     /* μ grads + (top bucket) the log σ gradient behind them */
     const int cat = !tab && cat_on(d);
+    const int sd = !tab && sd_on(d);
     /* the KL monitor under masking: the masked joint lp, the categorical policy as nvec = {A} */
     const int kl_mask = cat && mask_on(d);
-    const int kl_dist = kl_mask ? 2 : cat ? d->action_dist : 0;
+    const int kl_dist = kl_mask ? 2 : cat || sd ? d->action_dist : 0;
     const int* kl_off = kl_mask ? disc_off(d) : md_off(d);
     const int kl_D = kl_mask ? disc_D(d) : d->md_D;
     const uint32_t* kl_m = kl_mask ? d->mask : NULL;
@@ -832,6 +838,19 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
             phip_disc_head(mu->d_output, act, adv, olp, masked ? d->mask : NULL, masked ? rows : NULL, B, A,
                            disc_off(d), disc_D(d), disc_max_n(d, A), ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
                            d->stats + 1, d->cat_ent);
+        nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
+    } else if (sd) {       /* the state-dependent-σ Gaussian: the plain branch with its own head (gauss_sd.hip) */
+        /* log σ is unused, as under a discrete policy: the head writes no gradient to it and the entropy Adam below
+         * steps on the zeros kept here, which leaves log σ bit-identical */
+        if (mu->dtype != 0)
+            die("ppo_update: the state-dependent-σ Gaussian policy needs fp32 compute mode (μ is in bf16 mode)");
+        if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
+        *ls_zero = 1;
+        phip_memset(d->sd_rec, 0, offsetof(PhipSdRec, ticket));
+        d->sd_rows = B;
+        nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
+        phip_sd_head(mu->d_output, act, adv, olp, B, A, d->sd_ls[0], d->sd_ls[1], ppo->epsilon, ppo->ent_coeff, d->gmu,
+                     NULL, NULL, d->sd_rec, d->stats + 1);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
     } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
@@ -866,7 +885,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
                                cat && disc_max_n(d, A) > 32, NULL};
     if (kl_on && c->comm) {
         phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL);
+                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, d->sd_ls);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -890,7 +909,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (c->comm) phip_kl_decide(d->kl, target_kl, kl_rows, kl_x);
         else
             phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL);
+                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, d->sd_ls);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -961,7 +980,7 @@ static int step_graphs_ok(const StepCtx* c) {
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
     if (kl_target(c->d) > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
-    if (cat_on(c->d)) return 0;                   /* … and a captured policy step's head is the Gaussian one */
+    if (cat_on(c->d) || sd_on(c->d)) return 0;    /* … and a captured policy step's head is the Gaussian one */
     if (c->d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return 0;   /* … and a captured policy step gathers for itself */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
@@ -1232,9 +1251,10 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const char* serial_env = getenv("PPO_SERIAL");
     const int concurrent = nv > 0 && np > 0 && !(serial_env && *serial_env && *serial_env != '0');
     /* the fused and the wide output-layer kernels embed the Gaussian head: a categorical policy takes neither */
-    const int fuse_p = !cat_on(d) && nn_out_head_ok(mu, 1);
+    const int own_head = cat_on(d) || sd_on(d);
+    const int fuse_p = !own_head && nn_out_head_ok(mu, 1);
     StepCtx c = {ppo, d, B, S, A, limit, num_batches, comm, nn_out_head_ok(V, 0), fuse_p,
-                 !fuse_p && !cat_on(d) && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
+                 !fuse_p && !own_head && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
                  NULL, NULL, NULL, NULL, 16, 1, 1, 0, state};
     {
         const char* ge = getenv("PPO_GRAPH_STEPS");
@@ -1369,8 +1389,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     float s[4] = {0, 0, 0, 0}, a[2] = {0, 0};
     phip_d2h(s, d->stats, sizeof(s));
     if (g_adv_stats) phip_d2h(a, g_adv_stats, sizeof(a));
-    double v[34] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
-                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[36] = {s[0], (double)d->n_v, s[1], (double)d->n_p, compute_entropy_cuda(ppo->policy), a[0], a[1],
+                    (double)g_gae_own_rows, (double)d->n_graph, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (n > 9 && d->max_grad_norm > 0.f) {      /* gradient clipping: zeros while it is off */
         for (int i = 0; i < 2; i++) {
             PhipClipRec r;
@@ -1449,7 +1469,15 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[33] = o;
         }
     }
-    for (int i = 0; i < n && i < 34; i++) out[i] = v[i];
+    if (sd_on(d) && d->sd_rec) {   /* the state-dependent-σ Gaussian: the last policy step's mean row entropy and its
+                                    * clamped log-σ elements and elements (this rank's rows); zeros while it is off */
+        PhipSdRec r;
+        phip_d2h(&r, d->sd_rec, offsetof(PhipSdRec, ticket));
+        v[4] = d->sd_rows > 0 ? r.ent_sum / d->sd_rows : 0.0;
+        v[34] = (double)r.counts[0];
+        v[35] = (double)r.counts[1];
+    }
+    for (int i = 0; i < n && i < 36; i++) out[i] = v[i];
 }
 
 /* ppo_ext.h: running return-based reward normalisation */
@@ -1599,9 +1627,11 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
     if (env_kind < 0 || env_kind > 2) return -1;
     const int E = n_envs, T = horizon;
     const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
-    if (env_kind == 0 && (S != 3 || A != 1)) return -1;
+    /* the action columns the environment reads, from the PPODev if there is one: a declined call creates nothing */
+    const int Au = sd_on((const PPODev*)ppo->dev) ? A / 2 : A;
+    if (env_kind == 0 && (S != 3 || Au != 1)) return -1;
     PPODev* d = dev_ws(ppo, 1);
-    const int cat = cat_on(d);
+    const int cat = cat_on(d), sd = sd_on(d);
     if (env_kind == 2 && (S != 4 || A != 2 || !cat)) return -1;
     eval_ws(d, E, (long)E * T, S, A);
     /* the first reset and the key of every later draw, as ppo_rollout_device derives them; the step counter is
@@ -1624,10 +1654,14 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         else if (cat)
             phip_disc_sample_rows(pol->mu->d_output, NULL, d->ev_rows, disc_off(d), d->ev_act, d->ev_lp, NULL, E, A,
                                   disc_D(d), key, step);
+        else if (sd && deterministic) phip_sd_mean(pol->mu->d_output, d->ev_act, E, A);
+        else if (sd)
+            phip_sd_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, d->sd_ls[0], d->sd_ls[1], key,
+                                step);
         else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
-                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D);
+                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D, Au);
     }
     phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
                       d->ev_agg, NULL);
@@ -1962,7 +1996,8 @@ int ppo_policy_kl_device(const float* d_mu, const float* d_log_std, const float*
     if (!d_mu || !d_log_std || !d_action || !d_old_lp || !out2 || m <= 0 || A <= 0) return -1;
     if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
     phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
-    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, NULL);
+    phip_policy_kl(d_mu, d_log_std, d_action, d_old_lp, m, A, 0, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, NULL,
+                   NULL);
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
     out2[0] = (double)sums[0] / m;
@@ -2123,6 +2158,77 @@ int ppo_get_action_nvec(void* vppo, int* out, int cap) {
     return d->md_D;
 }
 
+/* ppo_ext.h: the state-dependent-σ Gaussian */
+static int sd_bounds_ok(float lo, float hi) {
+    return !isnan(lo) && !isnan(hi) && lo < hi && lo >= -20.f && lo <= 20.f && hi >= -20.f && hi <= 20.f;
+}
+
+int ppo_set_action_gaussian_sd(void* vppo, float ls_min, float ls_max) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !sd_bounds_ok(ls_min, ls_max) || !phip_sd_shape_ok(ppo->buffer->action_size)) return -1;
+    if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;           /* bf16 compute mode */
+    PPODev* d = dev_ws(ppo, 1);
+    if (!d->sd_rec) d->sd_rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    d->sd_ls[0] = ls_min;
+    d->sd_ls[1] = ls_max;
+    d->action_dist = 3;
+    if (d->mask_on) mask_store(ppo, d, 0);           /* masking belongs to a discrete policy: off with it */
+    return 0;
+}
+
+int ppo_get_action_gaussian_sd(void* vppo, float* out2) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    if (!sd_on(d)) return 0;
+    if (out2) { out2[0] = d->sd_ls[0]; out2[1] = d->sd_ls[1]; }
+    return 1;
+}
+
+/* the head, the sampler and the closed-form KL launch on caller-supplied device arrays (test entries: bad arguments
+ * return −1 ahead of any device call, so nothing is recorded for ppo_last_error) */
+int ppo_gauss_sd_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp,
+                             int m, int A, float ls_min, float ls_max, float eps, float ent_coeff, float* d_grad,
+                             float* d_lp, float* d_ent, double* loss, long long* clamped2) {
+    static PhipSdRec* rec = NULL;
+    if (!d_z || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || !clamped2 || m <= 0 ||
+        !phip_sd_shape_ok(A) || !sd_bounds_ok(ls_min, ls_max) || isnan(eps))
+        return -1;
+    if (!rec) rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    phip_memset(rec, 0, offsetof(PhipSdRec, ticket));
+    phip_sd_head(d_z, d_action, d_adv, d_old_lp, m, A, ls_min, ls_max, eps, ent_coeff, d_grad, d_lp, d_ent, rec, NULL);
+    phip_sync();
+    PhipSdRec r;
+    phip_d2h(&r, rec, offsetof(PhipSdRec, ticket));
+    *loss = r.loss;
+    clamped2[0] = (long long)r.counts[0];
+    clamped2[1] = (long long)r.counts[1];
+    return 0;
+}
+
+int ppo_gauss_sd_sample_device(const float* d_z, int m, int A, float ls_min, float ls_max, unsigned long long key,
+                               unsigned long long offset, float* d_action, float* d_log_prob) {
+    if (!d_z || !d_action || !d_log_prob || m <= 0 || !phip_sd_shape_ok(A) || !sd_bounds_ok(ls_min, ls_max)) return -1;
+    phip_sd_sample(d_z, NULL, d_action, d_log_prob, m, A, ls_min, ls_max, key, offset);
+    phip_sync();
+    return 0;
+}
+
+int ppo_gauss_sd_kl_exact_device(const float* d_new, const float* d_old, const int* d_rows, int m, int A, float ls_min,
+                                 float ls_max, double* d_row_kl, double* out_mean) {
+    static PhipKlRec* rec = NULL;
+    if (!d_new || !d_old || !out_mean || m <= 0 || !phip_sd_shape_ok(A) || !sd_bounds_ok(ls_min, ls_max)) return -1;
+    if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+    phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
+    const PhipKlExact ex = {d_old, NULL, d_rows, NULL, 0, 0, d_row_kl};
+    const float sd[2] = {ls_min, ls_max};
+    phip_policy_kl(d_new, NULL, NULL, NULL, m, A, 3, 0.f, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, &ex, sd);
+    phip_sync();
+    float sums[4];
+    phip_d2h(sums, rec->sums, sizeof(sums));
+    *out_mean = (double)sums[2] / m;
+    return 0;
+}
+
 /* the discrete head and sampler on caller-supplied device arrays (the test entries below: bad arguments return −1
  * ahead of any device call, so nothing is recorded for ppo_last_error); nvec is a host array, its offsets go to a
  * device array kept here */
@@ -2258,7 +2364,7 @@ int ppo_policy_kl_exact_device(int dist, const float* d_new, const float* d_log_
     const PhipKlExact ex = {d_old, d_log_std_old, d_rows, d_off, Dc, max_n > 32, d_row_kl};
     /* a mask takes the multi-discrete form of the launch, the categorical policy as nvec = {A} */
     phip_policy_kl(d_new, d_log_std_new, d_action, NULL, m, A, dist == 0 ? 0 : 2, 0.f, INFINITY, m, 1, rec, d_off, Dc,
-                   d_mask, d_mask ? d_rows : NULL, &ex);
+                   d_mask, d_mask ? d_rows : NULL, &ex, NULL);
     phip_sync();
     float sums[4];
     phip_d2h(sums, rec->sums, sizeof(sums));
@@ -2318,6 +2424,9 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
 void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, int n_epochs_policy,
                      int n_epochs_value) {
     /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
+    if (sd_on((PPODev*)ppo->dev))
+        die("train_ppo_epoch: the state-dependent-σ Gaussian policy (ppo_set_action_gaussian_sd) is not supported by "
+            "the host rollout; use ppo_rollout_device + ppo_update");
     if (cat_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: a discrete policy (ppo_set_action_dist, ppo_set_action_multidiscrete) is not supported "
             "by the host rollout; use ppo_rollout_device + ppo_update");
@@ -2340,6 +2449,9 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
+    if (sd_on((PPODev*)ppo->dev))
+        die("eval_ppo: the state-dependent-σ Gaussian policy (ppo_set_action_gaussian_sd) is not supported by the host "
+            "rollout; use ppo_eval_device");
     if (cat_on((PPODev*)ppo->dev))
         die("eval_ppo: a discrete policy (ppo_set_action_dist, ppo_set_action_multidiscrete) is not supported by the "
             "host rollout; use ppo_eval_device");
@@ -2445,9 +2557,11 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     if (env_kind < 0 || env_kind > 2)
         die("ppo_rollout_device: env_kind must be 0 (Pendulum-v1), 1 (synthetic) or 2 (CartPole-v1)");
     const int S = b->state_size, A = b->action_size;
-    if (env_kind == 0 && (S != 3 || A != 1)) die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1");
     PPODev* d = dev_ws(ppo, 1);
-    const int cat = cat_on(d);
+    const int cat = cat_on(d), sd = sd_on(d);
+    const int Au = sd ? A / 2 : A;                   /* the action columns the environment reads */
+    if (env_kind == 0 && (S != 3 || Au != 1))
+        die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1 (2 under the state-dependent-σ Gaussian)");
     if (env_kind == 2 && (S != 4 || A != 2 || !cat))
         die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
             "(ppo_set_action_dist, or ppo_set_action_multidiscrete with nvec = {2})");
@@ -2479,10 +2593,13 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         if (cat)
             phip_disc_sample_rows(pol->mu->d_output, NULL, rows, disc_off(d), b->d_action_p, b->d_logprob_p, NULL, E, A,
                                   disc_D(d), key, step);
+        else if (sd)
+            phip_sd_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
+                                key, step);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
-                      cat, md_off(d), d->md_D);
+                      cat, md_off(d), d->md_D, Au);
     }
     ro_finish(ppo, d, E, T);
 }
@@ -2513,6 +2630,11 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
         mask_fill_full(d, N, A);                     /* sampled unmasked: the rows carry full masks */
         phip_disc_sample(ppo->policy->mu->d_output, NULL, NULL, disc_off(d), b->d_action_p, b->d_logprob_p, NULL, (int)N,
                          A, disc_D(d), s0 ^ 0x5, 0);
+    } else if (sd_on((PPODev*)ppo->dev)) {           /* the "action noise" key, counter i·Aa + j */
+        PPODev* d = (PPODev*)ppo->dev;
+        nn_forward_dev(ppo->policy->mu, obs, (int)N);
+        phip_sd_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, d->sd_ls[0],
+                       d->sd_ls[1], s0 ^ 0x5, 0);
     } else {
         ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     }
@@ -2576,6 +2698,9 @@ static long long rollout_act(PPO* ppo, const uint32_t* d_mask, float* d_action) 
     if (cat_on(d))         /* under the caller's masks, which go to the step's rows of the store in the same launch */
         phip_disc_sample_rows(pol->mu->d_output, d_mask, rows, disc_off(d), b->d_action_p, b->d_logprob_p,
                               d_mask ? d->mask : NULL, E, A, disc_D(d), d->ext_key, step);
+    else if (sd_on(d))
+        phip_sd_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
+                            d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     if (!d_mask && mask_on(d)) phip_mask_fill_rows(d->mask, rows, E, A);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
@@ -2648,6 +2773,9 @@ static int act_device(PPO* ppo, const float* d_obs, const uint32_t* d_mask, int 
     else if (cat)
         phip_disc_sample_rows(pol->mu->d_output, d_mask, d->act_rows, disc_off(d), d_action, lp, NULL, m, A, disc_D(d),
                               key, step);
+    else if (sd_on(d) && deterministic) phip_sd_mean(pol->mu->d_output, d_action, m, A);
+    else if (sd_on(d))
+        phip_sd_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, d->sd_ls[0], d->sd_ls[1], key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;
@@ -2764,7 +2892,7 @@ int ppo_set_compute_dtype(void* vppo, int dtype) {
     /* bf16 mode knows ReLU and identity: a tanh layer in either network declines it, both left as they were */
     if (dtype == 1 && (nn_has_tanh(ppo->V) || nn_has_tanh(ppo->policy->mu))) return -1;
     /* … and the categorical head reads fp32 logits: bf16 mode is declined while it is on */
-    if (dtype == 1 && cat_on((PPODev*)ppo->dev)) return -1;
+    if (dtype == 1 && (cat_on((PPODev*)ppo->dev) || sd_on((PPODev*)ppo->dev))) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;
     return nn_set_compute_dtype(ppo->policy->mu, dtype);
 }

@@ -176,6 +176,13 @@ typedef struct {
     int kl_est;
     float *kl_old, *kl_old_ls;
     long kl_old_rows;
+    /* the state-dependent-σ Gaussian (ppo_set_action_gaussian_sd; action_dist == 3; csrc/gauss_sd.hip): μ's A outputs
+     * are A / 2 means and A / 2 raw log σ, clamped to sd_ls = {ls_min, ls_max} on read.  sd_rec: the head's device
+     * record — the last policy step's loss, entropy sum and the counters {clamped log-σ elements, elements};
+     * sd_rows: that step's rows.  NULL until the setter first succeeds */
+    float sd_ls[2];
+    PhipSdRec* sd_rec;
+    int sd_rows;
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

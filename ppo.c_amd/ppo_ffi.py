@@ -179,6 +179,14 @@ _SIGS = {
                                                 C.c_float, _P, _P, _P, C.POINTER(C.c_double)]),
     "ppo_multidiscrete_sample_device": (C.c_int, [_P, C.c_int, C.c_int, c_int_p, C.c_int, C.c_ulonglong,
                                                   C.c_ulonglong, _P, _P]),
+    "ppo_set_action_gaussian_sd": (C.c_int, [_P, C.c_float, C.c_float]),
+    "ppo_get_action_gaussian_sd": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ppo_gauss_sd_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                           _P, _P, _P, C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    "ppo_gauss_sd_sample_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                             _P, _P]),
+    "ppo_gauss_sd_kl_exact_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P,
+                                               C.POINTER(C.c_double)]),
     "ppo_set_action_mask": (C.c_int, [_P, C.c_int]),
     "ppo_get_action_mask": (C.c_int, [_P]),
     "ppo_action_mask_words": (C.c_int, [_P]),
