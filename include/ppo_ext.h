@@ -927,6 +927,72 @@ int ppo_gauss_sd_sample_device(const float* d_z, int m, int A, float ls_min, flo
 int ppo_gauss_sd_kl_exact_device(const float* d_new, const float* d_old, const int* d_rows, int m, int A,
                                  float ls_min, float ls_max, double* d_row_kl, double* out_mean);
 
+/* ---------------- the Beta policy for bounded continuous actions (csrc/beta.hip) ----------------
+ * A product of Beta distributions on (0, 1)^Aa (Chou et al. 2017; RLlib's Beta action distribution): the support is
+ * bounded, so no environment has to clip and the gradient carries no bias at the bounds.  A = action_size, the width
+ * of μ's output and of a stored action row, does not change; A must be even and Aa = A / 2 <= 32 is the action
+ * dimension.  It is action distribution 4, behind its own setter.  Columns 0 … Aa−1 of a row z of μ's output are raw
+ * α-logits, columns Aa … A−1 raw β-logits; a stored action row holds x_j ∈ (0, 1) in columns 0 … Aa−1 and +0 after
+ * them.  Per component, in double from the fp32 inputs, cast to fp32 where stored (csrc/ppo_math.h, the beta_* atoms):
+ *     zc    = z clamped to [−z_max, z_max] on read (NaN propagates and counts as inside)
+ *     α     = 1 + softplus(zc_j),  β = 1 + softplus(zc_{Aa+j})      both >= 1: every component is unimodal
+ *     lp_j  = (α−1)·ln x + (β−1)·ln(1−x) + lnΓ(α+β) − lnΓ(α) − lnΓ(β)
+ *     H_j   = lnΓ(α) + lnΓ(β) − lnΓ(α+β) − (α−1)ψ(α) − (β−1)ψ(β) + (α+β−2)ψ(α+β)
+ *     ∂lp/∂α = ln x + ψ(α+β) − ψ(α),  ∂H/∂α = −(α−1)ψ′(α) + (α+β−2)ψ′(α+β),  and symmetric for β with ln(1−x)
+ *     ∂α/∂z  = sigmoid(z) inside the clamp, +0 on a clamped logit — whose gradient is +0, written
+ * Per row: lp = Σ_j lp_j and H = Σ_j H_j, j ascending; one clipped surrogate on the joint ratio gives g = ∂loss/∂lp;
+ *     ∂loss/∂z = g·∂lp/∂z − (ent_coeff/m)·∂H/∂z,    loss = −Σ_rows surrogate/m − ent_coeff·(Σ_rows H)/m
+ * ψ and ψ′ are device functions (an upward recurrence to x >= 6, then the asymptotic series; the truncation terms are
+ * written beside them), lnΓ is the device library's.  Under PPO_KL_EXACT the row KL(old ‖ new) is the sum over
+ * components of lnB(α′,β′) − lnB(α,β) + (α−α′)ψ(α) + (β−β′)ψ(β) + (α′−α+β′−β)ψ(α+β), unprimed = old, over the clamped
+ * old and new rows.  z_max = 15 is the recommended value (α, β ∈ [1, 16]: the modes reach within 1/15 of the bounds);
+ * there is no default.
+ *
+ * Sampling: x = Ga/(Ga + Gb), two Gamma variates by Marsaglia–Tsang (shape >= 1, no boost); an attempt takes one
+ * Philox block at counter (e·Aa + j) | (2·attempt + sel) << 56 — a Box–Muller normal from .x .y, the acceptance
+ * uniform from .z; sel 0 is the α variate, 1 the β variate — key and offset those of the Gaussian sampler at each call
+ * site, so a draw is a pure function of (key, step, row, component).  Attempts are capped at 16: acceptance is >= 0.95
+ * per attempt for shape >= 1, so the cap is reached with probability <= 0.05¹⁶, and then the variate is shape − 1/3.
+ * x is clamped to [2⁻²⁴, 1 − 2⁻²⁴] in fp32.  The stored log-prob goes through the head's functions: the first ratio of
+ * an update is exactly 1 wherever the forward gives the same z.  The deterministic action is the mean α/(α+β).
+ *
+ * Action mapping: the built-in environments receive bound·(2x − 1) — Pendulum (accepted with A == 2) ±2, the synthetic
+ * environment (column j mod Aa) ±1; CartPole declines.  Through ppo_rollout_act / ppo_act_device the caller gets x and
+ * maps it itself.  ppo_env_step_device is not extended.
+ *
+ * While it is on a policy step is forward → this head → backward in the multi-launch loop (no fused head, wide pass,
+ * single-workgroup or cluster phase, no graph replay); the log σ vector gets no gradient, the entropy Adam steps on
+ * zeros and leaves it bit-identical.  ppo_rollout_device, ppo_rollout_act / _store, ppo_act_device, ppo_eval_device and
+ * ppo_fill_synthetic sample through it; the KL monitor runs under both estimators; gradient clipping, value clipping,
+ * both normalisers, the learning-rate schedules and data parallelism (no collective added) work as before.
+ * train_ppo_epoch and eval_ppo end the process with a message.  ppo_read_stats: out[4] is the mean row entropy of the
+ * last policy step's minibatch, out[34] its clamped logits and out[35] its logits m·A (exact integers, THIS RANK's
+ * rows under data parallelism).  ppo_save_state keeps the setting and z_max in a section {1, 0, z_max, 0} written only
+ * while the distribution is 4; save_ppo keeps nothing.
+ * Out of scope: Aa > 32, bf16 compute mode, α or β below 1, an affine action map for external environments, and the
+ * fused, cluster and graph paths.
+ *
+ * The setter returns 0, or −1 with the setting unchanged: NULL ppo, A odd, Aa > 32, z_max not finite or not positive,
+ * or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).  While it is on ppo_get_action_dist
+ * returns 4; ppo_set_action_dist(ppo, 0 | 1) switches away, ppo_set_action_dist(ppo, 4) returns −1 and
+ * ppo_set_action_mask returns −1.  The getter returns 1 while on (*out_z_max = z_max, may be NULL), else 0. */
+int ppo_set_action_beta(void* ppo, float z_max);
+int ppo_get_action_beta(void* ppo, float* out_z_max);
+/* test and serving entries: the head, the sampler and the KL monitor's launch on caller-supplied device arrays.
+ * Each synchronises; each returns −1 with nothing launched and nothing recorded for ppo_last_error on bad arguments.
+ * Head: d_grad [m, A], d_lp / d_ent [m], *loss the launch's loss, clamped2 = {clamped logits, m·A}.
+ * Sampler: d_action [m, A] and d_log_prob [m] under `key` at `offset`; deterministic != 0 writes the mean and no
+ * log-prob (d_log_prob may be NULL).  KL: the monitor's launch with both estimators — row i of d_new with the stored
+ * action row i and old log-prob i for k3 and the clip fraction, against row d_rows[i] (NULL: i) of d_old for the closed
+ * form; d_row_kl (may be NULL) [m] ← every row's closed-form KL; out3 = {mean k3, clip fraction, mean closed-form KL}. */
+int ppo_beta_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp, int m,
+                         int A, float z_max, float eps, float ent_coeff, float* d_grad, float* d_lp, float* d_ent,
+                         double* loss, long long* clamped2);
+int ppo_beta_sample_device(const float* d_z, int m, int A, float z_max, unsigned long long key,
+                           unsigned long long offset, int deterministic, float* d_action, float* d_log_prob);
+int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
+                       const float* d_old_lp, int m, int A, float z_max, float eps, double* d_row_kl, double* out3);
+
 /* layer 0's input of the last device forward of a NeuralNetwork*, m rows × input_size fp32, to the
  * host: the gathered minibatch rows the GEMMs read (NeuralNetwork.d_x0) — for parity tests;
  * synchronises.  bf16 copies (x0_dtype 1) are not converted: returns −1 for them and for m beyond the

@@ -30,6 +30,7 @@
 #include "ppo_math.h"
 #include "reduce.h"
 #include "rng.h"
+#include "tile_io.h"
 
 #include <cmath>
 
@@ -39,57 +40,6 @@ using namespace ppo_rng;
 
 constexpr int TPB = 64;                              // one wave: a lane per row of a 64-row tile
 constexpr int STPB = 256;                            // the sampler's workgroup
-
-// n floats from src (16-byte aligned when VEC) into an LDS tile [rows][pitch], columns < keep only; A floats a row
-template <bool VEC>
-__device__ __forceinline__ void tile_load(float* tile, int pitch, const float* __restrict__ src, int n, int A,
-                                          int keep, int tid) {
-    int done = 0;
-    if (VEC) {
-        const int n4 = n >> 2;
-        const float4* s4 = reinterpret_cast<const float4*>(src);
-        for (int q = tid; q < n4; q += TPB) {
-            const float4 v = s4[q];
-            const float c[4] = {v.x, v.y, v.z, v.w};
-            int row = (4 * q) / A, k = 4 * q - row * A;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (k < keep) tile[row * pitch + k] = c[i];
-                if (++k == A) { k = 0; ++row; }
-            }
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + tid; e < n; e += TPB) {
-        const int row = e / A, k = e - row * A;
-        if (k < keep) tile[row * pitch + k] = src[e];
-    }
-}
-
-template <bool VEC>
-__device__ __forceinline__ void tile_store(const float* tile, int pitch, float* __restrict__ dst, int n, int A,
-                                           int tid) {
-    int done = 0;
-    if (VEC) {
-        const int n4 = n >> 2;
-        float4* d4 = reinterpret_cast<float4*>(dst);
-        for (int q = tid; q < n4; q += TPB) {
-            float c[4];
-            int row = (4 * q) / A, k = 4 * q - row * A;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                c[i] = tile[row * pitch + k];
-                if (++k == A) { k = 0; ++row; }
-            }
-            d4[q] = make_float4(c[0], c[1], c[2], c[3]);
-        }
-        done = n4 << 2;
-    }
-    for (int e = done + tid; e < n; e += TPB) {
-        const int row = e / A, k = e - row * A;
-        dst[e] = tile[row * pitch + k];
-    }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(TPB) void sd_head_kernel(const float* __restrict__ z, const float* __restrict__ action,
@@ -112,8 +62,8 @@ __global__ __launch_bounds__(TPB) void sd_head_kernel(const float* __restrict__ 
         const long r0 = (long)t * TPB;
         const int nr = (int)min((long)TPB, (long)m - r0);
         const long base = r0 * A;
-        tile_load<VEC>(tile, pitch, z + base, nr * A, A, A, tid);
-        tile_load<VEC>(at, apitch, action + base, nr * A, A, Aa, tid);
+        ppo::tile_load<TPB, VEC>(tile, pitch, z + base, nr * A, A, A, tid);
+        ppo::tile_load<TPB, VEC>(at, apitch, action + base, nr * A, A, Aa, tid);
         __syncthreads();
         if (tid < nr) {
             float* zr = tile + tid * pitch;
@@ -135,7 +85,7 @@ __global__ __launch_bounds__(TPB) void sd_head_kernel(const float* __restrict__ 
             elems += (unsigned)Aa;
         }
         __syncthreads();
-        tile_store<VEC>(tile, pitch, grad + base, nr * A, A, tid);
+        ppo::tile_store<TPB, VEC>(tile, pitch, grad + base, nr * A, A, tid);
         __syncthreads();                             // the next tile's loads overwrite what the stores read
     }
 #pragma unroll

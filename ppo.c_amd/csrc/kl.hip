@@ -159,7 +159,8 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
     for (long base = blockIdx.x * (long)TPB; base < m; base += (long)gridDim.x * TPB) {
         const long i = base + threadIdx.x;
         if (i < m && (!EXACT || old_lp)) {
-            const float lp = dist == 3 ? ppo::sd_row(mu + i * A, action + i * A, A >> 1, sd_lo, sd_hi).lp
+            const float lp = dist == 4 ? ppo::beta_lp_row(mu + i * A, action + i * A, A >> 1, sd_hi)
+                             : dist == 3 ? ppo::sd_row(mu + i * A, action + i * A, A >> 1, sd_lo, sd_hi).lp
                              : mask    ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A,
                                                               ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
                              : dist == 2 ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A, ppo::NoMask{})
@@ -174,7 +175,8 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
                 if (i < m) {
                     const float* zo = ex.old_dist + (ex.rows ? (long)ex.rows[i] : i) * A;
                     const float* act = mask ? action + i * A : nullptr;
-                    const double r = dist == 3 ? ppo::sd_kl_row(zo, mu + i * A, A >> 1, sd_lo, sd_hi)
+                    const double r = dist == 4 ? ppo::beta_kl_row(zo, mu + i * A, A >> 1, sd_hi)
+                                     : dist == 3 ? ppo::sd_kl_row(zo, mu + i * A, A >> 1, sd_lo, sd_hi)
                                      : !ex.off ? ppo::kl_gauss_row(zo, ex.old_log_std, mu + i * A, log_std, A)
                                      : mask  ? ppo::kl_cat_row(zo, mu + i * A, ex.off, ex.D, act,
                                                                ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
@@ -262,12 +264,13 @@ void phip_policy_kl(const float* mu, const float* log_std, const float* action, 
     PPO_REQUIRE(dist != 2 || (md_off && D >= 1 && 2 * D <= A), "phip_policy_kl: multi-discrete offsets");
     PPO_REQUIRE(!mask || dist == 2, "phip_policy_kl: a mask needs the multi-discrete form (dist 1 as nvec = {A})");
     PPO_REQUIRE(ex || old_lp, "phip_policy_kl: the k3 launch needs the old log-probs");
-    PPO_REQUIRE(dist != 3 || (sd && !mask && (A & 1) == 0 && A / 2 <= PHIP_SD_MAX_AA),
-                "phip_policy_kl: the state-dependent-σ form needs its bounds and an even A <= 64");
-    PPO_REQUIRE(!ex || (ex->old_dist && (ex->off ? ex->D >= 1 && dist != 0 && dist != 3
-                                                 : (dist == 3 || (dist == 0 && ex->old_log_std)) && !ex->wide)),
+    const int own = dist == 3 || dist == 4;      /* [half | half] rows read under the bounds in sd */
+    PPO_REQUIRE(!own || (sd && !mask && (A & 1) == 0 && A / 2 <= PHIP_SD_MAX_AA),
+                "phip_policy_kl: the state-dependent-σ and Beta forms need their bounds and an even A <= 64");
+    PPO_REQUIRE(!ex || (ex->old_dist && (ex->off ? ex->D >= 1 && dist != 0 && !own
+                                                 : (own || (dist == 0 && ex->old_log_std)) && !ex->wide)),
                 "phip_policy_kl: the closed-form estimator's inputs");
-    const float sd_lo = dist == 3 ? sd[0] : 0.f, sd_hi = dist == 3 ? sd[1] : 0.f;
+    const float sd_lo = own ? sd[0] : 0.f, sd_hi = own ? sd[1] : 0.f;
     ppo::ProfScope ps(PPO_K_ADAM, (ex ? 12.0 : 8.0) * (double)m * A + 4.0 * m);
     if (ex)
         hipLaunchKernelGGL(kl_sum_kernel<true>, dim3(grid_for(m)), dim3(TPB), 0, ppo::stream(), mu, log_std, action,

@@ -151,17 +151,18 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
  * rollout's first observation continues the episode — 0 otherwise.  t addresses the row and ends the segment;
  * step, the same global counter phip_sample_rows takes, is the position in the env and reset streams (rng.h).
  * Au (phip_env_step, phip_env_step_eval): the action columns in use — A, or A / 2 under the state-dependent-σ
- * Gaussian, whose rows hold zeros after them: kind 0 then takes A = 2 and reads column 0, kind 1 reads column
- * j mod Au and averages the action term over Au columns */
+ * Gaussian and the Beta policy, whose rows hold zeros after them: kind 0 then takes A = 2 and reads column 0, kind 1
+ * reads column j mod Au and averages the action term over Au columns.  unit != 0 (the Beta policy): a column holds
+ * x ∈ (0, 1) and the environment receives bound·(2x − 1), bound = 2 for kind 0 and 1 for kind 1 */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat, const int* md_off, int D, int Au);
+                   uint64_t seed, int cat, const int* md_off, int D, int Au, int unit);
 /* the evaluation's step (ppo_eval_device): the same dynamics (shared __device__ functions) over compact arrays —
  * obs [E, S] is the current observation, read and replaced in place, action [E, A]; reward / term / trunc are
  * written at row e·T + t and cont as phip_env_step writes them; nothing else is kept */
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat, const int* md_off, int D, int Au);
+                        uint64_t seed, int cat, const int* md_off, int D, int Au, int unit);
 /* the dense step (ppo_env_step_device): the same dynamics again over [E, ·] arrays the caller owns — action in;
  * the transition's next observation, the observation the next step starts from (the reset one where the episode
  * ended), reward, terminated and the environment's own TimeLimit out.  No segment end, no cont */
@@ -363,6 +364,26 @@ void phip_sd_sample_rows(const float* z, const int* rows, float* action, float* 
 /* the deterministic action: action [m, A] ← the mean half, zeros after it */
 void phip_sd_mean(const float* z, float* action, int m, int A);
 
+/* ---------------- Beta policy: head and sampler (beta.hip) ---------------- */
+/* the clipped-surrogate head over z [m, A]: columns 0 … Aa−1 the raw α-logits, Aa … A−1 the raw β-logits, clamped to
+ * [−z_max, z_max] on read (ppo_math.h beta_*); x ∈ (0, 1) in columns 0 … Aa−1 of action [m, A].  grad [m, A] =
+ * ∂loss/∂z written (a clamped logit: +0), lp_out / ent_out (may be NULL) [m] = the row's log-prob / entropy.  rec (the
+ * state-dependent-σ head's record, used the same way): loss, Σ H, counts = {clamped logits, logits m·A} of this launch;
+ * d_loss_accum (may be NULL) += (float)loss by one thread.  Shapes: phip_sd_shape_ok.  One launch, deterministic: no
+ * floating-point atomics, grid a function of m, no host read. */
+void phip_beta_head(const float* z, const float* action, const float* adv, const float* old_lp, int m, int A,
+                    float z_max, float epsilon, float ent_coeff, float* grad, float* lp_out, float* ent_out,
+                    PhipSdRec* rec, float* d_loss_accum);
+/* x_j = Ga / (Ga + Gb) by Marsaglia–Tsang at counter (e·Aa + j) | (2·attempt + sel) << 56, `offset`, `key` for row e of
+ * z; the action row (zeros in columns Aa … A−1) and the log-prob (may be NULL) go to row rows[e] (rows NULL: e) */
+void phip_beta_sample(const float* z, const int* rows, float* action, float* logprob, int m, int A, float z_max,
+                      uint64_t key, uint64_t offset);
+/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
+void phip_beta_sample_rows(const float* z, const int* rows, float* action, float* logprob, int E, int A, float z_max,
+                           uint64_t key, uint64_t step);
+/* the deterministic action: action [m, A] ← the mean α / (α + β), zeros after it */
+void phip_beta_mean(const float* z, float* action, int m, int A, float z_max);
+
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
  * (n, mean, M2) in double for this shard.  Then normalise with the (global)
@@ -535,7 +556,9 @@ typedef struct {
  * skipped and left 0, action is read under a mask alone */
 /* dist 3 = the state-dependent-σ Gaussian (gauss_sd.hip): μ holds [mean | raw log σ], sd (host, {ls_min, ls_max};
  * unread otherwise) the clamp, lp is ppo_math.h's sd_row and, with ex, the row KL is sd_kl_row over old_dist's raw
- * rows, clamped on read (old_log_std and off are unread); log σ is unread */
+ * rows, clamped on read (old_log_std and off are unread); log σ is unread.
+ * dist 4 = the Beta policy (beta.hip): μ holds [α-logits | β-logits], sd = {−z_max, z_max}, lp is beta_lp_row and, with
+ * ex, the row KL is beta_kl_row over old_dist's raw rows, clamped on read */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
                     const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex,

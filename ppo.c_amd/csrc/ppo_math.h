@@ -349,6 +349,102 @@ __device__ __forceinline__ double sd_kl_row(const float* zo, const float* zn, in
     return kl;
 }
 
+// ---- Beta policy (ppo_set_action_beta; csrc/beta.hip; no counterpart in the reference): a row of μ's A outputs z is
+// Aa = A / 2 raw α-logits followed by Aa raw β-logits, clamped to [−z_max, z_max] where it is read; the action row
+// holds x_j ∈ (0, 1) in columns 0 … Aa−1 and +0 after them.  Per component, in double from the fp32 inputs:
+//     zc    = z < −z_max ? −z_max : (z > z_max ? z_max : z)                             beta_clamp   (NaN propagates)
+//     in    = !(z < −z_max) && !(z > z_max)                                             beta_inside  (NaN counts as inside)
+//     α     = 1 + softplus(zc_j),  β = 1 + softplus(zc_{Aa+j}),  softplus(t) = max(t, 0) + log1p(e^{−|t|})   beta_shape
+//     lp_j  = (α−1)·ln x + (β−1)·ln(1−x) + lnΓ(α+β) − lnΓ(α) − lnΓ(β)                   beta_lp
+//     H_j   = lnΓ(α) + lnΓ(β) − lnΓ(α+β) − (α−1)ψ(α) − (β−1)ψ(β) + (α+β−2)ψ(α+β)        beta_component
+//     ∂lp/∂α = ln x + ψ(α+β) − ψ(α)                  ∂lp/∂β = ln(1−x) + ψ(α+β) − ψ(β)
+//     ∂H/∂α  = −(α−1)ψ′(α) + (α+β−2)ψ′(α+β)           ∂H/∂β  = −(β−1)ψ′(β) + (α+β−2)ψ′(α+β)
+//     ∂α/∂z  = in ? 1/(1 + e^{−zc}) : +0                                                beta_dshape
+// Per row: lp = (float)Σ_j lp_j and H = (float)Σ_j H_j, j ascending from 0.0 in double (beta_lp_row; the head sums the
+// same terms in the same order); g = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g);
+//     ∂loss/∂z = g·∂lp/∂z − (ent_coeff/m)·∂H/∂z  (a clamped column: +0, written)
+//     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m
+// Closed-form KL(old ‖ new) per component, unprimed = old (beta_kl_term):
+//     lnB(α′,β′) − lnB(α,β) + (α−α′)ψ(α) + (β−β′)ψ(β) + (α′−α+β′−β)ψ(α+β),  lnB(a,b) = lnΓ(a) + lnΓ(b) − lnΓ(a+b)
+// lnΓ is the device library's lgamma in double.  tests/beta_ref.py restates all of it in float64.
+__device__ __forceinline__ float beta_clamp(float z, float zmax) { return z < -zmax ? -zmax : (z > zmax ? zmax : z); }
+__device__ __forceinline__ bool beta_inside(float z, float zmax) { return !(z < -zmax) && !(z > zmax); }
+__device__ __forceinline__ double beta_shape(float zc) {
+    const double t = (double)zc;
+    return 1.0 + (fmax(t, 0.0) + log1p(exp(-fabs(t))));
+}
+__device__ __forceinline__ double beta_dshape(float z, float zmax) {
+    return beta_inside(z, zmax) ? 1.0 / (1.0 + exp(-(double)z)) : 0.0;
+}
+
+// ψ(x) and ψ′(x) for x >= 1 in double: the upward recurrence ψ(x) = ψ(x+1) − 1/x, ψ′(x) = ψ′(x+1) + 1/x² to the
+// fixed shift point x >= 6 (at most 5 steps; the two share the reciprocal), then the asymptotic series in w = 1/x²:
+//     ψ(x)  ≈ ln x − 1/(2x) − Σ_{k=1…7} B_2k/(2k)·w^k        first term left out, at x = 6: (3617/8160)/6¹⁶ = 1.6e−13,
+//                                                            below 2⁻⁴⁰·ψ(6) = 2⁻⁴⁰·1.706 = 1.6e−12
+//     ψ′(x) ≈ 1/x + w/2 + (1/x)·Σ_{k=1…9} B_2k·w^k           first term left out, at x = 6: (174611/330)/6²¹ = 2.4e−14,
+//                                                            below 2⁻⁴⁰·ψ′(6) = 2⁻⁴⁰·0.1813 = 1.6e−13
+// (both series alternate and their terms still fall at x = 6, so the error is below the first term left out; larger x
+// only shrinks it).  NaN propagates; x < 1 is outside the contract (the loop is bounded, it never hangs).
+struct BetaPsi { double psi, tri; };
+__device__ __forceinline__ BetaPsi beta_psi2(double x) {
+    double p = 0.0, t = 0.0;
+    for (int k = 0; k < 5 && x < 6.0; ++k) {
+        const double r = 1.0 / x;
+        p -= r;
+        t += r * r;
+        x += 1.0;
+    }
+    const double r = 1.0 / x, w = r * r;
+    const double sp = w * (1.0 / 12 - w * (1.0 / 120 - w * (1.0 / 252 - w * (1.0 / 240 - w * (1.0 / 132 -
+                      w * (691.0 / 32760 - w * (1.0 / 12)))))));
+    const double st = w * (1.0 / 6 - w * (1.0 / 30 - w * (1.0 / 42 - w * (1.0 / 30 - w * (5.0 / 66 -
+                      w * (691.0 / 2730 - w * (7.0 / 6 - w * (3617.0 / 510 - w * (43867.0 / 798)))))))));
+    return BetaPsi{p + ((log(x) - 0.5 * r) - sp), t + ((r + 0.5 * w) + r * st)};
+}
+__device__ __forceinline__ double beta_digamma(double x) { return beta_psi2(x).psi; }
+__device__ __forceinline__ double beta_trigamma(double x) { return beta_psi2(x).tri; }
+__device__ __forceinline__ double beta_lnB(double a, double b) { return (lgamma(a) + lgamma(b)) - lgamma(a + b); }
+
+__device__ __forceinline__ double beta_lp_of(double a, double b, double lx, double l1x, double lnB) {
+    return ((a - 1.0) * lx + (b - 1.0) * l1x) - lnB;
+}
+__device__ __forceinline__ double beta_lp(double a, double b, float x) {
+    return beta_lp_of(a, b, log((double)x), log(1.0 - (double)x), beta_lnB(a, b));
+}
+// one component in full: its log-prob, entropy and their four partial derivatives in (α, β)
+struct BetaComp { double lp, H, dlp_a, dlp_b, dH_a, dH_b; };
+__device__ __forceinline__ BetaComp beta_component(double a, double b, float x) {
+    const double lx = log((double)x), l1x = log(1.0 - (double)x);
+    const double lnB = beta_lnB(a, b);
+    const BetaPsi pa = beta_psi2(a), pb = beta_psi2(b), pab = beta_psi2(a + b);
+    BetaComp c;
+    c.lp = beta_lp_of(a, b, lx, l1x, lnB);
+    c.H = ((lnB - (a - 1.0) * pa.psi) - (b - 1.0) * pb.psi) + ((a + b) - 2.0) * pab.psi;
+    c.dlp_a = lx + (pab.psi - pa.psi);
+    c.dlp_b = l1x + (pab.psi - pb.psi);
+    c.dH_a = ((a + b) - 2.0) * pab.tri - (a - 1.0) * pa.tri;
+    c.dH_b = ((a + b) - 2.0) * pab.tri - (b - 1.0) * pb.tri;
+    return c;
+}
+// one thread walks one row: the joint log-prob of x[0 … Aa) under z's clamped logits (the sampler, the KL monitor)
+__device__ __forceinline__ float beta_lp_row(const float* z, const float* x, int Aa, float zmax) {
+    double lp = 0.0;
+    for (int j = 0; j < Aa; ++j)
+        lp += beta_lp(beta_shape(beta_clamp(z[j], zmax)), beta_shape(beta_clamp(z[Aa + j], zmax)), x[j]);
+    return (float)lp;
+}
+__device__ __forceinline__ double beta_kl_term(double a, double b, double an, double bn) {
+    return ((beta_lnB(an, bn) - beta_lnB(a, b)) + (a - an) * beta_digamma(a) + (b - bn) * beta_digamma(b)) +
+           ((an - a) + (bn - b)) * beta_digamma(a + b);
+}
+__device__ __forceinline__ double beta_kl_row(const float* zo, const float* zn, int Aa, float zmax) {
+    double kl = 0.0;
+    for (int j = 0; j < Aa; ++j)
+        kl += beta_kl_term(beta_shape(beta_clamp(zo[j], zmax)), beta_shape(beta_clamp(zo[Aa + j], zmax)),
+                           beta_shape(beta_clamp(zn[j], zmax)), beta_shape(beta_clamp(zn[Aa + j], zmax)));
+    return kl;
+}
+
 // ---- Adam on one element (adam.cu:53-74): step = lr/bc1, ε added in double
 __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float step, float b1, float b2,
                                           float bc2) {

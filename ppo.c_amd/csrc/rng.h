@@ -42,6 +42,15 @@
 //     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter e·Aa + j   offset kNoise + g   .x .y   N(0, 1)
 //     ppo_gauss_sd_sample_device(key, offset)             counter i·Aa + j   offset `offset`   .x .y   N(0, 1)
+//   Beta policy (ppo_set_action_beta; beta.hip; Aa = A / 2): the Gaussian rows' key and offset at each call site; one
+//   Philox block per Marsaglia–Tsang attempt (at most 16) of each of the two Gamma variates of a component — the
+//   counter's low 56 bits the element, its top byte 2·attempt + sel (sel 0: the α variate, 1: the β variate)
+//     ppo_fill_synthetic      action noise   key s0 ^ 5   counter (i·Aa + j) | (2·attempt + sel) << 56   offset 0
+//                                            .x .y   N(0, 1) by Box–Muller, .z   u01, the acceptance test
+//     ppo_rollout_device / ppo_eval_device / ppo_rollout_act / ppo_act_device
+//                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter (e·Aa + j) | (2·attempt + sel) << 56
+//                                            offset kNoise + g   .x .y .z as above
+//     ppo_beta_sample_device(key, offset)                 counter (i·Aa + j) | (2·attempt + sel) << 56   offset `offset`
 #pragma once
 
 #include <cmath>

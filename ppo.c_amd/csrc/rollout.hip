@@ -66,6 +66,12 @@ __device__ __forceinline__ float angle_normalize(float x) {
     return y - (float)M_PI;
 }
 
+// What a built-in environment receives for a stored action column a: a itself, or — unit, the Beta policy, whose
+// columns hold x ∈ (0, 1) — bound·(2x − 1), bound the environment's own (Pendulum 2, the synthetic one 1)
+__device__ __forceinline__ float env_action(float a, int unit, float bound) {
+    return unit ? bound * (2.f * a - 1.f) : a;
+}
+
 // One Pendulum-v1 step of environment e from (θ, θ̇, steps) under action a: the transition's reward and next
 // observation; on return (θ, θ̇, steps) is what the next step starts from — the TimeLimit reset drawn where
 // `limit`.  The training and the evaluation kernels both step through this, so the two cannot drift.
@@ -101,14 +107,15 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
                                      const float* __restrict__ action, float* __restrict__ next_state,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
                                      uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
-                                     uint64_t step, uint64_t seed, int A) {
+                                     uint64_t step, uint64_t seed, int A, int unit) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
     float th = es[3 * e], thdot = es[3 * e + 1];
     float steps = es[3 * e + 2];
     // the torque is column 0 of the action row (A = 2: the state-dependent-σ Gaussian's row, a zero after it)
-    const PendulumStep o = pendulum_advance(th, thdot, steps, action[row * A], (uint64_t)e, step, seed);
+    const PendulumStep o = pendulum_advance(th, thdot, steps, env_action(action[row * A], unit, 2.f), (uint64_t)e, step,
+                                            seed);
     next_state[3 * row] = o.next[0];
     next_state[3 * row + 1] = o.next[1];
     next_state[3 * row + 2] = o.next[2];
@@ -130,13 +137,14 @@ __global__ void pendulum_step_kernel(float* __restrict__ es, float* __restrict__
 __global__ void pendulum_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                      float* __restrict__ reward, uint8_t* __restrict__ term,
                                      uint8_t* __restrict__ trunc, uint8_t* __restrict__ cont, int E, int T, int t,
-                                     uint64_t step, uint64_t seed, int A) {
+                                     uint64_t step, uint64_t seed, int A, int unit) {
     const int e = blockIdx.x * TPB + threadIdx.x;
     if (e >= E) return;
     const long row = (long)e * T + t;
     float th = es[3 * e], thdot = es[3 * e + 1];
     float steps = es[3 * e + 2];
-    const PendulumStep o = pendulum_advance(th, thdot, steps, action[(long)e * A], (uint64_t)e, step, seed);
+    const PendulumStep o = pendulum_advance(th, thdot, steps, env_action(action[(long)e * A], unit, 2.f), (uint64_t)e,
+                                            step, seed);
     reward[row] = o.reward;
     term[row] = 0;
     trunc[row] = (o.limit || t == T - 1) ? 1 : 0;
@@ -163,7 +171,7 @@ __device__ __forceinline__ float md_centre(const float* __restrict__ ar, const i
 // A: the action columns in use (the state-dependent-σ Gaussian's row holds A / 2 of them and zeros after)
 __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restrict__ ar, long k, int e, int j, int A,
                                                    uint64_t step, uint64_t seed, int cat,
-                                                   const int* __restrict__ md_off, int D) {
+                                                   const int* __restrict__ md_off, int D, int unit = 0) {
     SynthStep s;
     const u32x4 d = philox((uint64_t)e, kEnv + 2 * step, seed);
     s.done = u01(d.z) < 1.f / 500.f;
@@ -171,13 +179,16 @@ __device__ __forceinline__ SynthStep synth_advance(float o, const float* __restr
     // categorical: the index of column 0 mapped onto [−1, 1]
     float c = cat ? 2.f * (float)ppo::cat_index(ar[0], A) / (float)(A - 1) - 1.f : 0.f;
     if (md_off) c = md_centre(ar, md_off, j % D);    // multi-discrete: this element's component
-    float o2 = 0.95f * o + 0.05f * tanhf(cat ? c : ar[j % A]) + 0.05f * eps;
+    float o2 = 0.95f * o + 0.05f * tanhf(cat ? c : env_action(ar[j % A], unit, 1.f)) + 0.05f * eps;
     o2 = fminf(fmaxf(o2, -1.f), 1.f);
     s.o2 = o2;
     s.reward = 0.f;
     if (j == 0) {
         float ss = 0.f;
-        for (int q = 0; q < A; ++q) ss += ar[q] * ar[q];
+        for (int q = 0; q < A; ++q) {
+            const float aq = env_action(ar[q], unit, 1.f);
+            ss += aq * aq;
+        }
         float act_term = cat ? -0.01f * (c * c) : -0.01f * ss / (float)A;
         if (md_off) {
             float cc = 0.f;
@@ -198,12 +209,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
                                   float* __restrict__ next_state, float* __restrict__ reward,
                                   uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au, int unit) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, Au, step, seed, cat, md_off, D);
+    const SynthStep s = synth_advance(es[k], action + row * A, k, e, j, Au, step, seed, cat, md_off, D, unit);
     next_state[row * S + j] = s.o2;
     if (j == 0) {
         reward[row] = s.reward;
@@ -219,12 +230,12 @@ __global__ void synth_step_kernel(float* __restrict__ es, float* __restrict__ st
 __global__ void synth_eval_kernel(float* __restrict__ es, float* __restrict__ obs, const float* __restrict__ action,
                                   float* __restrict__ reward, uint8_t* __restrict__ term, uint8_t* __restrict__ trunc,
                                   uint8_t* __restrict__ cont, int E, int T, int t, uint64_t step, int S, int A,
-                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au) {
+                                  uint64_t seed, int cat, const int* __restrict__ md_off, int D, int Au, int unit) {
     const long k = (long)blockIdx.x * TPB + threadIdx.x;
     if (k >= (long)E * S) return;
     const int e = (int)(k / S), j = (int)(k % S);
     const long row = (long)e * T + t;
-    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, Au, step, seed, cat, md_off, D);
+    const SynthStep s = synth_advance(es[k], action + (long)e * A, k, e, j, Au, step, seed, cat, md_off, D, unit);
     if (j == 0) {
         reward[row] = s.reward;
         term[row] = s.done ? 1 : 0;
@@ -490,14 +501,14 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
 
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                   uint64_t seed, int cat, const int* md_off, int D, int Au) {
+                   uint64_t seed, int cat, const int* md_off, int D, int Au, int unit) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (3 * S + A + 2));
     PPO_REQUIRE(Au == A || (!cat && 2 * Au == A), "phip_env_step: the action columns in use");
     PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step: multi-discrete offsets");
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && Au == 1, "phip_env_step: Pendulum-v1 needs S = 3 and one action column");
         hipLaunchKernelGGL(pendulum_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
-                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed, A);
+                           state, action, next_state, reward, term, trunc, cont, E, T, t, step, seed, A, unit);
     } else if (kind == 2) {
         PPO_REQUIRE(S == 4 && A == 2 && cat, "phip_env_step: CartPole-v1 needs S = 4, A = 2 and categorical actions");
         hipLaunchKernelGGL(cartpole_step_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state,
@@ -505,14 +516,14 @@ void phip_env_step(int kind, float* env_state, float* state, const float* action
     } else {
         hipLaunchKernelGGL(synth_step_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, state, action, next_state, reward, term, trunc, cont, E, T, t, step, S, A,
-                           seed, cat, md_off, D, Au);
+                           seed, cat, md_off, D, Au, unit);
     }
     PPO_LAUNCH_CHECK();
 }
 
 void phip_env_step_eval(int kind, float* env_state, float* obs, const float* action, float* reward, uint8_t* term,
                         uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
-                        uint64_t seed, int cat, const int* md_off, int D, int Au) {
+                        uint64_t seed, int cat, const int* md_off, int D, int Au, int unit) {
     ppo::ProfScope ps(PPO_K_OTHER, 4.0 * E * (2 * S + A + 2));
     PPO_REQUIRE(Au == A || (!cat && 2 * Au == A), "phip_env_step_eval: the action columns in use");
     PPO_REQUIRE(!md_off || (cat && D >= 1 && 2 * D <= A), "phip_env_step_eval: multi-discrete offsets");
@@ -521,7 +532,7 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
     if (kind == 0) {
         PPO_REQUIRE(S == 3 && Au == 1, "phip_env_step_eval: Pendulum-v1 needs S = 3 and one action column");
         hipLaunchKernelGGL(pendulum_eval_kernel, dim3(ppo_divup(E, TPB)), dim3(TPB), 0, ppo::stream(), env_state, obs,
-                           action, reward, term, trunc, cont, E, T, t, step, seed, A);
+                           action, reward, term, trunc, cont, E, T, t, step, seed, A, unit);
     } else if (kind == 2) {
         PPO_REQUIRE(S == 4 && A == 2 && cat,
                     "phip_env_step_eval: CartPole-v1 needs S = 4, A = 2 and categorical actions");
@@ -530,7 +541,7 @@ void phip_env_step_eval(int kind, float* env_state, float* obs, const float* act
     } else {
         hipLaunchKernelGGL(synth_eval_kernel, dim3(ppo_divup((long)E * S, TPB)), dim3(TPB), 0, ppo::stream(),
                            env_state, obs, action, reward, term, trunc, cont, E, T, t, step, S, A, seed, cat, md_off,
-                           D, Au);
+                           D, Au, unit);
     }
     PPO_LAUNCH_CHECK();
 }

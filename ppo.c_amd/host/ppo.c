@@ -230,6 +230,10 @@ static int cat_on(const PPODev* d) { return d && (d->action_dist == 1 || d->acti
 static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
 /* the state-dependent-σ Gaussian (3): μ's outputs are [mean | raw log σ], the log σ vector is unread */
 static int sd_on(const PPODev* d) { return d && d->action_dist == 3; }
+/* the Beta policy (4): μ's outputs are [raw α-logits | raw β-logits], the log σ vector is unread */
+static int beta_on(const PPODev* d) { return d && d->action_dist == 4; }
+/* either of the two: half of the action row's columns hold the action, the head is the distribution's own */
+static int half_on(const PPODev* d) { return sd_on(d) || beta_on(d); }
 /* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
 static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
 
@@ -605,7 +609,7 @@ static int ppo_update_tiny(PPO* ppo, PPODev* d, const float* state, int B, int n
     /* … and their policy heads are Gaussian: a categorical policy takes that loop too */
     if (cat_on(d)) return -1;
     /* … as does the state-dependent-σ Gaussian, whose head reads half of μ's outputs as log σ */
-    if (sd_on(d)) return -1;
+    if (half_on(d)) return -1;                       /* … and the Beta policy, likewise */
     PhipTinyNet nv, np;
     /* one workgroup per phase for networks ≤ 128 wide; otherwise the cluster kernel (S → 256 → 256 → O
      * at B = 64, cluster.hip) when it takes the shape */
@@ -811,9 +815,12 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     /* μ grads + (top bucket) the log σ gradient behind them */
     const int cat = !tab && cat_on(d);
     const int sd = !tab && sd_on(d);
+    const int beta = !tab && beta_on(d);
+    /* the bounds the KL launch clamps under: the state-dependent-σ pair, or {−z_max, z_max} */
+    const float kl_sd[2] = {beta ? -d->beta_zmax : d->sd_ls[0], beta ? d->beta_zmax : d->sd_ls[1]};
     /* the KL monitor under masking: the masked joint lp, the categorical policy as nvec = {A} */
     const int kl_mask = cat && mask_on(d);
-    const int kl_dist = kl_mask ? 2 : cat || sd ? d->action_dist : 0;
+    const int kl_dist = kl_mask ? 2 : cat || sd || beta ? d->action_dist : 0;
     const int* kl_off = kl_mask ? disc_off(d) : md_off(d);
     const int kl_D = kl_mask ? disc_D(d) : d->md_D;
     const uint32_t* kl_m = kl_mask ? d->mask : NULL;
@@ -852,6 +859,16 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         phip_sd_head(mu->d_output, act, adv, olp, B, A, d->sd_ls[0], d->sd_ls[1], ppo->epsilon, ppo->ent_coeff, d->gmu,
                      NULL, NULL, d->sd_rec, d->stats + 1);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
+    } else if (beta) {     /* the Beta policy: the same branch with its head (beta.hip); log σ is unused in the same way */
+        if (mu->dtype != 0) die("ppo_update: the Beta policy needs fp32 compute mode (μ is in bf16 mode)");
+        if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
+        *ls_zero = 1;
+        phip_memset(d->sd_rec, 0, offsetof(PhipSdRec, ticket));
+        d->sd_rows = B;
+        nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
+        phip_beta_head(mu->d_output, act, adv, olp, B, A, d->beta_zmax, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
+                       d->sd_rec, d->stats + 1);
+        nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
     } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         nn_out_head_step(mu, 1, c->state, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
@@ -885,7 +902,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
                                cat && disc_max_n(d, A) > 32, NULL};
     if (kl_on && c->comm) {
         phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, d->sd_ls);
+                       0, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, kl_sd);
         phip_allreduce_sum_f32_async(d->kl->sums, 4);
     }
     phip_allreduce_join();
@@ -909,7 +926,7 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         if (c->comm) phip_kl_decide(d->kl, target_kl, kl_rows, kl_x);
         else
             phip_policy_kl(mu->d_output, pol->d_log_std, act, olp, B, A, kl_dist, ppo->epsilon, target_kl, kl_rows,
-                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, d->sd_ls);
+                           1, d->kl, kl_off, kl_D, kl_m, kl_m ? rows : NULL, kl_x ? &kl_ex : NULL, kl_sd);
         skip = &d->kl->stopped;
     }
     /* the last step of a policy epoch keeps its gradients while the feature is on: the host looks at the
@@ -980,7 +997,7 @@ static int step_graphs_ok(const StepCtx* c) {
     if (c->d->max_grad_norm > 0.f) return 0;      /* the table Adam does not read a clip coefficient */
     if (kl_target(c->d) > 0.f) return 0;          /* … nor a stop word, and a captured step has no KL launch */
     if (c->d->value_clip > 0.f) return 0;         /* … and a captured value step's head is the plain MSE */
-    if (cat_on(c->d) || sd_on(c->d)) return 0;    /* … and a captured policy step's head is the Gaussian one */
+    if (cat_on(c->d) || half_on(c->d)) return 0;  /* … and a captured policy step's head is the Gaussian one */
     if (c->d->adv_norm_mode != PPO_ADV_NORM_GLOBAL) return 0;   /* … and a captured policy step gathers for itself */
     PPO* ppo = c->ppo;
     Adam* ads[3] = {ppo->adam_V, ppo->adam_policy, ppo->adam_entropy};
@@ -1251,7 +1268,7 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const char* serial_env = getenv("PPO_SERIAL");
     const int concurrent = nv > 0 && np > 0 && !(serial_env && *serial_env && *serial_env != '0');
     /* the fused and the wide output-layer kernels embed the Gaussian head: a categorical policy takes neither */
-    const int own_head = cat_on(d) || sd_on(d);
+    const int own_head = cat_on(d) || half_on(d);
     const int fuse_p = !own_head && nn_out_head_ok(mu, 1);
     StepCtx c = {ppo, d, B, S, A, limit, num_batches, comm, nn_out_head_ok(V, 0), fuse_p,
                  !fuse_p && !own_head && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
@@ -1469,8 +1486,9 @@ void ppo_read_stats(void* vppo, double* out, int n) {
             v[33] = o;
         }
     }
-    if (sd_on(d) && d->sd_rec) {   /* the state-dependent-σ Gaussian: the last policy step's mean row entropy and its
-                                    * clamped log-σ elements and elements (this rank's rows); zeros while it is off */
+    if (half_on(d) && d->sd_rec) { /* the state-dependent-σ Gaussian: the last policy step's mean row entropy and its
+                                    * clamped log-σ elements and elements (this rank's rows); zeros while it is off.
+                                    * The Beta policy: the same slots, its clamped logits and its logits m·A */
         PhipSdRec r;
         phip_d2h(&r, d->sd_rec, offsetof(PhipSdRec, ticket));
         v[4] = d->sd_rows > 0 ? r.ent_sum / d->sd_rows : 0.0;
@@ -1628,10 +1646,10 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
     const int E = n_envs, T = horizon;
     const int S = ppo->buffer->state_size, A = ppo->buffer->action_size;
     /* the action columns the environment reads, from the PPODev if there is one: a declined call creates nothing */
-    const int Au = sd_on((const PPODev*)ppo->dev) ? A / 2 : A;
+    const int Au = half_on((const PPODev*)ppo->dev) ? A / 2 : A;
     if (env_kind == 0 && (S != 3 || Au != 1)) return -1;
     PPODev* d = dev_ws(ppo, 1);
-    const int cat = cat_on(d), sd = sd_on(d);
+    const int cat = cat_on(d), sd = sd_on(d), beta = beta_on(d);
     if (env_kind == 2 && (S != 4 || A != 2 || !cat)) return -1;
     eval_ws(d, E, (long)E * T, S, A);
     /* the first reset and the key of every later draw, as ppo_rollout_device derives them; the step counter is
@@ -1658,10 +1676,13 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         else if (sd)
             phip_sd_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, d->sd_ls[0], d->sd_ls[1], key,
                                 step);
+        else if (beta && deterministic) phip_beta_mean(pol->mu->d_output, d->ev_act, E, A, d->beta_zmax);
+        else if (beta)
+            phip_beta_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, d->beta_zmax, key, step);
         else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
-                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D, Au);
+                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D, Au, beta);
     }
     phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
                       d->ev_agg, NULL);
@@ -2229,6 +2250,78 @@ int ppo_gauss_sd_kl_exact_device(const float* d_new, const float* d_old, const i
     return 0;
 }
 
+/* ppo_ext.h: the Beta policy */
+static int beta_zmax_ok(float z_max) { return isfinite(z_max) && z_max > 0.f; }
+
+int ppo_set_action_beta(void* vppo, float z_max) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !beta_zmax_ok(z_max) || !phip_sd_shape_ok(ppo->buffer->action_size)) return -1;
+    if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;           /* bf16 compute mode */
+    PPODev* d = dev_ws(ppo, 1);
+    if (!d->sd_rec) d->sd_rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    d->beta_zmax = z_max;
+    d->action_dist = 4;
+    if (d->mask_on) mask_store(ppo, d, 0);           /* masking belongs to a discrete policy: off with it */
+    return 0;
+}
+
+int ppo_get_action_beta(void* vppo, float* out_z_max) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    if (!beta_on(d)) return 0;
+    if (out_z_max) *out_z_max = d->beta_zmax;
+    return 1;
+}
+
+/* the head, the sampler and the KL launch on caller-supplied device arrays (test and serving entries: bad arguments return −1 ahead
+ * of any device call, so nothing is recorded for ppo_last_error) */
+int ppo_beta_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp, int m,
+                         int A, float z_max, float eps, float ent_coeff, float* d_grad, float* d_lp, float* d_ent,
+                         double* loss, long long* clamped2) {
+    static PhipSdRec* rec = NULL;
+    if (!d_z || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || !clamped2 || m <= 0 ||
+        !phip_sd_shape_ok(A) || !beta_zmax_ok(z_max) || isnan(eps))
+        return -1;
+    if (!rec) rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    phip_memset(rec, 0, offsetof(PhipSdRec, ticket));
+    phip_beta_head(d_z, d_action, d_adv, d_old_lp, m, A, z_max, eps, ent_coeff, d_grad, d_lp, d_ent, rec, NULL);
+    phip_sync();
+    PhipSdRec r;
+    phip_d2h(&r, rec, offsetof(PhipSdRec, ticket));
+    *loss = r.loss;
+    clamped2[0] = (long long)r.counts[0];
+    clamped2[1] = (long long)r.counts[1];
+    return 0;
+}
+
+int ppo_beta_sample_device(const float* d_z, int m, int A, float z_max, unsigned long long key,
+                           unsigned long long offset, int deterministic, float* d_action, float* d_log_prob) {
+    if (!d_z || !d_action || (!deterministic && !d_log_prob) || m <= 0 || !phip_sd_shape_ok(A) || !beta_zmax_ok(z_max))
+        return -1;
+    if (deterministic) phip_beta_mean(d_z, d_action, m, A, z_max);
+    else phip_beta_sample(d_z, NULL, d_action, d_log_prob, m, A, z_max, key, offset);
+    phip_sync();
+    return 0;
+}
+
+int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
+                       const float* d_old_lp, int m, int A, float z_max, float eps, double* d_row_kl, double* out3) {
+    static PhipKlRec* rec = NULL;
+    if (!d_new || !d_old || !d_action || !d_old_lp || !out3 || m <= 0 || !phip_sd_shape_ok(A) || !beta_zmax_ok(z_max) ||
+        isnan(eps))
+        return -1;
+    if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+    phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
+    const PhipKlExact ex = {d_old, NULL, d_rows, NULL, 0, 0, d_row_kl};
+    const float sd[2] = {-z_max, z_max};
+    phip_policy_kl(d_new, NULL, d_action, d_old_lp, m, A, 4, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, &ex, sd);
+    phip_sync();
+    float sums[4];
+    phip_d2h(sums, rec->sums, sizeof(sums));
+    for (int k = 0; k < 3; k++) out3[k] = (double)sums[k] / m;
+    return 0;
+}
+
 /* the discrete head and sampler on caller-supplied device arrays (the test entries below: bad arguments return −1
  * ahead of any device call, so nothing is recorded for ppo_last_error); nvec is a host array, its offsets go to a
  * device array kept here */
@@ -2424,6 +2517,9 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
 void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, int n_epochs_policy,
                      int n_epochs_value) {
     /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
+    if (beta_on((PPODev*)ppo->dev))
+        die("train_ppo_epoch: the Beta policy (ppo_set_action_beta) is not supported by the host rollout; use "
+            "ppo_rollout_device + ppo_update");
     if (sd_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: the state-dependent-σ Gaussian policy (ppo_set_action_gaussian_sd) is not supported by "
             "the host rollout; use ppo_rollout_device + ppo_update");
@@ -2449,6 +2545,8 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
+    if (beta_on((PPODev*)ppo->dev))
+        die("eval_ppo: the Beta policy (ppo_set_action_beta) is not supported by the host rollout; use ppo_eval_device");
     if (sd_on((PPODev*)ppo->dev))
         die("eval_ppo: the state-dependent-σ Gaussian policy (ppo_set_action_gaussian_sd) is not supported by the host "
             "rollout; use ppo_eval_device");
@@ -2558,10 +2656,11 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         die("ppo_rollout_device: env_kind must be 0 (Pendulum-v1), 1 (synthetic) or 2 (CartPole-v1)");
     const int S = b->state_size, A = b->action_size;
     PPODev* d = dev_ws(ppo, 1);
-    const int cat = cat_on(d), sd = sd_on(d);
-    const int Au = sd ? A / 2 : A;                   /* the action columns the environment reads */
+    const int cat = cat_on(d), sd = sd_on(d), beta = beta_on(d);
+    const int Au = sd || beta ? A / 2 : A;           /* the action columns the environment reads */
     if (env_kind == 0 && (S != 3 || Au != 1))
-        die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1 (2 under the state-dependent-σ Gaussian)");
+        die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1 (2 under the state-dependent-σ Gaussian "
+            "and the Beta policy)");
     if (env_kind == 2 && (S != 4 || A != 2 || !cat))
         die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
             "(ppo_set_action_dist, or ppo_set_action_multidiscrete with nvec = {2})");
@@ -2596,10 +2695,12 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
         else if (sd)
             phip_sd_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
                                 key, step);
+        else if (beta)
+            phip_beta_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->beta_zmax, key, step);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
-                      cat, md_off(d), d->md_D, Au);
+                      cat, md_off(d), d->md_D, Au, beta);
     }
     ro_finish(ppo, d, E, T);
 }
@@ -2635,6 +2736,11 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
         nn_forward_dev(ppo->policy->mu, obs, (int)N);
         phip_sd_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, d->sd_ls[0],
                        d->sd_ls[1], s0 ^ 0x5, 0);
+    } else if (beta_on((PPODev*)ppo->dev)) {         /* the "action noise" key, counter i·Aa + j under the attempt byte */
+        PPODev* d = (PPODev*)ppo->dev;
+        nn_forward_dev(ppo->policy->mu, obs, (int)N);
+        phip_beta_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, d->beta_zmax,
+                         s0 ^ 0x5, 0);
     } else {
         ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     }
@@ -2701,6 +2807,8 @@ static long long rollout_act(PPO* ppo, const uint32_t* d_mask, float* d_action) 
     else if (sd_on(d))
         phip_sd_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
                             d->ext_key, step);
+    else if (beta_on(d))
+        phip_beta_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->beta_zmax, d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     if (!d_mask && mask_on(d)) phip_mask_fill_rows(d->mask, rows, E, A);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
@@ -2776,6 +2884,9 @@ static int act_device(PPO* ppo, const float* d_obs, const uint32_t* d_mask, int 
     else if (sd_on(d) && deterministic) phip_sd_mean(pol->mu->d_output, d_action, m, A);
     else if (sd_on(d))
         phip_sd_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, d->sd_ls[0], d->sd_ls[1], key, step);
+    else if (beta_on(d) && deterministic) phip_beta_mean(pol->mu->d_output, d_action, m, A, d->beta_zmax);
+    else if (beta_on(d))
+        phip_beta_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, d->beta_zmax, key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;
@@ -2892,7 +3003,7 @@ int ppo_set_compute_dtype(void* vppo, int dtype) {
     /* bf16 mode knows ReLU and identity: a tanh layer in either network declines it, both left as they were */
     if (dtype == 1 && (nn_has_tanh(ppo->V) || nn_has_tanh(ppo->policy->mu))) return -1;
     /* … and the categorical head reads fp32 logits: bf16 mode is declined while it is on */
-    if (dtype == 1 && (cat_on((PPODev*)ppo->dev) || sd_on((PPODev*)ppo->dev))) return -1;
+    if (dtype == 1 && (cat_on((PPODev*)ppo->dev) || half_on((PPODev*)ppo->dev))) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;
     return nn_set_compute_dtype(ppo->policy->mu, dtype);
 }

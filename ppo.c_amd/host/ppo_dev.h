@@ -183,6 +183,10 @@ typedef struct {
     float sd_ls[2];
     PhipSdRec* sd_rec;
     int sd_rows;
+    /* the Beta policy (ppo_set_action_beta; action_dist == 4; csrc/beta.hip): μ's A outputs are A / 2 raw α-logits and
+     * A / 2 raw β-logits, clamped to [−beta_zmax, beta_zmax] on read.  Its head leaves its record in sd_rec and its
+     * rows in sd_rows, as the state-dependent-σ head does: counts = {clamped logits, logits m·A} */
+    float beta_zmax;
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

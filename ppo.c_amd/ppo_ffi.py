@@ -187,6 +187,14 @@ _SIGS = {
                                              _P, _P]),
     "ppo_gauss_sd_kl_exact_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P,
                                                C.POINTER(C.c_double)]),
+    "ppo_set_action_beta": (C.c_int, [_P, C.c_float]),
+    "ppo_get_action_beta": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ppo_beta_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P, _P, _P,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_longlong)]),
+    "ppo_beta_sample_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_ulonglong, C.c_ulonglong, C.c_int, _P,
+                                         _P]),
+    "ppo_beta_kl_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P,
+                                     C.POINTER(C.c_double)]),
     "ppo_set_action_mask": (C.c_int, [_P, C.c_int]),
     "ppo_get_action_mask": (C.c_int, [_P]),
     "ppo_action_mask_words": (C.c_int, [_P]),
