@@ -993,6 +993,34 @@ int ppo_beta_sample_device(const float* d_z, int m, int A, float z_max, unsigned
 int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
                        const float* d_old_lp, int m, int A, float z_max, float eps, double* d_row_kl, double* out3);
 
+/* ---------------- orthogonal weight initialisation (csrc/ortho.hip) ----------------
+ * How Stable-Baselines3 (ortho_init, its default), CleanRL (layer_init) and baselines PPO2 start a run: every weight
+ * matrix orthogonal, every bias zero.  create_ppo keeps the reference's He / Xavier-uniform draw from rand(); this
+ * call replaces that draw on the device, with torch.nn.init.orthogonal_'s definition restated in double.  For a
+ * weight W [rows = out][cols = in], gain g and a Gaussian G of W's shape in fp32:
+ *     M = G if rows >= cols, else Gᵀ: T × S, T = max(rows, cols), S = min(rows, cols)
+ *     M = Q·R by Householder reflections (Q: T × S with orthonormal columns, R upper triangular)
+ *     Q ← Q·diag(s), s_j = sign(R_jj), +1 for a zero
+ *     W = (float)((double)g · Q) if rows >= cols, else the same of Qᵀ
+ * in double from the fp32 G on, rounded to fp32 once, at the store.  A zero column gets no reflection: no NaN.  W is a
+ * function of (G, shape, g) alone — no floating-point atomics — so every rank of a data-parallel run that passes the
+ * same seed holds identical parameters.  Limits: 1 <= S <= 1024, T <= 4096.
+ * ppo_init_orthogonal draws G[r·cols + c] = normal_at(r·cols + c, offset, key), key = splitmix64(seed ^ "ORTHO"), the
+ * offset naming (network, layer) (csrc/rng.h's stream table: no two layers and neither network share a draw), and
+ * fills and orthogonalises every layer of the policy's μ and of V in one launch: hidden layers with gain_hidden, μ's
+ * output layer with gain_policy_out, V's with gain_value_out (SB3: √2, 0.01, 1).  Every bias becomes +0.  log σ, every
+ * option and the three Adams stay untouched.  Call it after create_ppo and before the first update.  It is a by-value
+ * change of parameters, as a load is: the host mirrors pull at their next use, bf16 mode's shadow is refreshed, every
+ * update path stays available, and checkpoints need nothing new.  Synchronises.  Returns 0, or −1 with nothing
+ * changed: a NULL ppo, a gain that is not finite or not positive, a layer outside the limits, or an Adam of the PPO
+ * whose time_step is not 0.
+ * ppo_orthogonal_device is the test entry, the same launch on one caller-supplied matrix: d_W holds G on entry and W
+ * on return.  Synchronises.  Returns 0, or −1 with nothing launched and nothing recorded for ppo_last_error for bad
+ * arguments (a NULL array, a shape outside the limits, a gain that is not finite or not positive). */
+int ppo_init_orthogonal(void* ppo, unsigned long long seed, float gain_hidden, float gain_policy_out,
+                        float gain_value_out);
+int ppo_orthogonal_device(float* d_W, int rows, int cols, float gain);
+
 /* layer 0's input of the last device forward of a NeuralNetwork*, m rows × input_size fp32, to the
  * host: the gathered minibatch rows the GEMMs read (NeuralNetwork.d_x0) — for parity tests;
  * synchronises.  bf16 copies (x0_dtype 1) are not converted: returns −1 for them and for m beyond the

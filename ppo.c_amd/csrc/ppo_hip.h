@@ -384,6 +384,26 @@ void phip_beta_sample_rows(const float* z, const int* rows, float* action, float
 /* the deterministic action: action [m, A] ← the mean α / (α + β), zeros after it */
 void phip_beta_mean(const float* z, float* action, int m, int A, float z_max);
 
+/* ---------------- orthogonal weight initialisation (ortho.hip) ---------------- */
+/* one matrix of a launch: W [rows][cols] row-major ← gain · (the orthogonal factor of G, torch.nn.init.orthogonal_'s
+ * definition in double); fill != 0: G[r·cols + c] = normal_at(r·cols + c, offset, key) (rng.h), else G is what W
+ * holds on entry; bias (may be NULL) [n_bias] ← +0.  work is the launcher's */
+typedef struct {
+    float* W;
+    int rows, cols;
+    float gain;
+    int fill;
+    uint64_t key, offset;
+    float* bias;
+    int n_bias;
+    double* work;
+} PhipOrthoJob;
+int  phip_ortho_shape_ok(int rows, int cols);   /* 1 <= min <= 1024, max <= 4096 */
+/* n matrices (a HOST array; shapes checked by the caller), one launch, one workgroup each.  The exception to this
+ * header's rule: the two double workspaces per matrix and the device copy of the jobs are allocated for the call and
+ * freed after it — it runs once per training run.  Synchronises */
+void phip_ortho(PhipOrthoJob* jobs, int n);
+
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
  * (n, mean, M2) in double for this shard.  Then normalise with the (global)

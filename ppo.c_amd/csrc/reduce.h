@@ -46,6 +46,15 @@ template <ChanFn F> struct TripleMerge {  // chan or chan_ref_order as a fold's 
 };
 struct DaddRn { __device__ double operator()(double a, double b) const { return __dadd_rn(a, b); } };
 
+// ---- a wave's sum of one double per lane ------------------------------------------------------------------------
+// The __shfl_xor butterfly (xor 32, 16, … 1), every lane gets the sum: the order block_two_pass_triple's wave sums are
+// written in, and the one ortho.hip's dot products and column norms take.
+__device__ __forceinline__ double wave_sum_xor_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // ---- runs, then a pairwise tree over the threads ---------------------------------------------------------------
 // The pairwise tree over s[0 … T) of a T-thread workgroup: stride 1, 2, 4, …, thread t, a multiple of 2·stride,
 // does s[t] = op(s[t], s[t + stride]).  Thread t has stored s[t]; every thread calls this and gets s[0].  NOT the

@@ -51,6 +51,9 @@
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter (e·Aa + j) | (2·attempt + sel) << 56
 //                                            offset kNoise + g   .x .y .z as above
 //     ppo_beta_sample_device(key, offset)                 counter (i·Aa + j) | (2·attempt + sel) << 56   offset `offset`
+//   orthogonal initialisation (ppo_init_orthogonal(seed); ortho.hip): the Gaussian matrix of every layer
+//     G              key splitmix64(seed ^ 0x4F5254484F)   counter r·cols + c (the weight's own layout)
+//                    offset network << 32 | layer (network 0: μ, 1: V)   .x .y   N(0, 1)
 #pragma once
 
 #include <cmath>

@@ -2322,6 +2322,58 @@ int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows
     return 0;
 }
 
+/* ---- orthogonal initialisation (ppo_ext.h; csrc/ortho.hip) ---- */
+#define ORTHO_TAG 0x4F5254484FULL                     /* "ORTHO": the stream's key is splitmix64(seed ^ tag), rng.h */
+static int ortho_gain_ok(float g) { return isfinite(g) && g > 0.f; }
+
+static int ortho_shapes_ok(const NeuralNetwork* nn) {
+    for (int i = 0; i < nn->num_layers - 1; i++)
+        if (!phip_ortho_shape_ok(nn->layers[i].output_size, nn->layers[i].input_size)) return 0;
+    return 1;
+}
+
+/* the jobs of one network: network 0 is μ, 1 is V; the last layer takes gain_out */
+static int ortho_jobs(PhipOrthoJob* jobs, NeuralNetwork* nn, uint64_t network, uint64_t key, float gain_hidden,
+                      float gain_out) {
+    const int L = nn->num_layers - 1;
+    for (int i = 0; i < L; i++) {
+        Layer* ly = &nn->layers[i];
+        const PhipOrthoJob job = {ly->d_weights, ly->output_size, ly->input_size, i == L - 1 ? gain_out : gain_hidden,
+                                  1, key, network << 32 | (uint64_t)i, ly->d_biases, ly->output_size, NULL};
+        jobs[i] = job;
+    }
+    return L;
+}
+
+int ppo_init_orthogonal(void* vppo, unsigned long long seed, float gain_hidden, float gain_policy_out,
+                        float gain_value_out) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !ortho_gain_ok(gain_hidden) || !ortho_gain_ok(gain_policy_out) || !ortho_gain_ok(gain_value_out))
+        return -1;
+    NeuralNetwork *mu = ppo->policy->mu, *V = ppo->V;
+    if (!ortho_shapes_ok(mu) || !ortho_shapes_ok(V)) return -1;
+    if (ppo->adam_policy->time_step != 0 || ppo->adam_V->time_step != 0 || ppo->adam_entropy->time_step != 0) return -1;
+    PhipOrthoJob* jobs = (PhipOrthoJob*)xmalloc(sizeof(PhipOrthoJob) * (size_t)(mu->num_layers + V->num_layers));
+    const uint64_t key = splitmix64(seed ^ ORTHO_TAG);
+    int n = ortho_jobs(jobs, mu, 0, key, gain_hidden, gain_policy_out);
+    n += ortho_jobs(jobs + n, V, 1, key, gain_hidden, gain_value_out);
+    phip_ortho(jobs, n);
+    free(jobs);
+    /* a parameter write like the end of ppo_update: the host mirrors pull, the bf16 shadows follow */
+    V->dev_version++;
+    mu->dev_version++;
+    nn_sync_w16(V);
+    nn_sync_w16(mu);
+    return 0;
+}
+
+int ppo_orthogonal_device(float* d_W, int rows, int cols, float gain) {
+    if (!d_W || !phip_ortho_shape_ok(rows, cols) || !ortho_gain_ok(gain)) return -1;
+    PhipOrthoJob job = {d_W, rows, cols, gain, 0, 0, 0, NULL, 0, NULL};
+    phip_ortho(&job, 1);
+    return 0;
+}
+
 /* the discrete head and sampler on caller-supplied device arrays (the test entries below: bad arguments return −1
  * ahead of any device call, so nothing is recorded for ppo_last_error); nvec is a host array, its offsets go to a
  * device array kept here */

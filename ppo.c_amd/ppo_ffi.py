@@ -195,6 +195,8 @@ _SIGS = {
                                          _P]),
     "ppo_beta_kl_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, _P,
                                      C.POINTER(C.c_double)]),
+    "ppo_init_orthogonal": (C.c_int, [_P, C.c_ulonglong, C.c_float, C.c_float, C.c_float]),
+    "ppo_orthogonal_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
     "ppo_set_action_mask": (C.c_int, [_P, C.c_int]),
     "ppo_get_action_mask": (C.c_int, [_P]),
     "ppo_action_mask_words": (C.c_int, [_P]),
