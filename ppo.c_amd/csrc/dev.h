@@ -53,6 +53,39 @@ inline long long gemm_key(int op, int engine, long m, long n, long l) {
 // h propagates; tests/tanh_ref.py states the same order in numpy.
 __device__ __forceinline__ float tanh_bwd(float g, float h) { return __fsub_rn(g, __fmul_rn(__fmul_rn(g, h), h)); }
 
+// ELU, α = 1: h = z > 0 ? z : expm1f(z).  expm1f runs unconditionally on min(z, 0) and the result is selected, so
+// no branch diverges around its long sequence; the select is on z ≤ 0, false for NaN, which therefore passes
+// through (fminf alone would turn it into 0).  expm1f rounds to −1 exactly for z ≲ −17; +inf → +inf, −inf → −1.
+__device__ __forceinline__ float elu_fwd(float z) {
+    const float e = expm1f(fminf(z, 0.f));
+    return z <= 0.f ? e : z;
+}
+// ELU′ through the post-activation h: for z ≤ 0, h + 1 = e^z = ELU′(z), so gx = h > 0 ? a : a·(h + 1), two
+// roundings (sum, product), never fused.  h = −1 passes exactly 0, h = 0 passes a unchanged, NaN in h gives
+// a·NaN (the comparison is false on NaN); tests/elu_ref.py states the same in numpy.
+__device__ __forceinline__ float elu_bwd(float a, float h) { return h > 0.f ? a : __fmul_rn(a, __fadd_rn(h, 1.0f)); }
+
+// The h-derived activations of the GEMM epilogues, by kind HA (PHIP_ACT_TANH, PHIP_ACT_ELU): forward applied to
+// z = acc + bias, backward to the accumulator a = g·W and the stored post-activation h of the layer below.  One
+// more such activation is one more case here and one more instantiation of the tiled kernels.
+template <int HA>
+__device__ __forceinline__ float hact_fwd(float z) {
+    static_assert(HA == PHIP_ACT_TANH || HA == PHIP_ACT_ELU, "hact_fwd: not an h-derived activation");
+    if constexpr (HA == PHIP_ACT_TANH) return tanhf(z);
+    else return elu_fwd(z);
+}
+template <int HA>
+__device__ __forceinline__ float hact_bwd(float a, float h) {
+    static_assert(HA == PHIP_ACT_TANH || HA == PHIP_ACT_ELU, "hact_bwd: not an h-derived activation");
+    if constexpr (HA == PHIP_ACT_TANH) return tanh_bwd(a, h);
+    else return elu_bwd(a, h);
+}
+// the same with the kind a run-time value, uniform over a launch (the small-M kernels)
+__device__ __forceinline__ float hact_fwd_rt(int ha, float z) { return ha == PHIP_ACT_ELU ? elu_fwd(z) : tanhf(z); }
+__device__ __forceinline__ float hact_bwd_rt(int ha, float a, float h) {
+    return ha == PHIP_ACT_ELU ? elu_bwd(a, h) : tanh_bwd(a, h);
+}
+
 // Wave sum by the __shfl_xor butterfly (xor 32, 16, … 1): every lane gets the sum.  Not interchangeable with
 // wave_sum64 below, which adds in another order and gives other bits.
 __device__ __forceinline__ float wave_sum_xor(float v) {

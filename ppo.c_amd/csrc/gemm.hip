@@ -5,7 +5,9 @@
 //   grad_x    gx = g·W (·1[y_prev>0])    mat_mul.cu:175-188 (K3) + activation_function.cu:24-29 (K6)
 //   grad_W    gW = gᵀ·x, gb = Σ_m g      mat_mul.cu:195-208 (K4) + neural_network.cu:108-118 (K7)
 // and, with no counterpart in the reference, tanh layers: forward y = tanhf(x·Wᵀ + b) (no mask bits) and
-// grad_x gx = a − (a·h)·h with a = g·W and h the stored post-activation of the layer below (ppo::tanh_bwd).
+// grad_x gx = a − (a·h)·h with a = g·W and h the stored post-activation of the layer below (ppo::tanh_bwd);
+// ELU layers (α = 1) the same way: forward y = z > 0 ? z : expm1f(z), grad_x gx = h > 0 ? a : a·(h + 1)
+// (ppo::elu_bwd).  Both are "h-derived" kinds of one epilogue variant (HA below; ppo::hact_fwd / hact_bwd).
 //
 // Design (gfx950):
 //  * v_mfma_f32_32x32x2_f32 — exact fp32 (a k-ordered fma chain), 64 FLOP/clk/SIMD, the same
@@ -37,9 +39,10 @@ struct Args {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
     const float* bias; int relu;          // OP_NT epilogue
-    int tanh;                             // OP_NT: tanhf after the bias (relu = 0, no bits); OP_NN: `mask` is a tanh
-                                          // layer's post-activation h and gx = acc − (acc·h)·h.  The host picks the
-                                          // tiled TH kernels from it; the small-M kernel reads it (uniform over a launch).
+    int hact;                             // 0, PHIP_ACT_TANH or PHIP_ACT_ELU.  OP_NT: that activation after the bias
+                                          // (relu = 0, no bits); OP_NN: `mask` is such a layer's post-activation h and
+                                          // gx = hact_bwd(acc, h).  The host picks the tiled HA kernels from it; the
+                                          // small-M kernel reads it (uniform over a launch).
     const float* mask; int ldmask;        // OP_NN epilogue (post-activation of the previous layer)
     const int* ridx;                      // OP_NT: A row r is memory row ridx[r] (fused gather)
     float* acopy;                         // OP_NT: tn == 0 workgroups write the gathered A rows here
@@ -208,12 +211,13 @@ constexpr int lds_floats() {
 
 // One workgroup's output tile: block b of an nwg-block grid (the kernels below pass their own
 // block id, or an offset one when two GEMMs share a launch).
-// TH: the tanh forms of the forward / grad_x epilogue (forward: tanhf after the bias, no bits; grad_x:
-// acc − (acc·h)·h with h = a.mask at C's own coordinates).  A kernel of its own, chosen on the host from
-// the launch's activation kind: the ReLU / identity kernels (TH = false) are instruction for instruction
-// what they were — inside one kernel the extra epilogue version raised the 128×128 grad_x tile past its
-// 128-VGPR budget (17 spills, also in the paired launch, which never takes a tanh layer).
-template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, bool TH = false>
+// HA (0, PHIP_ACT_TANH, PHIP_ACT_ELU): the h-derived forms of the forward / grad_x epilogue (forward:
+// ppo::hact_fwd<HA> after the bias, no bits; grad_x: ppo::hact_bwd<HA>(acc, h) with h = a.mask at C's own
+// coordinates, a block's 16 values loaded once whichever kind reads them).  A kernel of its own per kind,
+// chosen on the host from the launch's activation kind: the ReLU / identity kernels (HA = 0) are instruction
+// for instruction what they were — inside one kernel the extra epilogue version raised the 128×128 grad_x
+// tile past its 128-VGPR budget (17 spills, also in the paired launch, which never takes such a layer).
+template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, int HA = 0>
 __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int nwg, float* __restrict__ lds) {
     constexpr int WARPS_N = 4 / WARPS_M;
     constexpr int WM = BM / WARPS_M, WN = BN / WARPS_N;
@@ -353,7 +357,7 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
             if (OP == OP_NT && a.bias) bcol = a.bias[colc];
             bool keep[16];
             float hv[16];
-            if constexpr (OP == OP_NN && TH) {                // h at C's own coordinates, clamped into [M, N)
+            if constexpr (OP == OP_NN && HA != 0) {           // h at C's own coordinates, clamped into [M, N)
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
                     hv[e] = a.mask[(long)min(r0 + (e & 3) + 8 * (e >> 2), a.M - 1) * a.ldmask + colc];
@@ -384,9 +388,9 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
                 const bool ok = col_ok && row < a.M;
                 float v = acc[i][j][e];
                 float* dst = a.C + (long)row * a.ldc + col;
-                if constexpr (TH) {
-                    if (OP == OP_NT) v = tanhf(v + bcol);
-                    else v = ppo::tanh_bwd(v, hv[e]);
+                if constexpr (HA != 0) {
+                    if (OP == OP_NT) v = ppo::hact_fwd<HA>(v + bcol);
+                    else v = ppo::hact_bwd<HA>(v, hv[e]);
                     if (ok) *dst = v;
                 } else if (OP == OP_NT) {
                     v += bcol;
@@ -403,18 +407,18 @@ __device__ __forceinline__ void gemm_tile(const Args& a, const int b, const int 
                     else *dst = v;
                 }
             }
-            if (!TH && OP == OP_NT && a.bits_out && r < 16) {
+            if (HA == 0 && OP == OP_NT && a.bits_out && r < 16) {
                 const int row = r0 + (r & 3) + 8 * (r >> 2);
                 if (row < a.M && c0 < a.N) a.bits_out[(long)row * a.wpr + (c0 >> 5)] = word;
             }
         }
 }
 
-template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int BK, bool VEC, bool DBUF, int HA = 0>
 __global__ __launch_bounds__(NT_, min_waves(BM * BN, BK)) void gemm_f32_kernel(Args a) {
-    static_assert(!TH || OP != OP_TN, "tanh epilogues: forward and grad_x only");
+    static_assert(HA == 0 || OP != OP_TN, "h-derived activation epilogues: forward and grad_x only");
     __shared__ __attribute__((aligned(16))) float lds[lds_floats<OP, BM, BN, BK, DBUF>()];
-    gemm_tile<OP, BM, BN, WARPS_M, BK, VEC, DBUF, TH>(a, blockIdx.x, gridDim.x, lds);
+    gemm_tile<OP, BM, BN, WARPS_M, BK, VEC, DBUF, HA>(a, blockIdx.x, gridDim.x, lds);
 }
 
 // grad_W and grad_x of one layer in one launch (both 128x128/BK16, vector loads): blocks
@@ -550,15 +554,15 @@ __global__ __launch_bounds__(64 * SM_WAVES) void gemm_smallm_kernel(Args a) {
             if (OP == OP_NT) {
                 v += bc;
                 if (a.relu) v = v > 0.f ? v : 0.f;
-                else if (a.tanh) v = tanhf(v);               // uniform over the launch; no bits
+                else if (a.hact) v = ppo::hact_fwd_rt(a.hact, v);   // uniform over the launch; no bits
                 if (ok) a.C[(long)row * a.ldc + col] = v;
                 if (a.bits_out) {
                     const unsigned long long bb = __ballot(ok && v > 0.f);
                     if (r == e) word = h ? (unsigned)(bb >> 32) : (unsigned)bb;
                 }
             } else if (OP == OP_NN) {
-                if (ok && a.tanh) {                         // a.mask = h: acc − (acc·h)·h
-                    a.C[(long)row * a.ldc + col] = ppo::tanh_bwd(v, a.mask[(long)row * a.ldmask + col]);
+                if (ok && a.hact) {                         // a.mask = h: tanh′ or ELU′ through h
+                    a.C[(long)row * a.ldc + col] = ppo::hact_bwd_rt(a.hact, v, a.mask[(long)row * a.ldmask + col]);
                 } else if (ok) {
                     bool keep = true;
                     if (a.bits_in) keep = (a.bits_in[(long)row * a.wpr + (n0 >> 5)] >> r) & 1u;
@@ -590,6 +594,18 @@ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
 
 int g_flags = 0;               // experiment bits passed to every tiled launch (ppo_gemm_flags)
 
+// one h-derived kind's own kernels (gemm_tile HA)
+template <int OP, int BM, int BN, int WARPS_M, int BK, bool DBUF, int HA>
+void launch_hact(const Args& a, long grid) {
+    if (a.vec_a && a.vec_b)
+        PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, true, DBUF, HA>), dim3((unsigned)grid), dim3(NT_),
+                           0, ppo::stream(), a);
+    else
+        PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, false, DBUF, HA>), dim3((unsigned)grid), dim3(NT_),
+                           0, ppo::stream(), a);
+    PPO_LAUNCH_CHECK();
+}
+
 template <int OP, int BM, int BN, int WARPS_M, int BK, bool DBUF>
 void launch(Args a) {
     a.tiles_m = ppo_divup(a.M, BM);
@@ -599,16 +615,14 @@ void launch(Args a) {
     const long grid = (long)a.tiles_m * a.tiles_n * a.splits;
     PPO_REQUIRE(grid > 0 && grid < (1L << 31), "gemm: grid out of range");
     if constexpr (OP != OP_TN) {
-        if (a.tanh) {                      // the tanh epilogue's own kernels (gemm_tile TH)
-            if (a.vec_a && a.vec_b)
-                PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, true, DBUF, true>), dim3((unsigned)grid),
-                                   dim3(NT_), 0, ppo::stream(), a);
-            else
-                PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, false, DBUF, true>), dim3((unsigned)grid),
-                                   dim3(NT_), 0, ppo::stream(), a);
-            PPO_LAUNCH_CHECK();
-            return;
+        switch (a.hact) {
+        case 0: break;
+        case PHIP_ACT_TANH: launch_hact<OP, BM, BN, WARPS_M, BK, DBUF, PHIP_ACT_TANH>(a, grid); return;
+        case PHIP_ACT_ELU: launch_hact<OP, BM, BN, WARPS_M, BK, DBUF, PHIP_ACT_ELU>(a, grid); return;
+        default: PPO_REQUIRE(false, "gemm: unknown h-derived activation kind");
         }
+    } else {
+        PPO_REQUIRE(!a.hact, "gemm: grad_W takes no activation");
     }
     if (a.vec_a && a.vec_b)
         PPO_TIMED_LAUNCH((gemm_f32_kernel<OP, BM, BN, WARPS_M, BK, true, DBUF>), dim3((unsigned)grid), dim3(NT_),
@@ -691,7 +705,7 @@ void fwd(float* y, const float* x, const float* W, const float* b, int m, int n,
     a.ridx = ridx; a.acopy = acopy;
     a.A = x; a.lda = n; a.B = W; a.ldb = n; a.C = y; a.ldc = l;
     a.M = m; a.N = l; a.K = n; a.kchunk = n; a.splits = 1;
-    a.bias = b; a.tanh = act == PHIP_ACT_TANH; a.relu = act != 0 && !a.tanh;
+    a.bias = b; a.hact = (act == PHIP_ACT_TANH || act == PHIP_ACT_ELU) ? act : 0; a.relu = act != 0 && !a.hact;
     a.bits_out = a.relu ? bits : nullptr; a.wpr = ppo_divup(l, 32);
     a.vec_a = (n % 4 == 0) && aligned16(x);             // kcont, extent K = n
     a.vec_b = (n % 4 == 0) && aligned16(W);
@@ -704,13 +718,15 @@ void fwd(float* y, const float* x, const float* W, const float* b, int m, int n,
     launch_cfg<OP_NT>(cfg < 0 ? pick_cfg(OP_NT, m, l) : cfg, a);
 }
 
-// hpost: a tanh layer's post-activation [m, n] (then mask and bits are null): gx = acc − (acc·h)·h
+// hpost: a tanh or ELU layer's post-activation [m, n] (then mask and bits are null) and hkind its kind:
+// gx = acc − (acc·h)·h or h > 0 ? acc : acc·(h + 1)
 Args bwd_x_args(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m, int n,
-                int l, const float* hpost = nullptr) {
+                int l, const float* hpost = nullptr, int hkind = PHIP_ACT_TANH) {
+    PPO_REQUIRE(!hpost || hkind == PHIP_ACT_TANH || hkind == PHIP_ACT_ELU, "gemm grad_x: h of an unknown activation kind");
     Args a{};
     a.A = g; a.lda = l; a.B = W; a.ldb = n; a.C = gx; a.ldc = n;
     a.M = m; a.N = n; a.K = l; a.kchunk = l; a.splits = 1;
-    a.mask = hpost ? hpost : mask; a.ldmask = n; a.tanh = hpost != nullptr;
+    a.mask = hpost ? hpost : mask; a.ldmask = n; a.hact = hpost ? hkind : 0;
     a.bits_in = hpost ? nullptr : bits; a.wpr = ppo_divup(n, 32);
     a.vec_a = (l % 4 == 0) && aligned16(g);             // kcont, extent K = l
     a.vec_b = (n % 4 == 0) && aligned16(W);             // mncont, extent N = n, ld = n
@@ -718,8 +734,8 @@ Args bwd_x_args(float* gx, const float* g, const float* W, const float* mask, co
 }
 
 void bwd_x(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits, int m, int n, int l,
-           int cfg, const float* hpost = nullptr) {
-    const Args a = bwd_x_args(gx, g, W, mask, bits, m, n, l, hpost);
+           int cfg, const float* hpost = nullptr, int hkind = PHIP_ACT_TANH) {
+    const Args a = bwd_x_args(gx, g, W, mask, bits, m, n, l, hpost, hkind);
     if (cfg < 0 && g_force_cfg < 0 && use_smallm(m, l, n)) {
         launch_smallm<OP_NN>(a, a.vec_a);
         return;
@@ -857,16 +873,16 @@ void phip_linear_fwd_gather(float* y, const float* x, const int* ridx, float* xc
 }
 
 void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits,
-                            const float* h, int m, int n, int l) {
+                            const float* h, int hkind, int m, int n, int l) {
     if (m <= 0 || n <= 0) return;
     PPO_REQUIRE(gx && g && W && l > 0, "phip_linear_bwd_x: null operand");
-    PPO_REQUIRE(!h || (!mask && !bits), "phip_linear_bwd_x: a tanh layer's h excludes a ReLU mask");
+    PPO_REQUIRE(!h || (!mask && !bits), "phip_linear_bwd_x: a tanh or ELU layer's h excludes a ReLU mask");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(1, 0, m, n, l));
-    bwd_x(gx, g, W, mask, bits, m, n, l, -1, h);
+    bwd_x(gx, g, W, mask, bits, m, n, l, -1, h, hkind);
 }
 
 void phip_linear_bwd_x(float* gx, const float* g, const float* W, const float* mask, int m, int n, int l) {
-    phip_linear_bwd_x_bits(gx, g, W, mask, nullptr, nullptr, m, n, l);
+    phip_linear_bwd_x_bits(gx, g, W, mask, nullptr, nullptr, 0, m, n, l);
 }
 
 void phip_linear_bwd_w_ex(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed) {
@@ -904,8 +920,8 @@ int ppo_gemm_tune(int force_cfg, int splitk_target) {
 }
 
 // Tuning / roofline utility: average device time (µs) of one launch of `op` (0 fwd + ReLU, 1 grad_x,
-// 2 grad_W, 3 fwd without activation, 6 fwd + tanh, 7 grad_x with a tanh layer's h operand) at the given
-// shape, measured with HIP events on libppo's stream.
+// 2 grad_W, 3 fwd without activation, 6 fwd + tanh, 7 grad_x with a tanh layer's h operand, 8 fwd + ELU,
+// 9 grad_x with an ELU layer's h operand) at the given shape, measured with HIP events on libppo's stream.
 double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
     ppo::ensure_device();
     const size_t sx = (size_t)m * n, sw = (size_t)l * n, sy = (size_t)m * l;
@@ -918,7 +934,8 @@ double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
     phip_fill_uniform(W, (long)sw, 2, -0.1f, 0.1f);
     phip_fill_uniform(y, (long)(sy > sx ? sy : sx), 3, -1.f, 1.f);
     phip_fill_uniform(b, (long)(l > n ? l : n), 4, -0.1f, 0.1f);
-    float* hp = op == 7 ? (float*)phip_malloc(sizeof(float) * sx) : nullptr;    // a tanh layer's post-activation
+    // a tanh / ELU layer's post-activation (ELU's lies in (−1, ∞): the same fill serves both)
+    float* hp = (op == 7 || op == 9) ? (float*)phip_malloc(sizeof(float) * sx) : nullptr;
     if (hp) phip_fill_uniform(hp, (long)sx, 5, -1.f, 1.f);
     auto run = [&]() {
         if (op == 0) fwd(y, x, W, b, m, n, l, 1, nullptr, cfg);
@@ -926,6 +943,8 @@ double ppo_bench_gemm(int op, int m, int n, int l, int iters, int cfg) {
         else if (op == 1) bwd_x(x, y, W, nullptr, nullptr, m, n, l, cfg);
         else if (op == 6) fwd(y, x, W, b, m, n, l, PHIP_ACT_TANH, nullptr, cfg);     // forward + tanh
         else if (op == 7) bwd_x(x, y, W, nullptr, nullptr, m, n, l, cfg, hp);         // grad_x with the h read
+        else if (op == 8) fwd(y, x, W, b, m, n, l, PHIP_ACT_ELU, nullptr, cfg);      // forward + ELU
+        else if (op == 9) bwd_x(x, y, W, nullptr, nullptr, m, n, l, cfg, hp, PHIP_ACT_ELU);   // ELU′ through h
         else bwd_w(gw, b, y, x, m, n, l, 0, cfg);
     };
     for (int i = 0; i < 3; ++i) run();

@@ -6,7 +6,8 @@
 //   grad_x    gx = (g·W) ⊙ 1[y_prev > 0]                                                   NN
 //   grad_W    gW = gᵀ·x, gb = Σ_rows g      (split-K over the batch, f32 atomics)          TN
 // and tanh layers (not in the reference): forward y = tanhf(x·Wᵀ + b), no bits; grad_x gx = a − (a·h)·h, a = g·W,
-// h the layer below's stored post-activation read at gx's own coordinates (the TH kernels).
+// h the layer below's stored post-activation read at gx's own coordinates; and ELU layers (α = 1) the same way:
+// forward y = z > 0 ? z : expm1f(z), grad_x gx = h > 0 ? a : a·(h + 1) (the HA kernels, one set per kind).
 //
 // Arithmetic.  Every fp32 operand value splits exactly into three bf16 planes x = x0 + x1 + x2
 // (round-to-nearest v_cvt_pk_bf16_f32 of x, of the residual, of the second residual: x0 carries 8
@@ -54,9 +55,10 @@ struct X3Args {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
     const float* bias; int relu;
-    int tanh;                             // forward: tanhf after the bias (relu = 0, no bits); uniform over a launch
-    const float* hpost;                   // grad_x: a tanh layer's post-activation [M][ldc], read at C's own
-                                          // coordinates — C = acc − (acc·h)·h (null: none)
+    int hact;                             // 0, PHIP_ACT_TANH or PHIP_ACT_ELU, uniform over a launch.  Forward: that
+                                          // activation after the bias (relu = 0, no bits); grad_x: the kind of hpost
+    const float* hpost;                   // grad_x: a tanh / ELU layer's post-activation [M][ldc], read at C's own
+                                          // coordinates — C = hact_bwd(acc, h) (null: none, hact = 0)
     const int* ridx; float* acopy;        // forward: fused gather of A's rows + the gathered copy
     unsigned* bits_out; const unsigned* bits_in; int wpr;
     float* gbias;                         // grad_W: bias gradient (Σ over the batch of g)
@@ -344,9 +346,10 @@ struct StageX3 {
 // loop version of their own, grad_x's mask words brought into LDS (BM·BN/32 words, free on entry) by
 // one coalesced pass (they were 16 dependent loads per block).  Element stores in the accumulator
 // layout (each wave store: two 128-B row segments).
-// TH: the tanh forms (forward: tanhf after the bias, no bits; grad_x: acc − (acc·h)·h, a block's 16 h values loaded
-// as one batch ahead of its stores) — kernels of their own (launch_x3), never with the value-head fold.
-template <int OP, int BM, int BN, int TM, int TN, int NTH, bool YD = false, bool FG = false, bool TH = false>
+// HA (0, PHIP_ACT_TANH, PHIP_ACT_ELU): the h-derived forms (forward: ppo::hact_fwd<HA> after the bias, no bits;
+// grad_x: ppo::hact_bwd<HA>(acc, h), a block's 16 h values loaded once, as one batch ahead of its stores, whichever
+// kind reads them) — kernels of their own per kind (launch_x3), never with the value-head fold.
+template <int OP, int BM, int BN, int TM, int TN, int NTH, bool YD = false, bool FG = false, int HA = 0>
 __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[TM][TN], unsigned short* lds, int m0,
                                                 int n0, int wm, int wn, int tid) {
     constexpr int WM = TM * 32, WN = TN * 32;
@@ -427,7 +430,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                 const bool col_ok = col < a.N;
                 unsigned word = 0;
                 float hv[16];
-                if constexpr (TH && OP == OP_NN) {             // clamped into [M, N): every load is in bounds
+                if constexpr (HA != 0 && OP == OP_NN) {        // clamped into [M, N): every load is in bounds
                     const int colc = col_ok ? col : a.N - 1;
 #pragma unroll
                     for (int e = 0; e < 16; ++e)
@@ -443,7 +446,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                     float* dst = a.C + (long)row * a.ldc + col;
                     if (OP == OP_NT) {
                         v += bcol[j];
-                        if constexpr (TH) v = tanhf(v);
+                        if constexpr (HA != 0) v = ppo::hact_fwd<HA>(v);
                         else if (a.relu) v = v > 0.f ? v : 0.f;
                         if (ok) *dst = v;
                         if constexpr (YD) yp[e] += v * wcol[j];
@@ -455,7 +458,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                     } else {
                         if (FG) v *= gsh[lr0 + dr];
                         if (masked && !((mk[(lr0 + dr) * WPT + ((c0 - n0) >> 5)] >> r) & 1u)) v = 0.f;
-                        if constexpr (TH) v = ppo::tanh_bwd(v, hv[e]);
+                        if constexpr (HA != 0) v = ppo::hact_bwd<HA>(v, hv[e]);
                         if (ok) *dst = v;
                     }
                 }
@@ -467,14 +470,14 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
             if constexpr (YD) ydot_block(yp, i);
         }
     };
-    if (!TH && OP == OP_NT && a.bits_out) body(std::true_type{});
+    if (HA == 0 && OP == OP_NT && a.bits_out) body(std::true_type{});
     else body(std::false_type{});
 }
 
 // FOLD: the value-head fold variant (forward: ydot / ypart; grad_x / grad_W: A synthesised from h).
 // The body of one workgroup (block b of a grid of `grid` blocks), a device function so that one launch
 // could run several products' tiles (a grad_W + grad_x pair was measured and not kept, see phip_x3_bwd_w)
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, int HA = 0>
 __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
     constexpr int NTG = NTH / KG;                                  // threads per k-group
     constexpr int NW = NTG / 64, WARPS_N = NW / WARPS_M;
@@ -867,7 +870,7 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
 
     if constexpr (OP != OP_TN) {
         static_assert(BM * (BN / 32 + 1) * 4 <= KG * NS * BUF * 2, "x3 epilogue: mask words exceed LDS");
-        x3_epilogue_out<OP, BM, BN, TM, TN, NTH, OP == OP_NT && FOLD != 0, OP == OP_NN && FOLD != 0, TH>(
+        x3_epilogue_out<OP, BM, BN, TM, TN, NTH, OP == OP_NT && FOLD != 0, OP == OP_NN && FOLD != 0, HA>(
             a, acc, lds, m0, n0, wm, wn, tid);
         return;
     }
@@ -931,24 +934,28 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         }
 }
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, int HA = 0>
 __global__ __launch_bounds__(NTH, OCC) void gemm_x3_kernel(X3Args a) {
-    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,TH>(a, (int)blockIdx.x, (int)gridDim.x);
+    static_assert(HA == 0 || (OP != OP_TN && FOLD == 0), "h-derived activation epilogues: plain forward and grad_x only");
+    x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB, HA>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
 int g_x3_last_slots = 0;                 // the last launch's ypart slots (tiles_n × waves along N)
 
-template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, bool TH = false>
+template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOLD = 0, int KB = BK, int HA = 0>
 void launch_x3(X3Args a) {
-    // a tanh launch (forward: a.tanh; grad_x: a.hpost) runs the TH kernels — the tanh epilogue compiled apart, so
-    // the ReLU / identity kernels keep the registers they had (x3_epilogue_out)
-    if constexpr (!TH && OP != OP_TN && FOLD == 0) {
-        if (OP == OP_NT ? a.tanh != 0 : a.hpost != nullptr) {
-            launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,true>(a);
-            return;
+    // a tanh / ELU launch (a.hact; grad_x: with a.hpost) runs that kind's HA kernels — the h-derived epilogues
+    // compiled apart, so the ReLU / identity kernels keep the registers they had (x3_epilogue_out)
+    if constexpr (HA == 0 && OP != OP_TN && FOLD == 0) {
+        switch (a.hact) {
+        case 0: break;
+        case PHIP_ACT_TANH: launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB, PHIP_ACT_TANH>(a); return;
+        case PHIP_ACT_ELU: launch_x3<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB, PHIP_ACT_ELU>(a); return;
+        default: PPO_REQUIRE(false, "gemm_x3: unknown h-derived activation kind");
         }
     }
-    PPO_REQUIRE(TH || (!a.tanh && !a.hpost), "gemm_x3: tanh operands on a variant without the tanh epilogue");
+    PPO_REQUIRE(a.hact == HA && (a.hpost != nullptr) == (HA != 0 && OP == OP_NN),
+                "gemm_x3: tanh / ELU operands on a variant without that epilogue");
     a.tiles_m = ppo_divup(a.M, BM);
     a.tiles_n = ppo_divup(a.N, BN);
     g_x3_last_slots = a.tiles_n * (NTH / KG / 64 / WARPS_M);
@@ -976,7 +983,7 @@ void launch_x3(X3Args a) {
             a.vh_ypart = nullptr;
         }
     }
-    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB,TH>;
+    auto kern = gemm_x3_kernel<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB, HA>;
     if (lds > 64 * 1024) {
         static bool attr = false;                      // once per instantiation (the whole LDS)
         if (!attr) {
@@ -1152,13 +1159,14 @@ int phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, c
     if (m <= 0 || l <= 0) return 0;
     PPO_REQUIRE(y && x && W && n > 0 && n % 4 == 0 && al16(x) && al16(W), "phip_x3_fwd: unsupported operands");
     PPO_REQUIRE(!ydot || ypart, "phip_x3_fwd: value-head fold without its partial buffer");
-    PPO_REQUIRE(!ydot || act != PHIP_ACT_TANH, "phip_x3_fwd: the value-head fold takes a ReLU layer only");
-    const int relu = act != 0 && act != PHIP_ACT_TANH;       // any other nonzero value: ReLU, as `relu != 0` was
+    const int hact = (act == PHIP_ACT_TANH || act == PHIP_ACT_ELU) ? act : 0;
+    PPO_REQUIRE(!ydot || !hact, "phip_x3_fwd: the value-head fold takes a ReLU layer only");
+    const int relu = act != 0 && !hact;                      // any other nonzero value: ReLU, as `relu != 0` was
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(0, 1, m, n, l));
     X3Args a{};
     a.A = x; a.lda = n; a.B = W; a.ldb = n; a.C = y; a.ldc = l;
     a.M = m; a.N = l; a.K = n; a.kchunk = n; a.splits = 1;
-    a.bias = b; a.relu = relu; a.tanh = act == PHIP_ACT_TANH; a.ridx = ridx; a.acopy = ridx ? xcopy : nullptr;
+    a.bias = b; a.relu = relu; a.hact = hact; a.ridx = ridx; a.acopy = ridx ? xcopy : nullptr;
     a.bits_out = relu ? bits : nullptr; a.wpr = ppo_divup(l, 32);
     a.ydot = ydot; a.ypart = ypart;
     launch_cfg_x3<OP_NT>(pick_x3(m, l, OP_NT), a);
@@ -1173,20 +1181,22 @@ void phip_x3_fwd(float* y, const float* x, const int* ridx, float* xcopy, const 
 // the upper layer's gradient A = g [m, l]; value-head fold (fold_g): A = the 0/1 mask words of h
 // (fold_bits [m][⌈l/32⌉]), W scaled per k-row by the output weights fold_w as it is staged (diag(w)·W), the
 // product scaled by fold_g per row — grad_x = diag(g)·(mask·diag(w)·W) ⊙ the input mask
-// hpost (without the fold only): a tanh layer below's post-activation [m, n] — gx = acc − (acc·h)·h
+// hpost (without the fold only): a tanh or ELU layer below's post-activation [m, n], hkind its kind —
+// gx = acc − (acc·h)·h or h > 0 ? acc : acc·(h + 1)
 static void x3_bwd_x(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
-                     const float* W, const unsigned* bits, const float* hpost, int m, int n, int l) {
+                     const float* W, const unsigned* bits, const float* hpost, int hkind, int m, int n, int l) {
     if (m <= 0 || n <= 0) return;
     PPO_REQUIRE(gx && (g || fold_bits) && W && l > 0 && l % 4 == 0 && n % 4 == 0 && (!g || al16(g)) && al16(W),
                 "phip_x3_bwd_x: unsupported operands");
     PPO_REQUIRE(!fold_bits || (fold_g && fold_w), "phip_x3_bwd_x: value-head fold operands");
-    PPO_REQUIRE(!hpost || (!fold_bits && !bits), "phip_x3_bwd_x: a tanh layer's h excludes a ReLU mask and the fold");
+    PPO_REQUIRE(!hpost || (!fold_bits && !bits), "phip_x3_bwd_x: a tanh or ELU layer's h excludes a ReLU mask and the fold");
+    PPO_REQUIRE(!hpost || hkind == PHIP_ACT_TANH || hkind == PHIP_ACT_ELU, "phip_x3_bwd_x: h of an unknown activation kind");
     ppo::ProfScope ps(PPO_K_GEMM, 2.0 * m * n * l, ppo::gemm_key(1, 1, m, n, l));
     X3Args a{};
     a.A = fold_bits ? W : g; a.lda = l; a.B = W; a.ldb = n; a.C = gx; a.ldc = n;
     a.M = m; a.N = n; a.K = l; a.kchunk = l; a.splits = 1;
     a.bits_in = bits; a.wpr = ppo_divup(n, 32);
-    a.hpost = hpost;
+    a.hpost = hpost; a.hact = hpost ? hkind : 0;
     a.fold_bits = fold_bits; a.fold_wpr = ppo_divup(l, 32); a.fold_g = fold_g; a.fold_w = fold_w;
     ppo::PendingReduce& pr = ppo::g_pending[phip_side_active() ? 1 : 0];
     if (pr.on) {
@@ -1199,12 +1209,12 @@ static void x3_bwd_x(float* gx, const float* g, const unsigned* fold_bits, const
 
 void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
                         const float* W, const unsigned* bits, int m, int n, int l) {
-    x3_bwd_x(gx, g, fold_bits, fold_g, fold_w, W, bits, nullptr, m, n, l);
+    x3_bwd_x(gx, g, fold_bits, fold_g, fold_w, W, bits, nullptr, 0, m, n, l);
 }
 
-void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int m, int n,
-                   int l) {
-    x3_bwd_x(gx, g, nullptr, nullptr, nullptr, W, bits, h, m, n, l);
+void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int hkind, int m,
+                   int n, int l) {
+    x3_bwd_x(gx, g, nullptr, nullptr, nullptr, W, bits, h, hkind, m, n, l);
 }
 
 void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
@@ -1315,7 +1325,7 @@ int ppo_gemm_x3_tune(int force_cfg, int splitk_target) {
 // average device µs of one launch (op 0 forward + bias + ReLU + bits, 1 grad_x with bits, 2 grad_W
 // + bias grad (split-K from zero), 3 forward without activation, 4 – 6 the value-head fold variants of
 // 0 – 2, 7 grad_x with a tanh layer's h operand, 8 forward + bias + tanh — ppo_bench_gemm's 6, which the fold
-// holds here); cfg −1 = automatic
+// holds here — 9 forward + bias + ELU, 10 grad_x with an ELU layer's h operand); cfg −1 = automatic
 double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int splitk_target) {
     ppo::ensure_device();
     const size_t sx = (size_t)m * n, sw = (size_t)l * n, sy = (size_t)m * l;
@@ -1335,16 +1345,19 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
     g_split_x3 = splitk_target;
     // ops 4 – 6: the value-head fold variants (forward with the partial dots; grad_x from the mask words
     // with the g row scale; grad_W from h with g / w scales and the output layer's gW)
-    float* hp = op == 7 ? (float*)phip_malloc(4 * sx) : nullptr;          // a tanh layer's post-activation [m, n]
+    // a tanh / ELU layer's post-activation [m, n] (ELU's lies in (−1, ∞): the same fill serves both)
+    float* hp = (op == 7 || op == 10) ? (float*)phip_malloc(4 * sx) : nullptr;
     if (hp) phip_fill_uniform(hp, (long)sx, 6, -1.f, 1.f);
     float* fold = (op >= 4 && op <= 6) ? (float*)phip_malloc(4 * ((size_t)m * (2 * ppo_divup(l, 64) + 1) + (size_t)l)) : nullptr;
     if (fold) phip_fill_uniform(fold, (long)m * (2 * ppo_divup(l, 64) + 1) + l, 5, -0.1f, 0.1f);
     auto run = [&]() {
         if (op == 0) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits);
         else if (op == 3) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, 0, nullptr);
-        else if (op == 1) phip_x3_bwd_x(x, y, W, bits, nullptr, m, n, l);
-        else if (op == 7) phip_x3_bwd_x(x, y, W, nullptr, hp, m, n, l);
+        else if (op == 1) phip_x3_bwd_x(x, y, W, bits, nullptr, 0, m, n, l);
+        else if (op == 7) phip_x3_bwd_x(x, y, W, nullptr, hp, PHIP_ACT_TANH, m, n, l);
         else if (op == 8) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, PHIP_ACT_TANH, nullptr);
+        else if (op == 9) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, PHIP_ACT_ELU, nullptr);
+        else if (op == 10) phip_x3_bwd_x(x, y, W, nullptr, hp, PHIP_ACT_ELU, m, n, l);
         else if (op == 4) phip_x3_fwd_vhead(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits, fold, fold + l);
         else if (op == 5) phip_x3_bwd_x_fold(x, nullptr, bits, fold, fold + m, W, bits, m, n, l);
         else if (op == 6) phip_x3_bwd_w_fold(gw, b, y, fold, fold + m, fold + m + l, x, m, n, l, 0);

@@ -63,8 +63,10 @@ typedef struct {
 /* ---------------- dense layers (gemm.hip) ---------------- */
 /* activation kinds of the forward launchers' `act` argument (host: nn_act_kind); the value is uniform over a
  * launch.  PHIP_ACT_TANH applies tanhf after the bias and writes no mask bits: tanh′ = 1 − h² needs only the
- * stored post-activation h, which the grad_x launchers take as their `h` operand */
-enum { PHIP_ACT_NONE = 0, PHIP_ACT_RELU = 1, PHIP_ACT_TANH = 2 };
+ * stored post-activation h, which the grad_x launchers take as their `h` operand with its kind `hkind`.
+ * PHIP_ACT_ELU (α = 1) is the second such h-derived kind: h = z > 0 ? z : expm1f(z), and ELU′ = h > 0 ? 1 : h + 1.
+ * Kinds above PHIP_ACT_RELU are the h-derived ones (no bits, no stored pre-activation) */
+enum { PHIP_ACT_NONE = 0, PHIP_ACT_RELU = 1, PHIP_ACT_TANH = 2, PHIP_ACT_ELU = 3 };
 /* y[m,l] = act(x[m,n]·W[l,n]ᵀ + b[l]) (mat_mul.cu:132-163 + K1/K5 fused) */
 void phip_linear_fwd(float* y, const float* x, const float* W, const float* b, int m, int n, int l, int act);
 /* same, and (act = relu) writes the ReLU′ mask as bits: word (row, c/32) bit c%32 = y[row, c] > 0,
@@ -77,11 +79,11 @@ void phip_linear_bwd_x(float* gx, const float* g, const float* W, const float* m
  * rows are also written to xcopy[m, n] (for the layer's grad_W) when xcopy != NULL */
 void phip_linear_fwd_gather(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b,
                             int m, int n, int l, int act, unsigned* bits);
-/* same with the mask given as bits (phip_linear_fwd_bits layout, ⌈n/32⌉ words per row); or, for a tanh
- * layer below, h [m, n] (ld = n) its stored post-activation: gx = acc − (acc·h)·h in fp32 (mask and bits
- * are then NULL) */
+/* same with the mask given as bits (phip_linear_fwd_bits layout, ⌈n/32⌉ words per row); or, for a tanh or ELU
+ * layer below, h [m, n] (ld = n) its stored post-activation and hkind its PHIP_ACT_* kind: gx = acc − (acc·h)·h
+ * (tanh) or h > 0 ? acc : acc·(h + 1) (ELU) in fp32 (mask and bits are then NULL; hkind is ignored without h) */
 void phip_linear_bwd_x_bits(float* gx, const float* g, const float* W, const float* mask, const unsigned* bits,
-                            const float* h, int m, int n, int l);
+                            const float* h, int hkind, int m, int n, int l);
 /* gW[l,n] = g[m,l]ᵀ·x[m,n] and gb[l] = Σ_m g[m,l] (K4 + K7 fused); overwrites */
 void phip_linear_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l);
 /* same, with gW/gb already zero on entry when `zeroed` (one memset per backward instead of two per layer) */
@@ -111,10 +113,11 @@ void phip_x3_fwd(float* y, const float* x, const int* ridx, float* xcopy, const 
 /* the next phip_x3_bwd_w(_fold) leaves its split-K slab reduce to the next phip_x3_bwd_x(_fold) on the same
  * stream (extra workgroups of that launch) — the caller guarantees grad_x follows */
 void phip_x3_defer_reduce(int on);
-/* bits: the ReLU′ mask of the layer below (NULL: none); h: a tanh layer below's post-activation [m, n], read
- * at gx's own coordinates — gx = acc − (acc·h)·h (NULL: none) */
-void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int m, int n,
-                   int l);
+/* bits: the ReLU′ mask of the layer below (NULL: none); h: a tanh or ELU layer below's post-activation [m, n],
+ * read at gx's own coordinates, hkind its PHIP_ACT_* kind — gx = acc − (acc·h)·h or h > 0 ? acc : acc·(h + 1)
+ * (NULL: none, hkind ignored) */
+void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int hkind, int m,
+                   int n, int l);
 void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed);
 /* value-head fold (nn_value_fold_step): forward partial y dots (returns ypart slots); backward with the
  * upper gradient g·w·1[h > 0] applied as the 0/1 mask of h with g, w as row / column scales (grad_x:
@@ -235,6 +238,9 @@ void phip_relu_bwd(const float* y, float* g, long count);
 /* x ← tanhf(x); g ← g − (g·y)·y with y the post-activation (tanh′ = 1 − y²) */
 void phip_tanh(float* x, long count);
 void phip_tanh_bwd(const float* y, float* g, long count);
+/* x ← ELU(x), α = 1; g ← y > 0 ? g : g·(y + 1) with y the post-activation (ELU′ = y + 1 where y ≤ 0) */
+void phip_elu(float* x, long count);
+void phip_elu_bwd(const float* y, float* g, long count);
 /* y += x (host-pointer API: the reference's CPU backward accumulates, mat_mul.cu:67,79) */
 void phip_axpy(float* y, const float* x, long count);
 /* d_loss[0] = Σ(t−y)²/count (written), d_loss_accum[0] += same (if non-NULL);

@@ -87,6 +87,26 @@ void Tanh_derivative(float* x, float* grad, int m, int n) {
     phip_d2h(grad, dg, sizeof(float) * cnt);
 }
 
+/* ELU, α = 1 (no counterpart in the reference): x ← x > 0 ? x : expm1f(x); grad ← x > 0 ? grad : grad·(x + 1),
+ * x the post-activation */
+void ELU_cuda(float* x, int m, int n) { phip_elu(x, (long)m * n); }
+void ELU_derivative_cuda(float* x, float* grad, int m, int n) { phip_elu_bwd(x, grad, (long)m * n); }
+
+void ELU(float* x, int m, int n) {
+    const size_t cnt = (size_t)m * n;
+    float* d = stage_up(ST_A, x, cnt);
+    phip_elu(d, (long)cnt);
+    phip_d2h(x, d, sizeof(float) * cnt);
+}
+
+void ELU_derivative(float* x, float* grad, int m, int n) {
+    const size_t cnt = (size_t)m * n;
+    float* dx = stage_up(ST_A, x, cnt);
+    float* dg = stage_up(ST_B, grad, cnt);
+    phip_elu_bwd(dx, dg, (long)cnt);
+    phip_d2h(grad, dg, sizeof(float) * cnt);
+}
+
 static ActivationFunction* build(const char* name, int device) {
     ActivationFunction* a = (ActivationFunction*)xmalloc(sizeof(ActivationFunction));
     if (name && strcmp(name, "relu") == 0) {
@@ -95,6 +115,9 @@ static ActivationFunction* build(const char* name, int device) {
     } else if (name && strcmp(name, "tanh") == 0) {
         a->activation = device ? &Tanh_cuda : &Tanh;
         a->activation_derivative = device ? &Tanh_derivative_cuda : &Tanh_derivative;
+    } else if (name && strcmp(name, "elu") == 0) {
+        a->activation = device ? &ELU_cuda : &ELU;
+        a->activation_derivative = device ? &ELU_derivative_cuda : &ELU_derivative;
     } else {                      /* any other name: identity (activation_function.cu:46-73) */
         a->activation = NULL;
         a->activation_derivative = NULL;

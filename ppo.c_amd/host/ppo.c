@@ -489,7 +489,7 @@ static const int* next_perm(PPO* ppo, PPODev* d, int shuffle_mode, uint64_t* key
 static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
     const int L = nn->num_layers - 1;
     if (nn->dtype != 0 || L < 1 || L > 8 || !adam_owns(adam, nn->d_params, nn->d_grads)) return -1;
-    if (nn_has_tanh(nn)) return -1;      /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
+    if (nn_has_hact(nn)) return -1;     /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
     for (int i = 0; i < L; i++)
         if (nn->layers[i].input_size > max_w || nn->layers[i].output_size > max_w) return -1;
     long nw = 0;
@@ -3052,8 +3052,8 @@ PPO* load_ppo(const char* filename, bool use_cuda) {
 int ppo_set_compute_dtype(void* vppo, int dtype) {
     PPO* ppo = (PPO*)vppo;
     if (!ppo) return -1;
-    /* bf16 mode knows ReLU and identity: a tanh layer in either network declines it, both left as they were */
-    if (dtype == 1 && (nn_has_tanh(ppo->V) || nn_has_tanh(ppo->policy->mu))) return -1;
+    /* bf16 mode knows ReLU and identity: a tanh or ELU layer in either network declines it, both left as they were */
+    if (dtype == 1 && (nn_has_hact(ppo->V) || nn_has_hact(ppo->policy->mu))) return -1;
     /* … and the categorical head reads fp32 logits: bf16 mode is declined while it is on */
     if (dtype == 1 && (cat_on((PPODev*)ppo->dev) || half_on((PPODev*)ppo->dev))) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;

@@ -279,6 +279,10 @@ _SIGS = {
     "Tanh_derivative": (None, [_P, _P, C.c_int, C.c_int]),
     "Tanh_cuda": (None, [_P, C.c_int, C.c_int]),
     "Tanh_derivative_cuda": (None, [_P, _P, C.c_int, C.c_int]),
+    "ELU": (None, [_P, C.c_int, C.c_int]),
+    "ELU_derivative": (None, [_P, _P, C.c_int, C.c_int]),
+    "ELU_cuda": (None, [_P, C.c_int, C.c_int]),
+    "ELU_derivative_cuda": (None, [_P, _P, C.c_int, C.c_int]),
     "mean_squared_error": (C.c_float, [_P, _P, C.c_int, C.c_int]),
     "mean_squared_error_derivative": (None, [_P, _P, _P, C.c_int, C.c_int]),
     "mean_squared_error_cuda": (C.c_float, [_P, _P, C.c_int, C.c_int]),
@@ -314,6 +318,8 @@ _SIGS = {
     "adam_update": (None, [C.POINTER(Adam), C.c_float]),
     "free_adam": (None, [C.POINTER(Adam)]),
     # FILE* arguments: an opaque pointer from the C library's fopen
+    "save_neural_network": (None, [C.POINTER(NeuralNetwork), _P]),
+    "load_neural_network": (C.POINTER(NeuralNetwork), [_P]),
     "save_adam": (None, [C.POINTER(Adam), _P, C.c_bool]),
     "load_adam": (C.POINTER(Adam), [_P, C.POINTER(_P), C.POINTER(_P), c_int_p, C.c_bool]),
     "load_adam_from_nn": (C.POINTER(Adam), [_P, C.POINTER(NeuralNetwork), C.c_bool]),
