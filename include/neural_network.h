@@ -96,6 +96,11 @@ typedef struct {
     long   host_version_w;  /* dev_version the host weight mirrors last matched (a weights-only sync) */
     float* d_fold_ws;       /* value-head fold scratch (nn_value_fold_step): partial dots [slots][m] | g [m] */
     long   fold_ws_cap;     /* floats */
+    /* layer normalisation of the hidden layers (ppo_ext.h nn_set_layer_norm); nothing is allocated while it is off */
+    float  ln_eps;          /* 0 = off; otherwise the eps under the square root */
+    int    ln_cap_m;        /* rows the two blocks below can hold */
+    float* d_ln_z;          /* the hidden pre-activations z, one [ln_cap_m, size_{i+1}] block per hidden layer i */
+    float* d_ln_stat;       /* (mean, rstd) of every row, one [ln_cap_m, 2] block per hidden layer */
 } NeuralNetwork;
 
 typedef struct {

@@ -1027,6 +1027,43 @@ int ppo_orthogonal_device(float* d_W, int rows, int cols, float gain);
  * last forward, else 0. */
 int ppo_nn_input_rows(void* nn, float* out, int m);
 
+/* ---------------- layer normalisation of the hidden layers ----------------
+ * Not in the reference; off by default.  With it on, every hidden layer i < L − 1 of a network computes
+ *     z = x·Wᵀ + b,   mean = Σ_j z_j / l,   d_j = z_j − mean,   var = Σ_j d_j² / l   (biased, two passes; the fp32
+ *     evaluation subtracts (Σ_j d_j / l)², zero in exact arithmetic: the corrected two-pass algorithm),
+ *     rstd = 1 / sqrtf(var + eps),   ẑ_j = d_j·rstd,   h_j = act(ẑ_j)
+ * with the layer's own activation (none, relu, tanh, elu) — torch's LayerNorm(l, eps, elementwise_affine=False)
+ * between the linear layer and its activation, the `normalization: layer_norm` of rl_games and `layer_norm=True` of
+ * Brax's PPO without their learnable scale and shift (γ, β are not provided).  The output layer is never normalised.
+ * All of it is fp32 (csrc/layernorm.hip; DESIGN.md §4 "Layer normalisation" has the backward and the kernel design).
+ * eps > 0 turns it on, 0 turns it off.  nn_set_layer_norm sets one network, ppo_set_layer_norm μ and V together;
+ * ppo_get_layer_norm returns μ's eps (0: off).  They return 0, or −1 with nothing changed: a negative or non-finite
+ * eps, a network with no hidden layer or with a hidden width above 4096, or bf16 compute mode — and while it is on,
+ * nn_set_compute_dtype(nn, 1) and ppo_set_compute_dtype(ppo, 1) return −1.  Such a network takes the multi-launch
+ * update loop, as a tanh or ELU network does: the fused output heads, the wide output pass, the value fold, the
+ * single-workgroup / cluster phases and graph replay decline it.  ppo_save_state keeps the setting (a section of its
+ * own, written only while it is on); save_ppo / save_neural_network keep the reference's layout and do not: a caller
+ * who loads such a file sets it again.
+ * ppo_nn_ln_rows copies, for hidden layer `layer` of a NeuralNetwork*, the pre-activations z [m, size] and the rows'
+ * (mean, rstd) [m, 2] of the last device forward to the host (either may be NULL) — for parity tests; synchronises;
+ * −1 when the feature is off, the layer is not a hidden one, or m is beyond the last forward.
+ * The two _device entries run the kernels on the caller's device arrays (tests, and callers who build their own
+ * networks): forward z [m, l] → h [m, l], stat [m, 2]; backward d_g [m, l] = ∂loss/∂h rewritten in place into
+ * ∂loss/∂z from z, stat and (tanh, elu only; may be NULL otherwise) the stored h.  act: 0 none, 1 relu, 2 tanh,
+ * 3 elu.  On libppo's stream, no synchronisation.  They return −1, and launch nothing, for l outside 1 … 4096,
+ * m <= 0, an unknown kind, a NULL array or (forward) an eps that is not finite and positive. */
+int   nn_set_layer_norm(void* nn, float eps);            /* NeuralNetwork* */
+int   ppo_set_layer_norm(void* ppo, float eps);
+float ppo_get_layer_norm(void* ppo);
+int   ppo_nn_ln_rows(void* nn, int layer, float* z_out, float* stat_out, int m);
+int   ppo_layer_norm_fwd_device(const float* d_z, float* d_h, float* d_stat, int m, int l, int act, float eps);
+int   ppo_layer_norm_bwd_device(float* d_g, const float* d_z, const float* d_h, const float* d_stat, int m, int l,
+                                int act);
+/* average device µs of one launch over `iters` back-to-back launches between two events: op 0 = the forward kernel,
+ * 1 = the backward kernel, 2 = a device-to-device copy moving as many bytes as op `bytes_like` (0 or 1) does — the
+ * yardstick; *bytes_out (may be NULL) receives the bytes one launch moves.  −1 for a shape the kernels decline. */
+double ppo_bench_layer_norm(int op, int m, int l, int act, int iters, int bytes_like, double* bytes_out);
+
 /* ---------------- training-state checkpoints ----------------
  * save_ppo / load_ppo keep the reference's byte layout: five hyper-parameters, the two networks, log σ and the three
  * Adams.  ppo_save_state keeps THE WHOLE TRAINING STATE, so that a run stopped between two updates and resumed with
@@ -1082,7 +1119,8 @@ int   ppo_state_image(void* ppo, int flags, void* out, long cap);
  * master parameters / Adam / heads / GAE, bf16 storage of hidden activations and their gradients
  * (BASELINE config C5).  Returns 0, or −1 for an invalid dtype.  The bf16 kernels know ReLU and identity
  * layers only: dtype 1 on a network with a "tanh" or "elu" layer (for ppo_set_compute_dtype: in either network)
- * returns −1 and leaves the setting unchanged; such networks run in fp32 mode, on both fp32 GEMM engines.
+ * returns −1 and leaves the setting unchanged; such networks run in fp32 mode, on both fp32 GEMM engines.  The same
+ * holds while layer normalisation is on (ppo_set_layer_norm).
  * ppo_set_compute_dtype(ppo, 1) also returns −1 while the categorical policy is on (ppo_set_action_dist). */
 int ppo_set_compute_dtype(void* ppo, int dtype);
 int nn_set_compute_dtype(void* nn, int dtype);          /* NeuralNetwork* */

@@ -86,6 +86,40 @@ __device__ __forceinline__ float hact_bwd_rt(int ha, float a, float h) {
     return ha == PHIP_ACT_ELU ? elu_bwd(a, h) : tanh_bwd(a, h);
 }
 
+// ---- layer normalisation of one row of l pre-activations, no scale and no shift (layernorm.hip; DESIGN.md §4
+// "Layer normalisation"): the atoms, fp32, each one rounding per operation, in this order:
+//     mean = (Σ z_j) / l        d_j = z_j − mean        var = (Σ d_j²) / l − ((Σ d_j) / l)²     two passes, biased
+//     rstd = 1 / sqrtf(max(var, 0) + eps)               ẑ_j = d_j·rstd              h_j = act(ẑ_j)
+// The second term of var is the corrected two-pass algorithm (Chan, Golub, LeVeque): it is zero in exact arithmetic
+// and takes out the square of the fp32 mean's own rounding error, which a row of large, nearly equal values (1000 ±
+// 1e-3) would otherwise carry into rstd a hundred times over its rounding bound.
+// With g = ∂loss/∂h:  a_j = act′·g_j,  s1 = (Σ a_j) / l,  s2 = (Σ a_j·ẑ_j) / l,
+//     ∂loss/∂z_j = rstd·((a_j − s1) − ẑ_j·s2).
+// The backward forms ẑ with ln_zhat from the stored z, mean and rstd, as the forward does: the same bits, so
+// ẑ > 0 ⇔ h > 0 for ReLU.  The order of the sums is the kernel's; tests/layernorm_ref.py restates all of it.
+__device__ __forceinline__ float ln_mean(float sum, int l) { return sum / (float)l; }
+__device__ __forceinline__ float ln_rstd(float sqsum, float dsum, int l, float eps) {
+    const float c = dsum / (float)l;
+    return 1.0f / sqrtf(fmaxf(sqsum / (float)l - c * c, 0.f) + eps);
+}
+__device__ __forceinline__ float ln_zhat(float z, float mean, float rstd) { return (z - mean) * rstd; }
+__device__ __forceinline__ float ln_dz(float a, float zh, float s1, float s2, float rstd) {
+    return rstd * ((a - s1) - zh * s2);
+}
+// the activation behind the normalisation, by kind: ReLU reads ẑ itself, tanh and ELU the stored h (hact_bwd)
+template <int ACT>
+__device__ __forceinline__ float ln_act_fwd(float zh) {
+    if constexpr (ACT == PHIP_ACT_NONE) return zh;
+    else if constexpr (ACT == PHIP_ACT_RELU) return zh > 0.f ? zh : 0.f;
+    else return hact_fwd<ACT>(zh);
+}
+template <int ACT>
+__device__ __forceinline__ float ln_act_bwd(float g, float zh, float h) {
+    if constexpr (ACT == PHIP_ACT_NONE) return g;
+    else if constexpr (ACT == PHIP_ACT_RELU) return zh > 0.f ? g : 0.f;
+    else return hact_bwd<ACT>(g, h);
+}
+
 // Wave sum by the __shfl_xor butterfly (xor 32, 16, … 1): every lane gets the sum.  Not interchangeable with
 // wave_sum64 below, which adds in another order and gives other bits.
 __device__ __forceinline__ float wave_sum_xor(float v) {

@@ -241,6 +241,13 @@ void phip_tanh_bwd(const float* y, float* g, long count);
 /* x ← ELU(x), α = 1; g ← y > 0 ? g : g·(y + 1) with y the post-activation (ELU′ = y + 1 where y ≤ 0) */
 void phip_elu(float* x, long count);
 void phip_elu_bwd(const float* y, float* g, long count);
+/* layernorm.hip — layer normalisation of the rows of z [m, l], no scale or shift (dev.h ln_*): h = act(ẑ),
+ * ẑ = (z − mean)·rstd, stat[m, 2] = (mean, rstd) per row; and g [m, l] = ∂loss/∂h rewritten in place into ∂loss/∂z
+ * from z, stat and (tanh, ELU only; NULL otherwise) the stored h.  1 <= l <= 4096, act a PHIP_ACT_* kind
+ * (phip_ln_shape_ok); on the library's stream, no host synchronisation */
+int  phip_ln_shape_ok(int l, int act);
+void phip_ln_fwd(const float* z, float* h, float* stat, int m, int l, int act, float eps);
+void phip_ln_bwd(float* g, const float* z, const float* h, const float* stat, int m, int l, int act);
 /* y += x (host-pointer API: the reference's CPU backward accumulates, mat_mul.cu:67,79) */
 void phip_axpy(float* y, const float* x, long count);
 /* d_loss[0] = Σ(t−y)²/count (written), d_loss_accum[0] += same (if non-NULL);

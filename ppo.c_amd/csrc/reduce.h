@@ -55,6 +55,16 @@ __device__ __forceinline__ double wave_sum_xor_f64(double v) {
     return v;
 }
 
+// The same butterfly on one float per lane, over groups of W consecutive lanes (W = 64: the wave; W = 16: each
+// quarter-wave on its own, xor 8, 4, 2, 1): every lane gets its group's sum.  layernorm.hip's row sums.
+template <int W = 64>
+__device__ __forceinline__ float wave_sum_xor_f32(float v) {
+    static_assert(W == 64 || W == 16, "wave_sum_xor_f32: a wave or a quarter-wave");
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 // ---- runs, then a pairwise tree over the threads ---------------------------------------------------------------
 // The pairwise tree over s[0 … T) of a T-thread workgroup: stride 1, 2, 4, …, thread t, a multiple of 2·stride,
 // does s[t] = op(s[t], s[t + stride]).  Thread t has stored s[t]; every thread calls this and gets s[0].  NOT the

@@ -98,6 +98,7 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     /* … and the state-dependent-σ Gaussian, likewise: its section exists only while the distribution is 3 */
     const int with_sd = d->action_dist == 3;
     const int with_beta = d->action_dist == 4;       /* … and the Beta policy, likewise */
+    const int with_ln = ppo_get_layer_norm(ppo) > 0.f;   /* … and layer normalisation, while it is on */
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
@@ -105,9 +106,9 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
                      (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u) |
                      (with_klest ? CKPT_F_KLEST : 0u) | (with_sd ? CKPT_F_GAUSS_SD : 0u) |
-                     (with_beta ? CKPT_F_BETA : 0u));
+                     (with_beta ? CKPT_F_BETA : 0u) | (with_ln ? CKPT_F_LAYERNORM : 0u));
     put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv +
-                     (uint32_t)with_klest + (uint32_t)with_sd + (uint32_t)with_beta);
+                     (uint32_t)with_klest + (uint32_t)with_sd + (uint32_t)with_beta + (uint32_t)with_ln);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -253,6 +254,14 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_f32(&s, d->beta_zmax);
         put_u32(&s, 0);
         put_section(img, CKPT_TAG_BETA, &s);
+        free(s.p);
+    }
+
+    if (with_ln) {
+        memset(&s, 0, sizeof(s));
+        put_f32(&s, ppo_get_layer_norm(ppo));
+        put_u32(&s, 0);
+        put_section(img, CKPT_TAG_LAYERNORM, &s);
         free(s.p);
     }
     return 0;
@@ -467,6 +476,9 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
     if (ix->sec[CKPT_TAG_KLEST].present &&
         ppo_set_kl_estimator(ppo, (int)ckpt_rd32(img + ix->sec[CKPT_TAG_KLEST].off)) != 0)
         return "a KL estimator ppo_set_kl_estimator declines";
+    /* layer normalisation through its setter (the compute dtype is set by now: bf16 mode declines it) */
+    if (ix->sec[CKPT_TAG_LAYERNORM].present && ppo_set_layer_norm(ppo, ix->ln_eps) != 0)
+        return "a layer normalisation ppo_set_layer_norm declines";
     phip_sync();
     return NULL;
 }

@@ -68,6 +68,9 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
     if (((ix->flags & CKPT_F_BETA) != 0) != (s[CKPT_TAG_BETA].present != 0))
         return fail(ix, "the header's Beta-policy flag and its section disagree");
 
+    if (((ix->flags & CKPT_F_LAYERNORM) != 0) != (s[CKPT_TAG_LAYERNORM].present != 0))
+        return fail(ix, "the header's layer-normalisation flag and its section disagree");
+
     /* Legacy: five floats, then state size, action size, capacity */
     if (s[CKPT_TAG_LEGACY].len < 32) return fail_tag(ix, "shorter than the legacy header", CKPT_TAG_LEGACY);
     const uint8_t* lg = img + s[CKPT_TAG_LEGACY].off;
@@ -214,6 +217,16 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         if (!(zm > 0.f) || !(zm <= 3.4028234e38f)) return fail_tag(ix, "z_max not finite and positive", CKPT_TAG_BETA);
         ix->beta_zmax = zm;
     }
+
+    /* layer normalisation: written only while it is on, so a finite positive eps, and a zero word */
+    if (s[CKPT_TAG_LAYERNORM].present) {
+        if (s[CKPT_TAG_LAYERNORM].len != CKPT_LAYERNORM_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_LAYERNORM);
+        const uint8_t* ln = img + s[CKPT_TAG_LAYERNORM].off;
+        const float eps = rd_f32(ln);
+        if (!(eps > 0.f) || !(eps <= 3.4028234e38f)) return fail_tag(ix, "eps not finite and positive", CKPT_TAG_LAYERNORM);
+        if (ckpt_rd32(ln + 4) != 0) return fail_tag(ix, "reserved word not zero", CKPT_TAG_LAYERNORM);
+        ix->ln_eps = eps;
+    }
     return 0;
 }
 
@@ -226,7 +239,7 @@ int ckpt_index(const void* buf, size_t len, CkptIndex* ix) {
     ix->flags = ckpt_rd32(img + 12);
     ix->count = ckpt_rd32(img + 16);
     if (ix->version != CKPT_VERSION) return fail(ix, "unsupported version (this reader knows version 1)");
-    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST | CKPT_F_GAUSS_SD | CKPT_F_BETA))
+    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST | CKPT_F_GAUSS_SD | CKPT_F_BETA | CKPT_F_LAYERNORM))
         return fail(ix, "unknown header flags");
     if (ix->count > (len - CKPT_HEADER_BYTES) / CKPT_SECTION_BYTES)
         return fail(ix, "more sections than the file could hold");

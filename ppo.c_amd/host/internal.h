@@ -43,7 +43,11 @@ NeuralNetwork* nn_create_ex(int* layer_sizes, char** activation_functions, int n
                             int init_from_rand);
 int  nn_act_kind(const NeuralNetwork* nn, int layer);   /* 0 none, 1 relu, 2 tanh, 3 elu (ppo_hip.h PHIP_ACT_*) */
 int  nn_is_relu(const NeuralNetwork* nn, int layer);    /* kind == 1 */
-int  nn_has_hact(const NeuralNetwork* nn);              /* any layer whose derivative reads h: kind > 1 (tanh, elu) */
+/* the network takes the multi-launch loop only: a layer whose derivative reads h (kind > 1: tanh, elu), or layer
+ * normalisation on (ln_eps > 0) — the fused, folded, single-workgroup and bf16 paths know ReLU and identity layers */
+int  nn_multi_launch_only(const NeuralNetwork* nn);
+int  nn_layer_norm_ok(const NeuralNetwork* nn, float eps);   /* nn_set_layer_norm would accept eps */
+int  nn_ln_layer(const NeuralNetwork* nn, int layer);   /* layer normalisation is on and `layer` is a hidden layer */
 void nn_ensure_act(NeuralNetwork* nn, int m);
 void nn_ensure_grad(NeuralNetwork* nn, int m);
 /* device forward using d_x as layer-0 input (no copy) */

@@ -31,13 +31,18 @@ int nn_act_kind(const NeuralNetwork* nn, int layer) {
 
 int nn_is_relu(const NeuralNetwork* nn, int layer) { return nn_act_kind(nn, layer) == PHIP_ACT_RELU; }
 
-/* a layer whose derivative reads the stored post-activation h (tanh, ELU: the kinds above ReLU).  The fused and
- * single-launch paths know ReLU and identity only: a network with such a layer declines them */
-int nn_has_hact(const NeuralNetwork* nn) {
+/* a layer whose derivative reads the stored post-activation h (tanh, ELU: the kinds above ReLU), or layer
+ * normalisation between the hidden GEMMs and their activations.  The fused and single-launch paths know ReLU and
+ * identity layers only: such a network declines them */
+int nn_multi_launch_only(const NeuralNetwork* nn) {
+    if (nn->ln_eps > 0.f) return 1;
     for (int i = 0; i < nn->num_layers - 1; i++)
         if (nn_act_kind(nn, i) > PHIP_ACT_RELU) return 1;
     return 0;
 }
+
+/* the output layer is never normalised */
+int nn_ln_layer(const NeuralNetwork* nn, int layer) { return nn->ln_eps > 0.f && layer < nn->num_layers - 2; }
 
 /* ---- host mirror <-> HBM reconciliation ------------------------------------------------------
  * The reference's host-pointer functions compute from the host mirrors (Layer.weights, log_std);
@@ -220,7 +225,24 @@ static long bits_words(const NeuralNetwork* nn, int upto, int m) {   /* words be
 /* ReLU′ bit mask of layers[i].d_input (written by the forward of layer i−1) */
 static unsigned* act_bits(NeuralNetwork* nn, int i) { return nn->d_act_bits + bits_words(nn, i, nn->act_cap_m); }
 
+/* layer normalisation's blocks of hidden layer i: its pre-activations z and its rows' (mean, rstd) */
+static long ln_floats(const NeuralNetwork* nn, int upto, int m) {
+    long f = 0;
+    for (int i = 0; i < upto; i++) f += align4((long)m * nn->layers[i].output_size);    /* 16-byte aligned blocks */
+    return f;
+}
+static float* ln_z(NeuralNetwork* nn, int i) { return nn->d_ln_z + ln_floats(nn, i, nn->ln_cap_m); }
+static float* ln_stat(NeuralNetwork* nn, int i) { return nn->d_ln_stat + 2L * i * nn->ln_cap_m; }
+
 void nn_ensure_act(NeuralNetwork* nn, int m) {
+    if (nn->ln_eps > 0.f && m > nn->ln_cap_m) {       /* they exist only while the feature is on */
+        const int H = nn->num_layers - 2, cap = m > nn->act_cap_m ? m : nn->act_cap_m;
+        phip_free(nn->d_ln_z);
+        phip_free(nn->d_ln_stat);
+        nn->d_ln_z = (float*)phip_malloc(sizeof(float) * (size_t)ln_floats(nn, H, cap));
+        nn->d_ln_stat = (float*)phip_malloc(sizeof(float) * 2 * (size_t)H * (size_t)cap);
+        nn->ln_cap_m = cap;
+    }
     if (m <= nn->act_cap_m) return;
     for (int i = 0; i < nn->num_layers; i++) {
         phip_free(nn->layers[i].d_input);
@@ -351,7 +373,12 @@ static void nn_forward_dev_upto(NeuralNetwork* nn, const float* d_x, const int* 
         Layer* ly = &nn->layers[i];
         float* out = nn->layers[i + 1].d_input;
         const int n = ly->input_size, l = ly->output_size;
-        const int act = nn_act_kind(nn, i);     /* the kernels write mask bits for ReLU only (tanh′ reads h) */
+        /* a normalised layer: the GEMM leaves the bare pre-activation z in the layer's block (kind NONE, no mask
+         * bits), and layernorm.hip writes h = act(ẑ) and the rows' (mean, rstd) */
+        const int ln = nn_ln_layer(nn, i);
+        const int act = ln ? PHIP_ACT_NONE : nn_act_kind(nn, i);   /* mask bits for ReLU only (tanh′ reads h) */
+        float* h = out;
+        if (ln) out = ln_z(nn, i);
         if (fold && i == upto - 1) {            /* nn_value_fold_ok: the x3 engine takes this layer */
             fold->slots = phip_x3_fwd_vhead(out, in, i == 0 ? d_rows : NULL, i == 0 ? d_xcopy : NULL, ly->d_weights,
                                             ly->d_biases, m, n, l, act, act_bits(nn, i + 1), fold->w, fold->ypart);
@@ -364,9 +391,10 @@ static void nn_forward_dev_upto(NeuralNetwork* nn, const float* d_x, const int* 
         } else {
             phip_linear_fwd_bits(out, in, ly->d_weights, ly->d_biases, m, n, l, act, act_bits(nn, i + 1));
         }
-        in = out;
+        if (ln) phip_ln_fwd(out, h, ln_stat(nn, i), m, l, nn_act_kind(nn, i), nn->ln_eps);
+        in = h;
     }
-    nn->bits_m = m;
+    nn->bits_m = nn->ln_eps > 0.f ? -1 : m;        /* a normalised forward writes no mask bits */
     nn->cache_m_forward = m;
     nn->d_output = nn->layers[L].d_input;
 }
@@ -458,12 +486,21 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
         const float* x = i == 0 ? nn->d_x0 : ly->d_input;
         const int n = ly->input_size, l = ly->output_size;
         const int want_gx = i > 0 || want_grad_x0;
-        const int relu_in = i > 0 && nn_is_relu(nn, i - 1);
+        /* a normalised layer: its upper gradient ∂/∂h becomes ∂/∂z in place (layernorm.hip), activation derivative
+         * included — so with the feature on no GEMM of the backward takes a mask or an h operand */
+        const int ln_on = nn->ln_eps > 0.f;
+        if (nn_ln_layer(nn, i)) {
+            if (g != nn->layers[i + 1].d_grad_x) die("nn_backward_dev: a normalised layer's gradient is not the network's own");
+            if (m > nn->ln_cap_m || m != nn->cache_m_forward) die("nn_backward_dev: backward must follow a normalised forward over the same rows");
+            phip_ln_bwd(nn->layers[i + 1].d_grad_x, ln_z(nn, i), nn->layers[i + 1].d_input, ln_stat(nn, i), m, l,
+                        nn_act_kind(nn, i));
+        }
+        const int relu_in = !ln_on && i > 0 && nn_is_relu(nn, i - 1);
         const unsigned* bits = relu_in && nn->bits_m == m ? act_bits(nn, i) : NULL;   /* this forward's bits */
         /* a tanh or ELU layer below: grad_x's epilogue reads its stored post-activation (gx = acc − (acc·h)·h,
          * or h > 0 ? acc : acc·(h + 1)); bits are never required (nor written) for it.  The paired launch and
          * the wide output pass know ReLU masks only: they are not taken, grad_W and grad_x go out as two launches */
-        const int hkind = i > 0 ? nn_act_kind(nn, i - 1) : PHIP_ACT_NONE;
+        const int hkind = i > 0 && !ln_on ? nn_act_kind(nn, i - 1) : PHIP_ACT_NONE;
         const float* hin = hkind > PHIP_ACT_RELU ? ly->d_input : NULL;
         if (fold && i == top - 1) {
             /* grad_W = diag(w)·(maskᵀ·diag(g)·x), grad_b = diag(w)·maskᵀ·g, the output layer's gW = Σ g·h;
@@ -477,7 +514,7 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
                 phip_x3_bwd_x_fold(ly->d_grad_x, NULL, act_bits(nn, i + 1), fold->g, fold->w, ly->d_weights, bits, m, n,
                                    l);
             }
-        } else if (i == L - 1 && want_gx && !hin && (!relu_in || bits) &&
+        } else if (i == L - 1 && want_gx && !hin && !ln_on && (!relu_in || bits) &&
             phip_out_bwd_wide(ly->d_grad_weights, ly->d_grad_biases, ly->d_grad_x, g, x, ly->d_weights, relu_in, m, n,
                               l)) {
             /* wide output layer (A = 17): grad_x and grad_W in one pass over the rows (out_head.hip) */
@@ -510,7 +547,7 @@ int nn_out_head_ok(const NeuralNetwork* nn, int head) {
     if ((e && e[0] == '0') || phip_gemm_deterministic()) return 0;     /* its gW sums use f32 atomics */
     const int L = nn->num_layers - 1;
     if (L < 2 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE) return 0;
-    if (nn_has_hact(nn)) return 0;          /* the head kernels take relu_in: a ReLU mask or none */
+    if (nn_multi_launch_only(nn)) return 0;          /* the head kernels take relu_in: a ReLU mask or none */
     if (nn->dtype == 1 && (head != 0 || nn->param_offset[L - 1] % 8 != 0)) return 0;   /* W shadow: 16-B rows */
     return phip_out_head_supported(head, nn->layers[L - 1].input_size, nn->layers[L - 1].output_size);
 }
@@ -552,7 +589,7 @@ int nn_value_fold_ok(const NeuralNetwork* nn, int m) {
     if ((e && e[0] == '0') || phip_gemm_deterministic()) return 0;     /* atomics in the gradient sums */
     const int L = nn->num_layers - 1;
     if (nn->dtype != 0 || L < 2 || nn->output_size != 1 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE ||
-        !nn_is_relu(nn, L - 2) || nn_has_hact(nn))       /* its backward reads ReLU masks only */
+        !nn_is_relu(nn, L - 2) || nn_multi_launch_only(nn))       /* its backward reads ReLU masks only */
         return 0;
     const Layer* hid = &nn->layers[L - 2];
     const int n = hid->input_size, l = hid->output_size;
@@ -595,7 +632,7 @@ void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, 
 int nn_policy_wide_ok(const NeuralNetwork* nn, int m) {
     const int L = nn->num_layers - 1;
     if (nn->dtype != 0 || L < 2 || nn_act_kind(nn, L - 1) != PHIP_ACT_NONE || phip_gemm_deterministic()) return 0;
-    if (nn_has_hact(nn)) return 0;          /* the wide head and the fused output layer take relu_in only */
+    if (nn_multi_launch_only(nn)) return 0;          /* the wide head and the fused output layer take relu_in only */
     const Layer* ly = &nn->layers[L - 1];
     if (nn->param_offset[L - 1] % 4 != 0) return 0;                     /* 16-B aligned W / gW */
     return phip_out_bwd_wide_ok(m, ly->input_size, ly->output_size, 1);
@@ -707,11 +744,51 @@ void nn_sync_w16(NeuralNetwork* nn) {
 int nn_set_compute_dtype(void* vnn, int dtype) {
     NeuralNetwork* nn = (NeuralNetwork*)vnn;
     if (!nn || (dtype != 0 && dtype != 1)) return -1;
-    if (dtype == 1 && nn_has_hact(nn)) return -1;      /* the bf16 kernels know ReLU and identity: setting unchanged */
+    /* the bf16 kernels know ReLU and identity layers, and no layer normalisation: setting unchanged */
+    if (dtype == 1 && nn_multi_launch_only(nn)) return -1;
     if (dtype == 1 && !nn->d_w16) nn->d_w16 = (unsigned short*)phip_malloc(sizeof(unsigned short) * (size_t)nn->num_params);
     nn->dtype = dtype;
     nn->bits_m = -1;
     nn_sync_w16(nn);
+    return 0;
+}
+
+/* eps > 0 turns layer normalisation of every hidden layer on, 0 turns it off (ppo_ext.h) */
+int nn_layer_norm_ok(const NeuralNetwork* nn, float eps) {
+    if (!nn || !isfinite(eps) || eps < 0.f) return 0;
+    if (eps > 0.f) {
+        if (nn->num_layers < 3 || nn->dtype != 0) return 0;       /* no hidden layer; bf16 mode */
+        for (int i = 0; i < nn->num_layers - 2; i++)
+            if (!phip_ln_shape_ok(nn->layers[i].output_size, nn_act_kind(nn, i))) return 0;
+    }
+    return 1;
+}
+
+int nn_set_layer_norm(void* vnn, float eps) {
+    NeuralNetwork* nn = (NeuralNetwork*)vnn;
+    if (!nn_layer_norm_ok(nn, eps)) return -1;
+    nn->ln_eps = eps;
+    nn->bits_m = -1;
+    return 0;
+}
+
+int ppo_nn_ln_rows(void* vnn, int layer, float* z_out, float* stat_out, int m) {
+    NeuralNetwork* nn = (NeuralNetwork*)vnn;
+    if (!nn || !nn_ln_layer(nn, layer) || layer < 0 || m <= 0 || m > nn->cache_m_forward || m > nn->ln_cap_m) return -1;
+    if (z_out) phip_d2h(z_out, ln_z(nn, layer), sizeof(float) * (size_t)m * nn->layers[layer].output_size);
+    if (stat_out) phip_d2h(stat_out, ln_stat(nn, layer), sizeof(float) * 2 * (size_t)m);
+    return 0;
+}
+
+int ppo_layer_norm_fwd_device(const float* d_z, float* d_h, float* d_stat, int m, int l, int act, float eps) {
+    if (!d_z || !d_h || !d_stat || m <= 0 || !phip_ln_shape_ok(l, act) || !isfinite(eps) || eps <= 0.f) return -1;
+    phip_ln_fwd(d_z, d_h, d_stat, m, l, act, eps);
+    return 0;
+}
+
+int ppo_layer_norm_bwd_device(float* d_g, const float* d_z, const float* d_h, const float* d_stat, int m, int l, int act) {
+    if (!d_g || !d_z || !d_stat || m <= 0 || !phip_ln_shape_ok(l, act) || (act > PHIP_ACT_RELU && !d_h)) return -1;
+    phip_ln_bwd(d_g, d_z, d_h, d_stat, m, l, act);
     return 0;
 }
 
@@ -752,6 +829,8 @@ void free_neural_network(NeuralNetwork* nn) {
     phip_free(nn->d_w16);
     phip_free(nn->d_tiny_wt);
     phip_free(nn->d_fold_ws);
+    phip_free(nn->d_ln_z);
+    phip_free(nn->d_ln_stat);
     phip_free(nn->d_params);
     phip_free(nn->d_grads);
     nn_registry_remove(nn);

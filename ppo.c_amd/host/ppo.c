@@ -489,7 +489,7 @@ static const int* next_perm(PPO* ppo, PPODev* d, int shuffle_mode, uint64_t* key
 static int tiny_net(NeuralNetwork* nn, Adam* adam, PhipTinyNet* t, int max_w) {
     const int L = nn->num_layers - 1;
     if (nn->dtype != 0 || L < 1 || L > 8 || !adam_owns(adam, nn->d_params, nn->d_grads)) return -1;
-    if (nn_has_hact(nn)) return -1;     /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
+    if (nn_multi_launch_only(nn)) return -1;    /* the single-workgroup and cluster kernels know relu[i] ∈ {0, 1} only */
     for (int i = 0; i < L; i++)
         if (nn->layers[i].input_size > max_w || nn->layers[i].output_size > max_w) return -1;
     long nw = 0;
@@ -3048,12 +3048,27 @@ PPO* load_ppo(const char* filename, bool use_cuda) {
     return ppo;
 }
 
+/* ppo_ext.h: layer normalisation of the hidden layers of μ and V — both networks or neither */
+int ppo_set_layer_norm(void* vppo, float eps) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !nn_layer_norm_ok(ppo->V, eps) || !nn_layer_norm_ok(ppo->policy->mu, eps)) return -1;
+    nn_set_layer_norm(ppo->V, eps);
+    nn_set_layer_norm(ppo->policy->mu, eps);
+    return 0;
+}
+
+float ppo_get_layer_norm(void* vppo) {
+    PPO* ppo = (PPO*)vppo;
+    return ppo ? ppo->policy->mu->ln_eps : 0.f;
+}
+
 /* ppo_ext.h: compute precision of both networks (bf16 MFMA for config C5) */
 int ppo_set_compute_dtype(void* vppo, int dtype) {
     PPO* ppo = (PPO*)vppo;
     if (!ppo) return -1;
-    /* bf16 mode knows ReLU and identity: a tanh or ELU layer in either network declines it, both left as they were */
-    if (dtype == 1 && (nn_has_hact(ppo->V) || nn_has_hact(ppo->policy->mu))) return -1;
+    /* bf16 mode knows ReLU and identity: a tanh or ELU layer in either network, or layer normalisation, declines it,
+     * both left as they were */
+    if (dtype == 1 && (nn_multi_launch_only(ppo->V) || nn_multi_launch_only(ppo->policy->mu))) return -1;
     /* … and the categorical head reads fp32 logits: bf16 mode is declined while it is on */
     if (dtype == 1 && (cat_on((PPODev*)ppo->dev) || half_on((PPODev*)ppo->dev))) return -1;
     if (nn_set_compute_dtype(ppo->V, dtype) != 0) return -1;

@@ -44,7 +44,8 @@ class NeuralNetwork(C.Structure):
                 ("d_tiny_wt", c_float_p), ("tiny_wt_cap", C.c_long),
                 ("h_sync", c_float_p), ("dev_version", C.c_long),
                 ("host_version", C.c_long), ("host_version_w", C.c_long),
-                ("d_fold_ws", c_float_p), ("fold_ws_cap", C.c_long)]
+                ("d_fold_ws", c_float_p), ("fold_ws_cap", C.c_long),
+                ("ln_eps", C.c_float), ("ln_cap_m", C.c_int), ("d_ln_z", c_float_p), ("d_ln_stat", c_float_p)]
 
 
 class GaussianPolicy(C.Structure):
@@ -115,6 +116,13 @@ _SIGS = {
     "ppo_set_compute_dtype": (C.c_int, [_P, C.c_int]),
     "ppo_rollout_device": (None, [_P, C.c_int, C.c_int, C.c_int, C.c_ulonglong]),
     "nn_set_compute_dtype": (C.c_int, [_P, C.c_int]),
+    "nn_set_layer_norm": (C.c_int, [_P, C.c_float]),
+    "ppo_set_layer_norm": (C.c_int, [_P, C.c_float]),
+    "ppo_get_layer_norm": (C.c_float, [_P]),
+    "ppo_nn_ln_rows": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "ppo_layer_norm_fwd_device": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float]),
+    "ppo_layer_norm_bwd_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),
+    "ppo_bench_layer_norm": (C.c_double, [C.c_int] * 6 + [C.POINTER(C.c_double)]),
     "ppo_bench_gemm": (C.c_double, [C.c_int] * 6),
     "ppo_bench_streams": (C.c_double, [C.c_int] * 4),
     "ppo_build_info": (C.c_char_p, []),
