@@ -764,6 +764,12 @@ long ppo_gae_state(double* welford, float* v, float* v_next, long n);
  * calls (−1 = no cap).  GAE, the shuffles and their rand() consumption are unchanged; only the
  * loops stop early (so one step of a 1M-row, B = 32768 update can be checked against the oracle). */
 void ppo_set_step_limit(void* ppo, long max_value_steps, long max_policy_steps);
+/* The folded value step (DESIGN.md §4 "value-head fold") does not store the value network's last hidden activation:
+ * only the LAST step of an update's value loop does, so that the activations read after ppo_update are that
+ * minibatch's, like its gradients.  on = 0 drops that store too (no fold step writes the block: a capped one-step
+ * update then runs the form every other step of a full update runs), 1 restores it (the default), < 0 only queries;
+ * returns the previous setting.  Like the step limit it is not part of a checkpoint. */
+int    ppo_value_fold_keep_h(void* ppo, int on);
 
 /* Batched policy sample on device: a = μ(s) + σ·ε, ε ~ N(0,1) (counter-based
  * Philox + Box–Muller), log_prob per row.  d_* are device pointers. */
@@ -1163,6 +1169,20 @@ int    ppo_gemm16_tn_width(int bn);
 int    ppo_gemm_x3_tune(int force_cfg, int splitk_target);
 /* average device µs of one x3 launch (fp32 operands; op as ppo_bench_gemm) */
 double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int splitk_target);
+/* The value-head fold's kernels of the last hidden layer (l units, n inputs, m rows) on caller-owned device buffers,
+ * as nn_value_fold_step drives them (DESIGN.md §4 "value-head fold"); for tests and tools.
+ * forward: h = relu(x·Wᵀ + b) [m, l], its ReLU′ mask words bits [m][⌈l/32⌉] and the partial dots of h·w into
+ * ypart [slots][m]; returns slots (−1: a shape the x3 engine does not take).  nostore != 0: h is left untouched.
+ * grad_w: exactly one of h (fp32 activation: gW = diag(w)·maskᵀ·diag(g)·x, gb = diag(w)·maskᵀ·g, gw_out = Σ_rows g·h)
+ * and bits (the mask words: gW = P = maskᵀ·diag(g)·x and gb = q = maskᵀ·g unscaled; w and gw_out unused) is given;
+ * the outputs are cleared first; returns 0 (−1: unsupported).
+ * finish (behind the bits form): gW = w·P, gb = w·q, gw_out[c] = ⟨W(c,:), P(c,:)⟩ + b[c]·q[c]. */
+int    ppo_x3_fold_forward(float* h, const float* x, const float* W, const float* b, int m, int n, int l, unsigned* bits,
+                           const float* w, float* ypart, int nostore);
+int    ppo_x3_fold_grad_w(float* gW, float* gb, const float* h, const unsigned* bits, const float* g, const float* w,
+                          float* gw_out, const float* x, int m, int n, int l);
+void   ppo_x3_fold_finish(float* gW, float* gb, const float* W, const float* b, const float* w, float* gw_out, int n,
+                          int l);
 
 /* ---------------- kernel timing ---------------- */
 enum { PPO_K_GEMM = 0, PPO_K_GAE = 1, PPO_K_ADAM = 2, PPO_K_GATHER = 3, PPO_K_HEAD = 4,

@@ -69,13 +69,19 @@ struct X3Args {
     // hidden layer's kernels; neural_network.c nn_value_fold_step):
     const float* ydot;                    // forward: w — each wave's Σ_cols relu(z)·w per row into ypart
     float* ypart;                         //   [tiles_n · WARPS_N][M] (slot = column tile · WARPS_N + wave col)
+    int nostore;                          // forward with ydot: no C tile is written (the bit words and ypart are) —
+                                          // the update's own fold step, whose backward reads h's mask words only
     // backward: the upper gradient is G(i, c) = g_i·w_c·1[h(i, c) > 0] (g = ∂L/∂y), so with the 0/1 mask
     // as the operand — exact in one bf16 plane: three plane products instead of six — g and w become row /
     // column scales: grad_x = diag(g)·(mask·diag(w)·W) (W scaled per k-row by w as it is staged),
     // grad_W = diag(w)·(maskᵀ·diag(g)·x), grad_b = diag(w)·maskᵀ·g
     const float* fold_g;                  // g [M batch rows]
     const float* fold_w;                  // w [units] (grad_x: W's row scale — B = diag(w)·W staged from W)
-    const unsigned* fold_bits;            // grad_x: the mask words of h [M][fold_wpr]
+    const unsigned* fold_bits;            // grad_x: the mask words of h [M][fold_wpr]; grad_W (FOLD 2): the same
+                                          // words [K batch rows][fold_wpr] as the A operand instead of fp32 h — the
+                                          // product P = maskᵀ·diag(g)·x and the bias sum q = maskᵀ·g then leave
+                                          // UNSCALED (no fold_w, no fold_gw: fold_finish_kernel applies w and
+                                          // forms the output layer's gW from P and q)
     int fold_wpr;
     float* fold_gw;                       // grad_W (A = h, fp32): + Σ_rows g·h per unit — the output layer's gW
     // grad_W fold carrying the value head (vh_ypart set): each workgroup forms g = 2(y − t)/m of its split's
@@ -197,6 +203,13 @@ struct StageX3 {
     float gq[NV];
     const unsigned* bw_row;
     unsigned bword;
+    // … or a row-contiguous operand taken from the same words (FM 3, the fold grad_W's A = maskᵀ): the thread's
+    // 4 rows (units row … row + 3, row a multiple of 4) are 4 bits of ONE word of each k-row (batch row) — bq[q]
+    // that word for load q, bsh the first unit's bit, bon false for units past the operand (a zero image, no load
+    // past the last word)
+    unsigned bq[NV];
+    int bsh, bwpr;
+    bool bon;
 
     // src row (k-contiguous: after the gather, clamped into the operand); rows past the end read row
     // Rmax − 1 (their products land in output rows that are never stored)
@@ -217,15 +230,36 @@ struct StageX3 {
             base = p + (long)(ridx ? ridx[gr] : gr) * ld + k;
         }
     }
+    // FM 3: the operand has no fp32 source — only the thread's place in the tile
+    __device__ __forceinline__ void init_place(int tid) {
+        ld = 0;
+        base = nullptr;
+        row = (tid % (R / 4)) * 4;
+        k = tid / (R / 4);
+    }
     __device__ __forceinline__ void init_fold(const float* __restrict__ g, const unsigned* __restrict__ bits, int wpr,
                                               int r0, int Rmax) {
         sg = g;
         if (!MN && bits) bw_row = bits + (long)min(r0 + row, Rmax - 1) * wpr;
+        if (MN && bits) {
+            const int u = r0 + row;                          // r0 a multiple of 32, Rmax of 4: a quad is whole or absent
+            bon = u < Rmax;
+            bw_row = bits + min(u >> 5, wpr - 1);
+            bsh = u & 31;
+            bwpr = wpr;
+        }
     }
     // FULL: the whole k-tile lies inside [kbeg, kend) — no clamping
     template <bool FULL, int FM = 0>
     __device__ __forceinline__ void load(int k0, int kend) {
-        if (MN) {
+        if (MN && FM == 3) {
+#pragma unroll
+            for (int q = 0; q < NV; ++q) {
+                const int dk = FULL ? k0 + q * KSTEP : min(k0 + k + q * KSTEP, kend - 1) - k;
+                bq[q] = bw_row[(long)(k + dk) * bwpr];
+                gq[q] = sg[k + dk];
+            }
+        } else if (MN) {
 #pragma unroll
             for (int q = 0; q < NV; ++q) {
                 const int dk = FULL ? k0 + q * KSTEP : min(k0 + k + q * KSTEP, kend - 1) - k;
@@ -254,6 +288,23 @@ struct StageX3 {
     }
     __device__ __forceinline__ bool kvalid(int q, int k0, int kend) const {
         return MN ? k0 + k + q * KSTEP < kend : k0 + k + 4 * q < kend;
+    }
+    // FM 3: the 4 mask bits of load q (unit row + e is bit e); zero for k-rows past the split and absent units
+    template <bool FULL>
+    __device__ __forceinline__ unsigned mask4(int q, int k0, int kend) const {
+        return bon && (FULL || kvalid(q, k0, kend)) ? (bq[q] >> bsh) & 15u : 0u;
+    }
+    // FM 3: the mask as the [k][R] image's plane 0 — bf16 1.0 (0x3F80) or 0 per unit, no fp32 value, no split,
+    // no other plane (the fold's products never read planes 1 and 2 of A)
+    template <bool FULL>
+    __device__ __forceinline__ void store_mask(unsigned short* img, int k0, int kend) {
+#pragma unroll
+        for (int q = 0; q < NV; ++q) {
+            const unsigned b = mask4<FULL>(q, k0, kend);
+            const unsigned lo = ((b & 1u) ? 0x3F80u : 0u) | ((b & 2u) ? 0x3F800000u : 0u);
+            const unsigned hi = ((b & 4u) ? 0x3F80u : 0u) | ((b & 8u) ? 0x3F800000u : 0u);
+            *reinterpret_cast<u32x2*>(img + mn_off(k + q * KSTEP, row)) = u32x2{lo, hi};
+        }
     }
     // ONE: the values are exact in one bf16 plane (0/1 masks): plane 0 only, planes 1 and 2 never read
     template <bool FULL, bool ONE = false>
@@ -380,6 +431,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
     // wave's 32 rows of block row i summed over its TN column blocks, then over the 32 lanes of each
     // half-wave, reduce-scattered so that lane r < 16 ends with row e = r of its half
     constexpr int WARPS_N = BN / WN;
+    const bool store_c = !(YD && a.nostore);                // the fold's no-store forward: bit words and ypart only
     float wcol[TN];
     if constexpr (YD) {
 #pragma unroll
@@ -448,7 +500,7 @@ __device__ __forceinline__ void x3_epilogue_out(const X3Args& a, f32x16 (&acc)[T
                         v += bcol[j];
                         if constexpr (HA != 0) v = ppo::hact_fwd<HA>(v);
                         else if (a.relu) v = v > 0.f ? v : 0.f;
-                        if (ok) *dst = v;
+                        if (ok && store_c) *dst = v;
                         if constexpr (YD) yp[e] += v * wcol[j];
                         if constexpr (BITS) {
                             const unsigned long long bb = __ballot(ok && v > 0.f);
@@ -534,12 +586,17 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
 
     SA sa;
     SB sb;
-    sa.init(a.A, a.lda, OP == OP_NT ? a.ridx : nullptr, m0, a.M, lt);
+    constexpr bool a_from_bits = OP == OP_TN && FOLD == 2;        // (mbits below) A has no fp32 source
+    if constexpr (a_from_bits) sa.init_place(lt);
+    else sa.init(a.A, a.lda, OP == OP_NT ? a.ridx : nullptr, m0, a.M, lt);
     sb.init(a.B, a.ldb, nullptr, n0, a.N, lt);
     // value-head fold (grad_x: A from the mask words, B = W scaled by w per k-row; grad_W: A = h → mask,
     // B = x scaled by g per k-row)
     constexpr bool syn = OP != OP_NT && FOLD != 0;
-    constexpr int FMA_ = !syn ? 0 : OP == OP_NN ? 2 : 1;          // A's fold load mode
+    // FOLD 2 (grad_W only): A = maskᵀ staged from h's mask words, P and q left unscaled (X3Args fold_bits)
+    constexpr bool mbits = OP == OP_TN && FOLD == 2;
+    static_assert(FOLD != 2 || OP == OP_TN, "FOLD 2: the grad_W fold from the mask words");
+    constexpr int FMA_ = !syn ? 0 : OP == OP_NN ? 2 : mbits ? 3 : 1;      // A's fold load mode
     constexpr int FMB_ = syn ? 1 : 0;                             // B's
     const float* fold_g = a.fold_g;
     if constexpr (OP == OP_TN && FOLD != 0) {
@@ -582,7 +639,7 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
         }
     }
     if (syn) {
-        sa.init_fold(fold_g, OP == OP_NN ? a.fold_bits : nullptr, a.fold_wpr, m0, a.M);
+        sa.init_fold(fold_g, OP == OP_NN || mbits ? a.fold_bits : nullptr, a.fold_wpr, m0, a.M);
         sb.init_fold(OP == OP_NN ? a.fold_w : fold_g, nullptr, 0, n0, a.N);
     }
     // the fused gather's copy of A's rows: every column tile of a row block stages the same rows, so
@@ -644,6 +701,20 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
             if (((k0 - kbeg) / KB) % a.tiles_n == tn) sa.copy_out(a.acopy, a.K, m0, a.M, k0, kend);
         }
         if constexpr (SYN && OP == OP_NN) sa.bits_to_values(k0);
+        if constexpr (SYN && mbits) {
+            // A = maskᵀ from the mask words: the bias's Σ 1[h > 0]·g (valid batch rows), then the one-plane image
+#pragma unroll
+            for (int q = 0; q < SA::NV; ++q) {
+                const unsigned b4 = sa.template mask4<FULL>(q, k0, kend);
+                const float g = sa.gq[q];
+                if constexpr (BSUM) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) bs[q][e] += ((b4 >> e) & 1u) ? g : 0.f;
+                }
+            }
+            sa.template store_mask<FULL>(img, k0, kend);
+            return;
+        }
         if constexpr (SYN && OP == OP_TN) {
             // A = h: the output layer's Σ g·h and the bias's Σ 1[h > 0]·g (valid batch rows), then the mask
 #pragma unroll
@@ -817,12 +888,12 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
             float s = 0.f;
             for (int j = 0; j < S; ++j) s += red[j * BM + tid];
             if (m0 + tid < a.M) {
-                if (syn) s *= a.fold_w[m0 + tid];            // grad_b = diag(w)·maskᵀ·g
+                if (syn && !mbits) s *= a.fold_w[m0 + tid];  // grad_b = diag(w)·maskᵀ·g (FOLD 2: q, unscaled)
                 if (a.splits > 1) atomicAdd(a.gbias + m0 + tid, s);
                 else a.gbias[m0 + tid] = s;
             }
         }
-        if constexpr (OP == OP_TN && syn) {           // the folded output layer's gW: the same reduction
+        if constexpr (OP == OP_TN && syn && !mbits) { // the folded output layer's gW: the same reduction
             __syncthreads();
 #pragma unroll
             for (int q = 1; q < SA::NV; ++q) bs3[0] += bs3[q];
@@ -909,7 +980,7 @@ __device__ __forceinline__ void x3_body(const X3Args& a, int b, int grid) {
                 const int row = r0 + (e & 3) + 8 * (e >> 2);
                 const bool ok = col_ok && row < a.M;
                 float v = acc[i][j][e];
-                if (OP == OP_TN && syn) v *= a.fold_w[row < a.M ? row : a.M - 1];     // grad_W = diag(w)·(…)
+                if (OP == OP_TN && syn && !mbits) v *= a.fold_w[row < a.M ? row : a.M - 1];   // grad_W = diag(w)·(…)
                 float* dst = a.C + (long)row * a.ldc + col;
                 if (OP == OP_NT) {
                     v += bcol;
@@ -938,6 +1009,37 @@ template <int OP, int BM, int BN, int WARPS_M, int NTH, int OCC, int KG, int FOL
 __global__ __launch_bounds__(NTH, OCC) void gemm_x3_kernel(X3Args a) {
     static_assert(HA == 0 || (OP != OP_TN && FOLD == 0), "h-derived activation epilogues: plain forward and grad_x only");
     x3_body<OP, BM, BN, WARPS_M, NTH, OCC, KG, FOLD, KB, HA>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The mask-word fold's finishing step, one wave per unit c of the folded layer (l units, n inputs), launched
+// behind the grad_W launch and its slab reduce — the kernel boundary is the synchronisation; every split of
+// P = maskᵀ·diag(g)·x (in gW) and q = maskᵀ·g (in gb) has landed:
+//   gw_out[c] = ⟨W(c, :), P(c, :)⟩ + b[c]·q[c]      the output layer's gW = Σ_rows g·h(·, c), since
+//                                                   h(i, c) = mask(i, c)·(Σ_k x(i, k)·W(c, k) + b[c]);
+//                                                   the products are exact in double, summed in double, rounded once
+//   gW(c, :) = w[c]·P(c, :),   gb[c] = w[c]·q[c]    the layer's own gradients
+__global__ __launch_bounds__(256) void fold_finish_kernel(float* __restrict__ gW, float* __restrict__ gb,
+                                                          const float* __restrict__ W, const float* __restrict__ b,
+                                                          const float* __restrict__ w, float* __restrict__ gw_out, int l,
+                                                          int n) {
+    const int c = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (c >= l) return;
+    const float wc = w[c];
+    float* P = gW + (long)c * n;
+    const float* Wr = W + (long)c * n;
+    double acc = 0.0;
+    for (int k = lane; k < n; k += 64) {
+        const float p = P[k];
+        acc += (double)p * (double)Wr[k];
+        P[k] = wc * p;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) {
+        const float q = gb[c];
+        gw_out[c] = (float)(acc + (double)b[c] * (double)q);
+        gb[c] = wc * q;
+    }
 }
 
 int g_x3_last_slots = 0;                 // the last launch's ypart slots (tiles_n × waves along N)
@@ -1065,6 +1167,9 @@ void launch_tile_x3(int c, const X3Args& a) {
 
 template <int OP>
 void launch_cfg_x3(int c, const X3Args& a) {
+    if constexpr (OP == OP_TN) {
+        if (a.fold_g && a.fold_bits) { launch_tile_x3<OP, 2>(c, a); return; }   // … its grad_W from the mask words
+    }
     if (a.ydot || a.fold_g) launch_tile_x3<OP, 1>(c, a);      // the value-head fold variants
     else launch_tile_x3<OP, 0>(c, a);
 }
@@ -1153,12 +1258,14 @@ int phip_x3_supported(int op, int m, int n, int l) {
 }
 
 // ydot / ypart (value-head fold): each wave's partial y = Σ relu(z)·ydot over its columns, per row, into
-// ypart [slots][m]; returns slots (0 without the fold)
+// ypart [slots][m]; returns slots (0 without the fold).  nostore (with ydot and bits only): y is not written —
+// the layer leaves its mask words and partial dots, all that the fold's backward reads of it
 int phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                      int n, int l, int act, unsigned* bits, const float* ydot, float* ypart) {
+                      int n, int l, int act, unsigned* bits, const float* ydot, float* ypart, int nostore) {
     if (m <= 0 || l <= 0) return 0;
     PPO_REQUIRE(y && x && W && n > 0 && n % 4 == 0 && al16(x) && al16(W), "phip_x3_fwd: unsupported operands");
     PPO_REQUIRE(!ydot || ypart, "phip_x3_fwd: value-head fold without its partial buffer");
+    PPO_REQUIRE(!nostore || (ydot && bits), "phip_x3_fwd: the no-store forward is the value-head fold's, with mask words");
     const int hact = (act == PHIP_ACT_TANH || act == PHIP_ACT_ELU) ? act : 0;
     PPO_REQUIRE(!ydot || !hact, "phip_x3_fwd: the value-head fold takes a ReLU layer only");
     const int relu = act != 0 && !hact;                      // any other nonzero value: ReLU, as `relu != 0` was
@@ -1168,14 +1275,14 @@ int phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, c
     a.M = m; a.N = l; a.K = n; a.kchunk = n; a.splits = 1;
     a.bias = b; a.relu = relu; a.hact = hact; a.ridx = ridx; a.acopy = ridx ? xcopy : nullptr;
     a.bits_out = relu ? bits : nullptr; a.wpr = ppo_divup(l, 32);
-    a.ydot = ydot; a.ypart = ypart;
+    a.ydot = ydot; a.ypart = ypart; a.nostore = nostore != 0;
     launch_cfg_x3<OP_NT>(pick_x3(m, l, OP_NT), a);
     return ydot ? g_x3_last_slots : 0;
 }
 
 void phip_x3_fwd(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
                  int n, int l, int act, unsigned* bits) {
-    (void)phip_x3_fwd_vhead(y, x, ridx, xcopy, W, b, m, n, l, act, bits, nullptr, nullptr);
+    (void)phip_x3_fwd_vhead(y, x, ridx, xcopy, W, b, m, n, l, act, bits, nullptr, nullptr, 0);
 }
 
 // the upper layer's gradient A = g [m, l]; value-head fold (fold_g): A = the 0/1 mask words of h
@@ -1217,14 +1324,15 @@ void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bi
     x3_bwd_x(gx, g, nullptr, nullptr, nullptr, W, bits, h, hkind, m, n, l);
 }
 
-void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
-                         const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc);
+void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, const unsigned* fold_bits, float* fold_g,
+                         const float* fold_w, float* fold_gw, const float* x, int m, int n, int l, int zeroed,
+                         const float* ypart, int slots, const float* b, const float* tgt, float* y, float* gb_out,
+                         float* loss_accum, const PhipVClip* vc);
 
 // zeroed: gW / gb already hold zeros (one memset per backward); otherwise they are cleared here
 void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed) {
-    phip_x3_bwd_w_vhead(gW, gb, g, nullptr, nullptr, nullptr, x, m, n, l, zeroed, nullptr, 0, nullptr, nullptr, nullptr,
-                        nullptr, nullptr, nullptr);
+    phip_x3_bwd_w_vhead(gW, gb, g, nullptr, nullptr, nullptr, nullptr, x, m, n, l, zeroed, nullptr, 0, nullptr, nullptr,
+                        nullptr, nullptr, nullptr, nullptr);
 }
 
 // value-head fold (fold_g): g = h [m, l] (fp32, its mask is the operand), x scaled by fold_g per row, the
@@ -1232,20 +1340,47 @@ void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, 
 // diag(w)·maskᵀ·g — and fold_gw [l] (zero on entry) += Σ_rows fold_g·h, the output layer's gW
 void phip_x3_bwd_w_fold(float* gW, float* gb, const float* g, const float* fold_g, const float* fold_w,
                         float* fold_gw, const float* x, int m, int n, int l, int zeroed) {
-    phip_x3_bwd_w_vhead(gW, gb, g, const_cast<float*>(fold_g), fold_w, fold_gw, x, m, n, l, zeroed, nullptr, 0, nullptr,
-                        nullptr, nullptr, nullptr, nullptr, nullptr);
+    phip_x3_bwd_w_vhead(gW, gb, g, nullptr, const_cast<float*>(fold_g), fold_w, fold_gw, x, m, n, l, zeroed, nullptr, 0,
+                        nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// the same from h's mask words fold_bits [m][⌈l/32⌉] instead of fp32 h, and UNSCALED: gW = P = maskᵀ·diag(g)·x,
+// gb = q = maskᵀ·g — phip_x3_fold_finish turns them into the layer's gradients and the output layer's gW
+void phip_x3_bwd_w_fold_bits(float* gW, float* gb, const unsigned* fold_bits, const float* fold_g, const float* x, int m,
+                             int n, int l, int zeroed) {
+    phip_x3_bwd_w_vhead(gW, gb, nullptr, fold_bits, const_cast<float*>(fold_g), nullptr, nullptr, x, m, n, l, zeroed,
+                        nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+// after phip_x3_bwd_w_fold_bits (and the grad_x launch that carries its slab reduce, if one does): gW = P → w·P,
+// gb = q → w·q, gw_out [l] = the output layer's gW (fold_finish_kernel); W [l, n], b [l] the folded layer's
+// parameters, w [l] the output layer's weights
+void phip_x3_fold_finish(float* gW, float* gb, const float* W, const float* b, const float* w, float* gw_out, int n,
+                         int l) {
+    if (l <= 0 || n <= 0) return;
+    PPO_REQUIRE(gW && gb && W && b && w && gw_out, "phip_x3_fold_finish: operands");
+    PPO_REQUIRE(!ppo::g_pending[phip_side_active() ? 1 : 0].on,
+                "phip_x3_fold_finish: the split-K reduce of P is still deferred (no grad_x carried it)");
+    ppo::ProfScope ps(PPO_K_HEAD, 4.0 * (3.0 * l * n + 5.0 * l));
+    PPO_TIMED_LAUNCH(fold_finish_kernel, dim3(ppo_divup(l, 4)), dim3(256), 0, ppo::stream(), gW, gb, W, b, w, gw_out, l,
+                     n);
+    PPO_LAUNCH_CHECK();
 }
 
 // + the carried value head (ypart set): g (fold_g, written) from the forward's partial dots, y, the output
 // bias gradient gb_out and the loss, in this launch (X3Args vh_*); vc: that head's value-loss clipping (null: off)
-void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, const float* fold_w, float* fold_gw,
-                         const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc) {
+// fold_bits (with fold_g; g, fold_w and fold_gw unused): the mask-word form of phip_x3_bwd_w_fold_bits
+void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, const unsigned* fold_bits, float* fold_g,
+                         const float* fold_w, float* fold_gw, const float* x, int m, int n, int l, int zeroed,
+                         const float* ypart, int slots, const float* b, const float* tgt, float* y, float* gb_out,
+                         float* loss_accum, const PhipVClip* vc) {
     if (l <= 0 || n <= 0) return;
     PPO_REQUIRE(!vc || !vc->v_old || (ypart && vc->counts && vc->eps > 0.f), "phip_x3_bwd_w: value-clip operands");
     PPO_REQUIRE(!ypart || (fold_g && slots > 0 && b && tgt && y && gb_out), "phip_x3_bwd_w: carried value head operands");
-    PPO_REQUIRE(gW && g && x && n % 4 == 0 && l % 4 == 0 && al16(g) && al16(x), "phip_x3_bwd_w: unsupported operands");
-    PPO_REQUIRE(!fold_g || (fold_w && fold_gw && gb), "phip_x3_bwd_w: value-head fold operands");
+    PPO_REQUIRE(gW && (g || fold_bits) && x && n % 4 == 0 && l % 4 == 0 && (!g || al16(g)) && al16(x),
+                "phip_x3_bwd_w: unsupported operands");
+    PPO_REQUIRE(!fold_bits || (fold_g && gb), "phip_x3_bwd_w: the mask-word fold takes g and a bias-sum buffer");
+    PPO_REQUIRE(!fold_g || fold_bits || (fold_w && fold_gw && gb), "phip_x3_bwd_w: value-head fold operands");
     const int defer = ppo::g_defer_next;
     ppo::g_defer_next = 0;
     ppo::PendingReduce& pr = ppo::g_pending[phip_side_active() ? 1 : 0];
@@ -1276,10 +1411,11 @@ void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, co
         return;
     }
     X3Args a{};
-    a.A = g; a.lda = l; a.B = x; a.ldb = n; a.C = gW; a.ldc = n;
+    a.A = g; a.lda = l; a.B = x; a.ldb = n; a.C = gW; a.ldc = n;     // (mask words: A is null, FOLD 2 never reads it)
     a.M = l; a.N = n; a.K = m; a.kchunk = kchunk; a.splits = splits;
     a.gbias = gb;
     a.fold_g = fold_g; a.fold_w = fold_w; a.fold_gw = fold_gw;
+    a.fold_bits = fold_bits; a.fold_wpr = ppo_divup(l, 32);
     a.vh_ypart = ypart; a.vh_slots = slots; a.vh_b = b; a.vh_t = tgt; a.vh_y = y; a.vh_gb = gb_out; a.vh_loss = loss_accum;
     if (vc) a.vh_vc = *vc;
     // split-K partials: per-split slabs written with plain stores and summed by one reduce launch
@@ -1316,6 +1452,33 @@ void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* g, float* fold_g, co
     ppo::slab_reduce(a.slab, gW, (long)l * n, (long)l * n, splits, timed ? e1 : nullptr);
 }
 
+// the value fold's last-hidden-layer kernels on caller-owned device buffers (include/ppo_ext.h)
+int ppo_x3_fold_forward(float* h, const float* x, const float* W, const float* b, int m, int n, int l, unsigned* bits,
+                        const float* w, float* ypart, int nostore) {
+    ppo::ensure_device();
+    if (!phip_x3_supported(0, m, n, l)) return -1;
+    return phip_x3_fwd_vhead(h, x, nullptr, nullptr, W, b, m, n, l, 1, bits, w, ypart, nostore);
+}
+
+int ppo_x3_fold_grad_w(float* gW, float* gb, const float* h, const unsigned* bits, const float* g, const float* w,
+                       float* gw_out, const float* x, int m, int n, int l) {
+    ppo::ensure_device();
+    if (!phip_x3_supported(2, m, n, l) || (h != nullptr) == (bits != nullptr)) return -1;
+    if (h) {
+        phip_memset(gw_out, 0, sizeof(float) * (size_t)l);
+        phip_x3_bwd_w_fold(gW, gb, h, g, w, gw_out, x, m, n, l, 0);
+    } else {
+        phip_x3_bwd_w_fold_bits(gW, gb, bits, g, x, m, n, l, 0);
+    }
+    return 0;
+}
+
+void ppo_x3_fold_finish(float* gW, float* gb, const float* W, const float* b, const float* w, float* gw_out, int n,
+                        int l) {
+    ppo::ensure_device();
+    phip_x3_fold_finish(gW, gb, W, b, w, gw_out, n, l);
+}
+
 int ppo_gemm_x3_tune(int force_cfg, int splitk_target) {
     g_force_x3 = force_cfg;
     if (splitk_target >= 0) g_split_x3 = splitk_target;
@@ -1325,7 +1488,8 @@ int ppo_gemm_x3_tune(int force_cfg, int splitk_target) {
 // average device µs of one launch (op 0 forward + bias + ReLU + bits, 1 grad_x with bits, 2 grad_W
 // + bias grad (split-K from zero), 3 forward without activation, 4 – 6 the value-head fold variants of
 // 0 – 2, 7 grad_x with a tanh layer's h operand, 8 forward + bias + tanh — ppo_bench_gemm's 6, which the fold
-// holds here — 9 forward + bias + ELU, 10 grad_x with an ELU layer's h operand); cfg −1 = automatic
+// holds here — 9 forward + bias + ELU, 10 grad_x with an ELU layer's h operand, 11 the fold forward
+// without its store, 12 the fold grad_W from the mask words, 13 that grad_W + the finishing launch); cfg −1 = automatic
 double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int splitk_target) {
     ppo::ensure_device();
     const size_t sx = (size_t)m * n, sw = (size_t)l * n, sy = (size_t)m * l;
@@ -1348,7 +1512,8 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
     // a tanh / ELU layer's post-activation [m, n] (ELU's lies in (−1, ∞): the same fill serves both)
     float* hp = (op == 7 || op == 10) ? (float*)phip_malloc(4 * sx) : nullptr;
     if (hp) phip_fill_uniform(hp, (long)sx, 6, -1.f, 1.f);
-    float* fold = (op >= 4 && op <= 6) ? (float*)phip_malloc(4 * ((size_t)m * (2 * ppo_divup(l, 64) + 1) + (size_t)l)) : nullptr;
+    const bool fold_op = (op >= 4 && op <= 6) || (op >= 11 && op <= 13);
+    float* fold = fold_op ? (float*)phip_malloc(4 * ((size_t)m * (2 * ppo_divup(l, 64) + 1) + (size_t)l)) : nullptr;
     if (fold) phip_fill_uniform(fold, (long)m * (2 * ppo_divup(l, 64) + 1) + l, 5, -0.1f, 0.1f);
     auto run = [&]() {
         if (op == 0) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits);
@@ -1358,9 +1523,14 @@ double ppo_bench_gemm_x3(int op, int m, int n, int l, int iters, int cfg, int sp
         else if (op == 8) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, PHIP_ACT_TANH, nullptr);
         else if (op == 9) phip_x3_fwd(y, x, nullptr, nullptr, W, b, m, n, l, PHIP_ACT_ELU, nullptr);
         else if (op == 10) phip_x3_bwd_x(x, y, W, nullptr, hp, PHIP_ACT_ELU, m, n, l);
-        else if (op == 4) phip_x3_fwd_vhead(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits, fold, fold + l);
+        else if (op == 4) phip_x3_fwd_vhead(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits, fold, fold + l, 0);
         else if (op == 5) phip_x3_bwd_x_fold(x, nullptr, bits, fold, fold + m, W, bits, m, n, l);
         else if (op == 6) phip_x3_bwd_w_fold(gw, b, y, fold, fold + m, fold + m + l, x, m, n, l, 0);
+        else if (op == 11) phip_x3_fwd_vhead(y, x, nullptr, nullptr, W, b, m, n, l, 1, bits, fold, fold + l, 1);
+        else if (op == 12 || op == 13) {
+            phip_x3_bwd_w_fold_bits(gw, b, bits, fold, x, m, n, l, 0);
+            if (op == 13) phip_x3_fold_finish(gw, b, W, fold + m, fold + m, fold + m + l, n, l);
+        }
         else phip_x3_bwd_w(gw, b, y, x, m, n, l, 0);
     };
     for (int i = 0; i < 3; ++i) run();

@@ -119,11 +119,12 @@ void phip_x3_defer_reduce(int on);
 void phip_x3_bwd_x(float* gx, const float* g, const float* W, const unsigned* bits, const float* h, int hkind, int m,
                    int n, int l);
 void phip_x3_bwd_w(float* gW, float* gb, const float* g, const float* x, int m, int n, int l, int zeroed);
-/* value-head fold (nn_value_fold_step): forward partial y dots (returns ypart slots); backward with the
+/* value-head fold (nn_value_fold_step): forward partial y dots (returns ypart slots; nostore: y is not written,
+ * the mask words and the dots are — requires ydot and bits); backward with the
  * upper gradient g·w·1[h > 0] applied as the 0/1 mask of h with g, w as row / column scales (grad_x:
  * W pre-scaled by w) and the output layer's gW */
 int  phip_x3_fwd_vhead(float* y, const float* x, const int* ridx, float* xcopy, const float* W, const float* b, int m,
-                       int n, int l, int act, unsigned* bits, const float* ydot, float* ypart);
+                       int n, int l, int act, unsigned* bits, const float* ydot, float* ypart, int nostore);
 void phip_x3_bwd_x_fold(float* gx, const float* g, const unsigned* fold_bits, const float* fold_g, const float* fold_w,
                         const float* W, const unsigned* bits, int m, int n, int l);
 void phip_x3_bwd_w_fold(float* gW, float* gb, const float* h, const float* fold_g, const float* fold_w, float* fold_gw,
@@ -131,9 +132,19 @@ void phip_x3_bwd_w_fold(float* gW, float* gb, const float* h, const float* fold_
 /* phip_x3_bwd_w_fold carrying the value head: g (into fold_g) from the forward's partial dots ypart [slots][m]
  * + b against tgt, y, the output bias gradient gb_out and loss_accum (+= loss / m) — value_head_kernel's work;
  * vc: value-loss clipping of that head (NULL: off) */
-void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* h, float* fold_g, const float* fold_w, float* fold_gw,
-                         const float* x, int m, int n, int l, int zeroed, const float* ypart, int slots, const float* b,
-                         const float* tgt, float* y, float* gb_out, float* loss_accum, const PhipVClip* vc);
+/* fold_bits (h, fold_w, fold_gw unused): the mask-word form — see phip_x3_bwd_w_fold_bits */
+void phip_x3_bwd_w_vhead(float* gW, float* gb, const float* h, const unsigned* fold_bits, float* fold_g,
+                         const float* fold_w, float* fold_gw, const float* x, int m, int n, int l, int zeroed,
+                         const float* ypart, int slots, const float* b, const float* tgt, float* y, float* gb_out,
+                         float* loss_accum, const PhipVClip* vc);
+/* the fold's grad_W with A staged from h's mask words (fold_bits [m][⌈l/32⌉], the words the forward wrote) instead
+ * of fp32 h, leaving gW = P = maskᵀ·diag(g)·x and gb = q = maskᵀ·g UNSCALED; phip_x3_fold_finish, behind it and its
+ * slab reduce on the stream, then writes gW = w·P, gb = w·q and the output layer's gW, gw_out[c] = ⟨W(c,:), P(c,:)⟩
+ * + b[c]·q[c] (= Σ_rows g·h, h never read), the dot in double */
+void phip_x3_bwd_w_fold_bits(float* gW, float* gb, const unsigned* fold_bits, const float* fold_g, const float* x, int m,
+                             int n, int l, int zeroed);
+void phip_x3_fold_finish(float* gW, float* gb, const float* W, const float* b, const float* w, float* gw_out, int n,
+                         int l);
 /* dst[i, :] = bf16(src[rows[i], :]) for i < m (S % 4 == 0): layer 0's gather in bf16 mode */
 void phip_gather_rows_bf16(unsigned short* dst, const float* src, const int* rows, int m, int S);
 void phip_f32_to_bf16(unsigned short* dst, const float* src, long count);

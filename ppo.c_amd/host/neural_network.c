@@ -342,8 +342,9 @@ int ppo_nn_input_rows(void* vnn, float* out, int m) {
 }
 
 /* value-head fold (nn_value_fold_step): the forward's last layer also forms the partial dots of the
- * 1-wide output layer (w) into ypart, and reports their slot count */
-typedef struct { const float* w; float* ypart; int slots; } FoldFwd;
+ * 1-wide output layer (w) into ypart, and reports their slot count; nostore: that layer's activation block is
+ * NOT written (its mask words are) — the fold's backward reads nothing else of it */
+typedef struct { const float* w; float* ypart; int slots; int nostore; } FoldFwd;
 
 /* forward through the first `upto` linear layers (fp32 storage; upto = L: the whole network) */
 static void nn_forward_dev_upto(NeuralNetwork* nn, const float* d_x, const int* d_rows, float* d_xcopy, int m,
@@ -381,7 +382,8 @@ static void nn_forward_dev_upto(NeuralNetwork* nn, const float* d_x, const int* 
         if (ln) out = ln_z(nn, i);
         if (fold && i == upto - 1) {            /* nn_value_fold_ok: the x3 engine takes this layer */
             fold->slots = phip_x3_fwd_vhead(out, in, i == 0 ? d_rows : NULL, i == 0 ? d_xcopy : NULL, ly->d_weights,
-                                            ly->d_biases, m, n, l, act, act_bits(nn, i + 1), fold->w, fold->ypart);
+                                            ly->d_biases, m, n, l, act, act_bits(nn, i + 1), fold->w, fold->ypart,
+                                            fold->nostore);
         } else if (use_x3_layer(m, n, l) && phip_x3_supported(0, m, n, l)) {
             phip_x3_fwd(out, in, i == 0 ? d_rows : NULL, i == 0 ? d_xcopy : NULL, ly->d_weights, ly->d_biases, m, n,
                         l, act, act_bits(nn, i + 1));
@@ -503,17 +505,23 @@ static void nn_backward_dev_top(NeuralNetwork* nn, const float* d_grad_out, int 
         const int hkind = i > 0 && !ln_on ? nn_act_kind(nn, i - 1) : PHIP_ACT_NONE;
         const float* hin = hkind > PHIP_ACT_RELU ? ly->d_input : NULL;
         if (fold && i == top - 1) {
-            /* grad_W = diag(w)·(maskᵀ·diag(g)·x), grad_b = diag(w)·maskᵀ·g, the output layer's gW = Σ g·h;
-             * grad_x = diag(g)·(mask·diag(w)·W) ⊙ the input mask (gemm_x3.hip) */
-            const float* h = nn->layers[i + 1].d_input;
+            /* grad_W = diag(w)·P, P = maskᵀ·diag(g)·x; grad_b = diag(w)·q, q = maskᵀ·g; the output layer's gW =
+             * Σ g·h = ⟨W(c,:), P(c,:)⟩ + b(c)·q(c) per unit c; grad_x = diag(g)·(mask·diag(w)·W) ⊙ the input mask
+             * (gemm_x3.hip).  Both backward GEMMs take the mask from this forward's bit words — h itself is
+             * stored on request only (FoldFwd nostore).  grad_W leaves P and q unscaled; the finishing launch, behind grad_x (which
+             * carries P's slab reduce) and ahead of the layer's all-reduce, applies w and forms the output layer's
+             * gW.  Everything downstream (all-reduce, gradient clipping, Adam) sees finished gradients. */
+            const unsigned* hbits = act_bits(nn, i + 1);
+            if (!hbits || nn->bits_m != m) die("nn_value_fold_step: the folded layer's ReLU′ bits are missing");
             phip_x3_defer_reduce(want_gx);                    /* its slab reduce rides on grad_x */
-            phip_x3_bwd_w_vhead(ly->d_grad_weights, ly->d_grad_biases, h, fold->g, fold->w, fold->gw_out, x, m, n, l, 1,
+            phip_x3_bwd_w_vhead(ly->d_grad_weights, ly->d_grad_biases, NULL, hbits, fold->g, NULL, NULL, x, m, n, l, 1,
                                 fold->ypart, fold->slots, fold->b, fold->tgt, fold->y, fold->gb, fold->loss, fold->vc);
             if (want_gx) {
                 if (relu_in && !bits) die("nn_value_fold_step: the forward's ReLU′ bits are missing");
-                phip_x3_bwd_x_fold(ly->d_grad_x, NULL, act_bits(nn, i + 1), fold->g, fold->w, ly->d_weights, bits, m, n,
-                                   l);
+                phip_x3_bwd_x_fold(ly->d_grad_x, NULL, hbits, fold->g, fold->w, ly->d_weights, bits, m, n, l);
             }
+            phip_x3_fold_finish(ly->d_grad_weights, ly->d_grad_biases, ly->d_weights, ly->d_biases, fold->w,
+                                fold->gw_out, n, l);
         } else if (i == L - 1 && want_gx && !hin && !ln_on && (!relu_in || bits) &&
             phip_out_bwd_wide(ly->d_grad_weights, ly->d_grad_biases, ly->d_grad_x, g, x, ly->d_weights, relu_in, m, n,
                               l)) {
@@ -583,7 +591,13 @@ void nn_out_head_step(NeuralNetwork* nn, int head, const float* d_x, const int* 
  * grad_W launch forms y, the loss, g and the output bias gradient from them before its mainloop (the head
  * carried: no launch of its own), and the hidden layer's backward GEMMs take the 0/1 mask of h as their
  * operand (one bf16 plane: three MFMA plane products instead of six) with g and w as row / column scales
- * (gemm_x3.hip FOLD; grad_x stages W scaled by w per k-row). */
+ * (gemm_x3.hip FOLD; grad_x stages W scaled by w per k-row).
+ * The step never reads h: its forward writes h's mask words and the partial dots, both backward GEMMs stage the
+ * mask from those words, and the one use of h's values — the output layer's gW = Σ g·h — comes from the grad_W's
+ * own product, gW_out(c) = ⟨W(c,:), P(c,:)⟩ + b(c)·q(c) (phip_x3_fold_finish).  store_h = 0: the forward does not
+ * write h either (64 MB per C4 step), so the network's last hidden activation block keeps what an earlier forward
+ * left there — ppo_update passes 1 on the last step of its value loop, whose activations a caller may read after
+ * the update, like its gradients; y (d_output) and every other layer's block are always current. */
 int nn_value_fold_ok(const NeuralNetwork* nn, int m) {
     const char* e = getenv("PPO_VALUE_FOLD");
     if ((e && e[0] == '0') || phip_gemm_deterministic()) return 0;     /* atomics in the gradient sums */
@@ -598,7 +612,7 @@ int nn_value_fold_ok(const NeuralNetwork* nn, int m) {
 }
 
 void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, float* d_xcopy, int m, int grads_zero,
-                        long reduce_extra, const float* tgt, float* loss_accum, const PhipVClip* vc) {
+                        long reduce_extra, const float* tgt, float* loss_accum, const PhipVClip* vc, int store_h) {
     const int L = nn->num_layers - 1;
     Layer* hid = &nn->layers[L - 2];
     Layer* out = &nn->layers[L - 1];
@@ -613,7 +627,7 @@ void nn_value_fold_step(NeuralNetwork* nn, const float* d_x, const int* d_rows, 
     }
     float* ypart = nn->d_fold_ws;
     float* g = ypart + slots_max * mp;
-    FoldFwd ff = {out->d_weights, ypart, 0};
+    FoldFwd ff = {out->d_weights, ypart, 0, !store_h};
     nn_forward_dev_upto(nn, d_x, d_rows, d_xcopy, m, L - 1, &ff);
     if (ff.slots <= 0 || (size_t)ff.slots > slots_max) die("nn_value_fold_step: unexpected partial-dot slots");
     nn_ensure_grad(nn, m);

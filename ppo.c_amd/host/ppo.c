@@ -57,6 +57,7 @@ static PPODev* dev_ws(PPO* ppo, int B) {
         d = (PPODev*)xcalloc(1, sizeof(PPODev));
         d->stats = (float*)phip_malloc(4 * sizeof(float));
         d->max_v = d->max_p = -1;
+        d->fold_keep_h = 1;
         d->ep_gamma = 0.99f;
         d->clip[0] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
         d->clip[1] = (PhipClipRec*)phip_malloc(sizeof(PhipClipRec));
@@ -767,7 +768,10 @@ static int value_step(StepCtx* c, long iv, int v_zero, int tab) {
     /* with a communicator: the gradients all-reduced after the backward (comm.hip: one all-reduce in
      * this stream by default; PPO_COMM_ASYNC=1 per-layer buckets on the comm stream), joined before Adam */
     if (c->fold_v && !tab) {   /* output layer + MSE folded into the last hidden layer (nn_value_fold_step) */
-        nn_value_fold_step(V, c->state, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0, vc);
+        /* the loop's last step also stores the last hidden activation, as it leaves its gradients in place: a
+         * caller may read the last minibatch's forward after the update; every other step writes no h at all */
+        nn_value_fold_step(V, c->state, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, d->stats + 0, vc,
+                           d->fold_keep_h && iv + 1 >= c->nv);
     } else if (c->fuse_v) {    /* output layer + MSE + output-layer backward in one pass (out_head.hip) */
         nn_out_head_step(V, 0, c->state, rows, d->states, B, v_zero, c->comm ? 0 : -1, tgt, NULL, NULL,
                          NULL, NULL, 0.f, 0.f, NULL, d->stats + 0, vc);
@@ -1385,6 +1389,13 @@ void ppo_set_step_limit(void* vppo, long max_value_steps, long max_policy_steps)
     PPODev* d = dev_ws((PPO*)vppo, 1);
     d->max_v = max_value_steps;
     d->max_p = max_policy_steps;
+}
+
+int ppo_value_fold_keep_h(void* vppo, int on) {
+    PPODev* d = dev_ws((PPO*)vppo, 1);
+    const int old = d->fold_keep_h;
+    if (on >= 0) d->fold_keep_h = on != 0;
+    return old;
 }
 
 void ppo_reset_stats(void* vppo) {

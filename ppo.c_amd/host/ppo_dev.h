@@ -34,6 +34,8 @@ typedef struct {
     unsigned long long seed;
     int seeded;
     long max_v, max_p;            /* ppo_set_step_limit: cap on value / policy minibatch steps (−1: none) */
+    int fold_keep_h;              /* ppo_value_fold_keep_h: the value loop's last fold step stores its last hidden
+                                   * activation (1, the default); 0: no fold step does */
     /* launch-free minibatch steps (graph replay): per phase (0 value, 1 policy) a device step table,
      * its step counter and the Adam kernel's ticket */
     PhipStepArgs* tab[2];

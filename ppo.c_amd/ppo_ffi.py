@@ -113,6 +113,10 @@ _SIGS = {
     "ppo_gemm16_tn_width": (C.c_int, [C.c_int]),
     "ppo_gemm_x3_tune": (C.c_int, [C.c_int, C.c_int]),
     "ppo_bench_gemm_x3": (C.c_double, [C.c_int] * 7),
+    "ppo_value_fold_keep_h": (C.c_int, [_P, C.c_int]),
+    "ppo_x3_fold_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
+    "ppo_x3_fold_grad_w": (C.c_int, [_P] * 8 + [C.c_int] * 3),
+    "ppo_x3_fold_finish": (None, [_P] * 6 + [C.c_int] * 2),
     "ppo_set_compute_dtype": (C.c_int, [_P, C.c_int]),
     "ppo_rollout_device": (None, [_P, C.c_int, C.c_int, C.c_int, C.c_ulonglong]),
     "nn_set_compute_dtype": (C.c_int, [_P, C.c_int]),
