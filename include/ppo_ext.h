@@ -911,8 +911,8 @@ int ppo_env_step_device(int env_kind, float* d_env_state, const float* d_action,
  * elements and out[35] its elements m·Aa (exact integers, THIS RANK's rows under data parallelism; 0 while off).
  * ppo_save_state keeps the setting and the bounds in a section written only while the distribution is 3; save_ppo
  * keeps nothing.
- * Out of scope: Aa > 32, bf16 compute mode, a tanh squash of the action, an additive log-σ offset, and the fused,
- * cluster and graph paths.
+ * Out of scope: Aa > 32, bf16 compute mode, an additive log-σ offset, and the fused, cluster and graph paths; a tanh
+ * squash of the action is distribution 5 below.
  *
  * The setter returns 0, or −1 with the setting unchanged: NULL ppo, A odd, Aa > 32, NaN, ls_min >= ls_max, either
  * outside [−20, 20], or bf16 compute mode (ppo_set_compute_dtype(ppo, 1) returns −1 while it is on).  While it is on
@@ -998,6 +998,75 @@ int ppo_beta_sample_device(const float* d_z, int m, int A, float z_max, unsigned
                            unsigned long long offset, int deterministic, float* d_action, float* d_log_prob);
 int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
                        const float* d_old_lp, int m, int A, float z_max, float eps, double* d_row_kl, double* out3);
+
+/* ---------------- the squashed (tanh) Gaussian policy (csrc/squash.hip) ----------------
+ * The state-dependent-σ Gaussian above with its sample passed through tanh: the policy of Brax's PPO
+ * (NormalTanhDistribution), of the SAC actors and of RLlib's SquashedGaussian — bounded actions in fp32, trained from
+ * the same network shape as distribution 3.  It is action distribution 5, behind its own setter, fp32 only.  A must be
+ * even, Aa = A / 2 <= 32; a row z of μ's output is Aa means and Aa raw log σ, clamped to [ls_min, ls_max] on read,
+ * exactly as under distribution 3.  A stored action row holds a_j = tanhf(u_j) in columns 0 … Aa−1 — what an
+ * environment consumes — and the pre-squash sample u_j in columns Aa … A−1: the log-prob is taken at u, never at
+ * atanh(a), which is unbounded where tanhf rounds to ±1.  Per row, fp32, j ascending (csrc/ppo_math.h, the sq_* atoms
+ * over the sd_* ones):
+ *     ldj(x)  = 2·((ln2 − x) − softplus(−2x)),   softplus(y) = fmaxf(y, 0) + log1pf(expf(−fabsf(y)))
+ *     lp_g    = log_prob_start(Aa), then sd_lp_step(lp_g, u_j, μ_j, ls_j)
+ *     J       = Σ_j ldj(u_j)
+ *     lp      = lp_g − J                          (the log-density of a; this is what is stored)
+ *     ε_j     = normal_at(i·Aa + j, offset, key)  (the entropy stream, below; i = the minibatch row)
+ *     u′_j    = μ_j + expf(ls_j)·ε_j
+ *     H       = (entropy_start(Aa) + Σ_j ls_j) + Σ_j ldj(u′_j)
+ *     g       = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)
+ *     ∂loss/∂z_j      = sd_grad_mu(u_j, μ_j, ls_j, g) + (ent_coeff/m)·2·tanhf(u′_j)
+ *     ∂loss/∂z_{Aa+j} = in_j ? (−1 + (u_j − μ_j)²·expf(−2·ls_j))·g
+ *                             − (ent_coeff/m)·(1 − 2·tanhf(u′_j)·expf(ls_j)·ε_j)
+ *                            : +0   (written)
+ *     loss    = −Σ_rows surrogate/m − ent_coeff·(Σ_rows H)/m
+ * The entropy has no closed form: H is Brax's estimate from one fresh reparameterised sample per row, and the gradient
+ * flows through it — the −2·tanh(u′) term is what pulls means out of saturation.
+ *
+ * Sampling: u_j = μ_j + normal_at(e·Aa + j, offset, key)·expf(ls_j), key and offset those of distribution 3 at each
+ * call site; a_j = tanhf(u_j); the log-prob through the head's atoms, so the first ratio of an update is exactly 1
+ * wherever the forward gives the same z.  The deterministic action has u = μ, a = tanhf(μ).
+ * KL: the squash is one fixed bijection, so under PPO_KL_EXACT the row KL is the base Gaussians' (distribution 3's);
+ * the k3 monitor and the clip fraction read u from the second half of the action row.
+ * The entropy stream: the key is splitmix64((k ^ seed) ^ 0x5351454E54), k the first policy epoch's shuffle key of the
+ * update (the device shuffle's running key, which ppo_save_state keeps; 0 under the host shuffle, where ppo_update's
+ * seed alone distinguishes updates) and seed ppo_update's; the offset is ppo_comm_rank() << 32 | the policy step's index
+ * within the update; the counter is i·Aa + j over the minibatch's rows.  No state of its own: a run resumed by
+ * ppo_load_state draws what the interrupted run would have drawn.
+ *
+ * While it is on a policy step is forward → this head → backward in the multi-launch loop (no fused head, wide pass,
+ * single-workgroup or cluster phase, no graph replay); the log σ vector gets no gradient and stays bit-identical.
+ * ppo_rollout_device, ppo_rollout_act, ppo_act_device, ppo_eval_device and ppo_fill_synthetic sample through it;
+ * Pendulum (accepted with A == 2) receives 2·a, the synthetic environment a of column j mod Aa, CartPole declines;
+ * through ppo_rollout_act / ppo_act_device the caller gets the row [a | u] and maps a itself.  train_ppo_epoch and
+ * eval_ppo end the process with a message.  ppo_read_stats: out[4] is the mean estimated row entropy of the last
+ * policy step's minibatch, out[34] its clamped log-σ elements and out[35] its elements m·Aa.  ppo_save_state keeps the
+ * setting and the bounds in a section {1, 0, ls_min, ls_max} written only while the distribution is 5.
+ * Out of scope: Aa > 32, bf16 compute mode, a squash over the fixed-σ Gaussian (no spare action columns), Brax's
+ * softplus + min_std σ parametrisation, an affine action map for external environments, and the fused, cluster and
+ * graph paths.
+ *
+ * The setter returns 0, or −1 with the setting unchanged, in the cases ppo_set_action_gaussian_sd declines.  While it
+ * is on ppo_get_action_dist returns 5; ppo_set_action_dist(ppo, 0 | 1) switches away, ppo_set_action_dist(ppo, 5)
+ * returns −1 and ppo_set_action_mask returns −1.  The getter returns 1 while on (out2 = {ls_min, ls_max}, may be NULL),
+ * else 0. */
+int ppo_set_action_squashed_gaussian(void* ppo, float ls_min, float ls_max);
+int ppo_get_action_squashed_gaussian(void* ppo, float* out2);
+/* test and serving entries, shaped like the Beta policy's.  Each synchronises; each returns −1 with nothing launched and
+ * nothing recorded for ppo_last_error on bad arguments.  Head: the entropy stream's (key, offset) as given; d_grad
+ * [m, A], d_lp / d_ent [m], *loss the launch's loss, clamped2 = {clamped log-σ elements, m·Aa}.  Sampler: d_action
+ * [m, A] = [a | u] and d_log_prob [m] under `key` at `offset`; deterministic != 0 writes [tanhf(μ) | μ] and no log-prob
+ * (d_log_prob may be NULL).  KL: as ppo_beta_kl_device — out3 = {mean k3, clip fraction, mean closed-form KL}. */
+int ppo_squash_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp, int m,
+                           int A, float ls_min, float ls_max, float eps, float ent_coeff, unsigned long long key,
+                           unsigned long long offset, float* d_grad, float* d_lp, float* d_ent, double* loss,
+                           long long* clamped2);
+int ppo_squash_sample_device(const float* d_z, int m, int A, float ls_min, float ls_max, unsigned long long key,
+                             unsigned long long offset, int deterministic, float* d_action, float* d_log_prob);
+int ppo_squash_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
+                         const float* d_old_lp, int m, int A, float ls_min, float ls_max, float eps, double* d_row_kl,
+                         double* out3);
 
 /* ---------------- orthogonal weight initialisation (csrc/ortho.hip) ----------------
  * How Stable-Baselines3 (ortho_init, its default), CleanRL (layer_init) and baselines PPO2 start a run: every weight

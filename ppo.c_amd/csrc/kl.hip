@@ -159,7 +159,8 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
     for (long base = blockIdx.x * (long)TPB; base < m; base += (long)gridDim.x * TPB) {
         const long i = base + threadIdx.x;
         if (i < m && (!EXACT || old_lp)) {
-            const float lp = dist == 4 ? ppo::beta_lp_row(mu + i * A, action + i * A, A >> 1, sd_hi)
+            const float lp = dist == 5 ? ppo::sq_lp_row(mu + i * A, action + i * A + (A >> 1), A >> 1, sd_lo, sd_hi)
+                             : dist == 4 ? ppo::beta_lp_row(mu + i * A, action + i * A, A >> 1, sd_hi)
                              : dist == 3 ? ppo::sd_row(mu + i * A, action + i * A, A >> 1, sd_lo, sd_hi).lp
                              : mask    ? ppo::md_log_prob_row(mu + i * A, md_off, D, action + i * A,
                                                               ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
@@ -176,7 +177,7 @@ __global__ void __launch_bounds__(TPB) kl_sum_kernel(const float* __restrict__ m
                     const float* zo = ex.old_dist + (ex.rows ? (long)ex.rows[i] : i) * A;
                     const float* act = mask ? action + i * A : nullptr;
                     const double r = dist == 4 ? ppo::beta_kl_row(zo, mu + i * A, A >> 1, sd_hi)
-                                     : dist == 3 ? ppo::sd_kl_row(zo, mu + i * A, A >> 1, sd_lo, sd_hi)
+                                     : dist == 3 || dist == 5 ? ppo::sd_kl_row(zo, mu + i * A, A >> 1, sd_lo, sd_hi)
                                      : !ex.off ? ppo::kl_gauss_row(zo, ex.old_log_std, mu + i * A, log_std, A)
                                      : mask  ? ppo::kl_cat_row(zo, mu + i * A, ex.off, ex.D, act,
                                                                ppo::MaskRow{mask + (rows ? (long)rows[i] : i) * W})
@@ -264,9 +265,9 @@ void phip_policy_kl(const float* mu, const float* log_std, const float* action, 
     PPO_REQUIRE(dist != 2 || (md_off && D >= 1 && 2 * D <= A), "phip_policy_kl: multi-discrete offsets");
     PPO_REQUIRE(!mask || dist == 2, "phip_policy_kl: a mask needs the multi-discrete form (dist 1 as nvec = {A})");
     PPO_REQUIRE(ex || old_lp, "phip_policy_kl: the k3 launch needs the old log-probs");
-    const int own = dist == 3 || dist == 4;      /* [half | half] rows read under the bounds in sd */
+    const int own = dist >= 3 && dist <= 5;      /* [half | half] rows read under the bounds in sd */
     PPO_REQUIRE(!own || (sd && !mask && (A & 1) == 0 && A / 2 <= PHIP_SD_MAX_AA),
-                "phip_policy_kl: the state-dependent-σ and Beta forms need their bounds and an even A <= 64");
+                "phip_policy_kl: the state-dependent-σ, Beta and squashed forms need their bounds and an even A <= 64");
     PPO_REQUIRE(!ex || (ex->old_dist && (ex->off ? ex->D >= 1 && dist != 0 && !own
                                                  : (own || (dist == 0 && ex->old_log_std)) && !ex->wide)),
                 "phip_policy_kl: the closed-form estimator's inputs");

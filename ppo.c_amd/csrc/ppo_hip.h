@@ -167,7 +167,8 @@ void phip_sample_rows(const float* mu, const float* log_std, const int* rows, fl
  * Au (phip_env_step, phip_env_step_eval): the action columns in use — A, or A / 2 under the state-dependent-σ
  * Gaussian and the Beta policy, whose rows hold zeros after them: kind 0 then takes A = 2 and reads column 0, kind 1
  * reads column j mod Au and averages the action term over Au columns.  unit != 0 (the Beta policy): a column holds
- * x ∈ (0, 1) and the environment receives bound·(2x − 1), bound = 2 for kind 0 and 1 for kind 1 */
+ * x ∈ (0, 1) and the environment receives bound·(2x − 1), bound = 2 for kind 0 and 1 for kind 1; unit == 2 (the
+ * squashed Gaussian): a column holds tanh(u) and the environment receives bound·a */
 void phip_env_step(int kind, float* env_state, float* state, const float* action, float* next_state, float* reward,
                    uint8_t* term, uint8_t* trunc, uint8_t* cont, int E, int T, int t, uint64_t step, int S, int A,
                    uint64_t seed, int cat, const int* md_off, int D, int Au, int unit);
@@ -428,6 +429,27 @@ int  phip_ortho_shape_ok(int rows, int cols);   /* 1 <= min <= 1024, max <= 4096
  * freed after it — it runs once per training run.  Synchronises */
 void phip_ortho(PhipOrthoJob* jobs, int n);
 
+/* ---------------- squashed (tanh) Gaussian policy: head and sampler (squash.hip) ---------------- */
+/* the clipped-surrogate head over z [m, A] read as the state-dependent-σ head reads it; action [m, A] holds
+ * a = tanhf(u) in columns 0 … Aa−1 (unread) and the pre-squash sample u in columns Aa … A−1 (ppo_math.h sq_*).  The row
+ * entropy is estimated from one fresh sample: ε_j = normal_at(i·Aa + j, offset, key) for row i of this launch.
+ * grad [m, A] = ∂loss/∂z written (a clamped log-σ column: +0), lp_out / ent_out (may be NULL) [m] = the row's log-prob
+ * / entropy estimate.  rec (the state-dependent-σ head's record, used the same way): loss, Σ H, counts = {clamped
+ * log-σ elements, elements m·Aa} of this launch; d_loss_accum (may be NULL) += (float)loss by one thread.  Shapes:
+ * phip_sd_shape_ok.  One launch, deterministic: no floating-point atomics, grid a function of m, no host read. */
+void phip_sq_head(const float* z, const float* action, const float* adv, const float* old_lp, int m, int A,
+                  float ls_min, float ls_max, float epsilon, float ent_coeff, uint64_t key, uint64_t offset,
+                  float* grad, float* lp_out, float* ent_out, PhipSdRec* rec, float* d_loss_accum);
+/* u_j = μ_j + normal_at(e·Aa + j, offset, key)·expf(ls_j) for row e of z; the action row [tanhf(u) | u] and the
+ * log-prob of a (may be NULL) go to row rows[e] (rows NULL: e) */
+void phip_sq_sample(const float* z, const int* rows, float* action, float* logprob, int m, int A, float ls_min,
+                    float ls_max, uint64_t key, uint64_t offset);
+/* the rollout's form, as phip_sample_rows: the "policy noise" stream at the global step counter `step` */
+void phip_sq_sample_rows(const float* z, const int* rows, float* action, float* logprob, int E, int A, float ls_min,
+                         float ls_max, uint64_t key, uint64_t step);
+/* the deterministic action: action [m, A] ← [tanhf(μ) | μ] */
+void phip_sq_mean(const float* z, float* action, int m, int A);
+
 /* ---------------- GAE + normalisation (gae.hip) ---------------- */
 /* advantages and targets by an exact segmented reverse scan; d_welford[0..2] =
  * (n, mean, M2) in double for this shard.  Then normalise with the (global)
@@ -602,7 +624,9 @@ typedef struct {
  * unread otherwise) the clamp, lp is ppo_math.h's sd_row and, with ex, the row KL is sd_kl_row over old_dist's raw
  * rows, clamped on read (old_log_std and off are unread); log σ is unread.
  * dist 4 = the Beta policy (beta.hip): μ holds [α-logits | β-logits], sd = {−z_max, z_max}, lp is beta_lp_row and, with
- * ex, the row KL is beta_kl_row over old_dist's raw rows, clamped on read */
+ * ex, the row KL is beta_kl_row over old_dist's raw rows, clamped on read.
+ * dist 5 = the squashed Gaussian (squash.hip): μ and sd as under dist 3, lp is sq_lp_row over the u half of the action
+ * row (columns A / 2 … A−1) and, with ex, the row KL is sd_kl_row */
 void phip_policy_kl(const float* mu, const float* log_std, const float* action, const float* old_lp, int m, int A,
                     int dist, float eps, float target_kl, long rows_global, int decide_here, PhipKlRec* rec,
                     const int* md_off, int D, const uint32_t* mask, const int* rows, const PhipKlExact* ex,

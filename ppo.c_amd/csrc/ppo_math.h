@@ -349,6 +349,50 @@ __device__ __forceinline__ double sd_kl_row(const float* zo, const float* zn, in
     return kl;
 }
 
+// ---- Squashed (tanh) Gaussian (ppo_set_action_squashed_gaussian; csrc/squash.hip; no counterpart in the reference):
+// the state-dependent-σ Gaussian above over the pre-squash sample u, the action a = tanhf(u).  z is read as there
+// (sd_clamp, sd_inside); the stored action row holds a_j in columns 0 … Aa−1 and u_j in columns Aa … A−1.  Per row,
+// fp32, j ascending, through the sd_* atoms:
+//     ldj(x) = 2·((ln2 − x) − softplus(−2x)),  softplus(y) = fmaxf(y, 0) + log1pf(expf(−fabsf(y)))    sq_ldj
+//     lp_g   = log_prob_start(Aa), then sd_lp_step(lp_g, u_j, μ_j, ls_j)
+//     J      = 0, then += ldj(u_j)
+//     lp     = lp_g − J                                   the log-density of a, taken at u            sq_lp_row
+//     ε_j    = normal_at(i·Aa + j, offset, key)           the entropy stream (rng.h), i the minibatch row
+//     q_j    = expf(ls_j)·ε_j,  u′_j = μ_j + q_j          one fresh reparameterised sample            sq_fresh
+//     H      = (entropy_start(Aa), then += ls_j) + (0, then += ldj(u′_j))                             sq_entropy
+//     g      = ∂loss/∂lp from surrogate(adv, lp, old_lp, eps, m, &g)
+//     ∂loss/∂z_j      = sd_grad_mu(u_j, μ_j, ls_j, g) + cm·(2·tanhf(u′_j))                            sq_grad_mu
+//     ∂loss/∂z_{Aa+j} = in_j ? sd_grad_ls(u_j, μ_j, t_j, …, g, 0) − cm·(1 − 2·tanhf(u′_j)·q_j) : +0   sq_grad_ls
+//     loss = −Σ_rows surrogate / m − ent_coeff·(Σ_rows H) / m,   cm = ent_coeff / m
+// ldj is ln(1 − tanh²x) in the form that neither overflows nor cancels; its derivative is −2·tanh x, which is where
+// the two tanhf(u′) terms come from.  The closed-form KL is the base Gaussians' (sd_kl_row): the squash is one fixed
+// bijection.  tests/squash_ref.py restates the new terms in float64.
+__device__ __forceinline__ float sq_softplus(float y) { return fmaxf(y, 0.f) + log1pf(expf(-fabsf(y))); }
+__device__ __forceinline__ float sq_ldj(float x) { return 2.f * ((0.69314718f - x) - sq_softplus(-2.f * x)); }
+// q = expf(ls)·ε, the fresh sample's offset from the mean
+__device__ __forceinline__ float sq_fresh(float ls, float eps) { return expf(ls) * eps; }
+// lp_g the base Gaussian's log-prob at u as sd_row leaves it, J = Σ ldj(u_j), j ascending from 0 in fp32
+__device__ __forceinline__ float sq_lp(float lp_g, float J) { return lp_g - J; }
+// one thread walks one row: z its A = 2·Aa outputs, u its Aa pre-squash samples (the KL monitor; the head and the
+// sampler compute ldj a lane per element and sum the same terms in the same order)
+__device__ __forceinline__ float sq_lp_row(const float* z, const float* u, int Aa, float lo, float hi) {
+    float J = 0.f;
+    for (int j = 0; j < Aa; ++j) J += sq_ldj(u[j]);
+    return sq_lp(sd_row(z, u, Aa, lo, hi).lp, J);
+}
+// hs = entropy_start(Aa) + Σ ls_j as sd_row leaves it, jp = Σ ldj(u′_j)
+__device__ __forceinline__ float sq_entropy(float hs, float jp) { return hs + jp; }
+// th = tanhf(u′_j)
+__device__ __forceinline__ float sq_grad_mu(float u, float mu, float ls, float g, float cm, float th) {
+    return sd_grad_mu(u, mu, ls, g) + cm * (2.f * th);
+}
+// t the raw log σ, q = sq_fresh of its clamped value
+__device__ __forceinline__ float sq_grad_ls(float u, float mu, float t, float lo, float hi, float g, float cm, float th,
+                                            float q) {
+    if (!sd_inside(t, lo, hi)) return 0.f;
+    return sd_grad_ls(u, mu, t, lo, hi, g, 0.f) - cm * (1.f - 2.f * th * q);
+}
+
 // ---- Beta policy (ppo_set_action_beta; csrc/beta.hip; no counterpart in the reference): a row of μ's A outputs z is
 // Aa = A / 2 raw α-logits followed by Aa raw β-logits, clamped to [−z_max, z_max] where it is read; the action row
 // holds x_j ∈ (0, 1) in columns 0 … Aa−1 and +0 after them.  Per component, in double from the fp32 inputs:

@@ -51,6 +51,14 @@
 //                             policy noise   key splitmix64(seed ^ 0x524F4C4C)  counter (e·Aa + j) | (2·attempt + sel) << 56
 //                                            offset kNoise + g   .x .y .z as above
 //     ppo_beta_sample_device(key, offset)                 counter (i·Aa + j) | (2·attempt + sel) << 56   offset `offset`
+//   squashed Gaussian (ppo_set_action_squashed_gaussian; squash.hip; Aa = A / 2; tests/squash_ref.py): its sampler
+//   reads the state-dependent-σ Gaussian's rows above, word for word (ppo_squash_sample_device as
+//   ppo_gauss_sd_sample_device); its head draws the fresh sample of the row-entropy estimate inside the update
+//     ppo_update(seed)        entropy noise  key splitmix64((k ^ seed) ^ 0x5351454E54), k = the first policy epoch's
+//                                            shuffle key (0 under the host shuffle)
+//                                            counter i·Aa + j (i the minibatch row)
+//                                            offset ppo_comm_rank() << 32 | policy step within the update   .x .y   N(0, 1)
+//     ppo_squash_head_device(key, offset)                 counter i·Aa + j   offset `offset`   .x .y   N(0, 1)
 //   orthogonal initialisation (ppo_init_orthogonal(seed); ortho.hip): the Gaussian matrix of every layer
 //     G              key splitmix64(seed ^ 0x4F5254484F)   counter r·cols + c (the weight's own layout)
 //                    offset network << 32 | layer (network 0: μ, 1: V)   .x .y   N(0, 1)

@@ -67,9 +67,10 @@ __device__ __forceinline__ float angle_normalize(float x) {
 }
 
 // What a built-in environment receives for a stored action column a: a itself, or — unit, the Beta policy, whose
-// columns hold x ∈ (0, 1) — bound·(2x − 1), bound the environment's own (Pendulum 2, the synthetic one 1)
+// columns hold x ∈ (0, 1) — bound·(2x − 1), bound the environment's own (Pendulum 2, the synthetic one 1); or —
+// unit 2, the squashed Gaussian, whose columns hold tanh(u) ∈ [−1, 1] — bound·a
 __device__ __forceinline__ float env_action(float a, int unit, float bound) {
-    return unit ? bound * (2.f * a - 1.f) : a;
+    return unit == 2 ? bound * a : unit ? bound * (2.f * a - 1.f) : a;
 }
 
 // One Pendulum-v1 step of environment e from (θ, θ̇, steps) under action a: the transition's reward and next

@@ -99,6 +99,7 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     const int with_sd = d->action_dist == 3;
     const int with_beta = d->action_dist == 4;       /* … and the Beta policy, likewise */
     const int with_ln = ppo_get_layer_norm(ppo) > 0.f;   /* … and layer normalisation, while it is on */
+    const int with_sq = d->action_dist == 5;         /* … and the squashed Gaussian, while the distribution is 5 */
     Bytes s;
 
     put_mem(img, CKPT_MAGIC, 8);
@@ -106,9 +107,11 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
     put_u32(img, (with_buffer ? CKPT_F_BUFFER : 0u) | (with_rollout ? CKPT_F_ROLLOUT : 0u) |
                      (with_lr ? CKPT_F_LRSCHED : 0u) | (with_adv ? CKPT_F_ADVNORM : 0u) |
                      (with_klest ? CKPT_F_KLEST : 0u) | (with_sd ? CKPT_F_GAUSS_SD : 0u) |
-                     (with_beta ? CKPT_F_BETA : 0u) | (with_ln ? CKPT_F_LAYERNORM : 0u));
+                     (with_beta ? CKPT_F_BETA : 0u) | (with_ln ? CKPT_F_LAYERNORM : 0u) |
+                     (with_sq ? CKPT_F_SQUASH : 0u));
     put_u32(img, 4u + (uint32_t)with_rollout + (uint32_t)with_buffer + (uint32_t)with_lr + (uint32_t)with_adv +
-                     (uint32_t)with_klest + (uint32_t)with_sd + (uint32_t)with_beta + (uint32_t)with_ln);
+                     (uint32_t)with_klest + (uint32_t)with_sd + (uint32_t)with_beta + (uint32_t)with_ln +
+                     (uint32_t)with_sq);
 
     /* Legacy: save_ppo's byte stream */
     {
@@ -264,6 +267,16 @@ static int build_image(PPO* ppo, int flags, Bytes* img) {
         put_section(img, CKPT_TAG_LAYERNORM, &s);
         free(s.p);
     }
+
+    if (with_sq) {
+        memset(&s, 0, sizeof(s));
+        put_u32(&s, 1);
+        put_u32(&s, 0);
+        put_f32(&s, d->sd_ls[0]);
+        put_f32(&s, d->sd_ls[1]);
+        put_section(img, CKPT_TAG_SQUASH, &s);
+        free(s.p);
+    }
     return 0;
 }
 
@@ -359,6 +372,9 @@ static const char* apply_sections(PPO* ppo, const uint8_t* img, const CkptIndex*
             return "bounds or an action size ppo_set_action_gaussian_sd declines";
     } else if (ix->action_dist == 4) {
         if (ppo_set_action_beta(ppo, ix->beta_zmax) != 0) return "a z_max or an action size ppo_set_action_beta declines";
+    } else if (ix->action_dist == 5) {
+        if (ppo_set_action_squashed_gaussian(ppo, ix->sd_ls[0], ix->sd_ls[1]) != 0)
+            return "bounds or an action size ppo_set_action_squashed_gaussian declines";
     } else if (ppo_set_action_dist(ppo, ix->action_dist) != 0) {
         return "an action distribution ppo_set_action_dist declines";
     }

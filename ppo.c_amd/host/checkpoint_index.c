@@ -70,6 +70,8 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
 
     if (((ix->flags & CKPT_F_LAYERNORM) != 0) != (s[CKPT_TAG_LAYERNORM].present != 0))
         return fail(ix, "the header's layer-normalisation flag and its section disagree");
+    if (((ix->flags & CKPT_F_SQUASH) != 0) != (s[CKPT_TAG_SQUASH].present != 0))
+        return fail(ix, "the header's squashed-Gaussian flag and its section disagree");
 
     /* Legacy: five floats, then state size, action size, capacity */
     if (s[CKPT_TAG_LEGACY].len < 32) return fail_tag(ix, "shorter than the legacy header", CKPT_TAG_LEGACY);
@@ -85,7 +87,7 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
     if (s[CKPT_TAG_SETTINGS].len < CKPT_SETTINGS_FIXED) return fail_tag(ix, "too short", CKPT_TAG_SETTINGS);
     const uint8_t* st = img + s[CKPT_TAG_SETTINGS].off;
     const uint32_t dist = ckpt_rd32(st + 32), D = ckpt_rd32(st + 36);
-    if (dist > 4u || D > (uint32_t)CKPT_MD_MAX_D || (D != 0) != (dist == 2u))
+    if (dist > 5u || D > (uint32_t)CKPT_MD_MAX_D || (D != 0) != (dist == 2u))
         return fail_tag(ix, "bad action distribution or component count", CKPT_TAG_SETTINGS);
     if (s[CKPT_TAG_SETTINGS].len != CKPT_SETTINGS_FIXED + 4ull * D)
         return fail_tag(ix, "length contradicts its component count", CKPT_TAG_SETTINGS);
@@ -218,6 +220,22 @@ static int check_sections(const uint8_t* img, CkptIndex* ix) {
         ix->beta_zmax = zm;
     }
 
+    /* the squashed Gaussian: present exactly while the action distribution is 5; the state-dependent-σ section's
+     * layout under the same conditions */
+    if ((s[CKPT_TAG_SQUASH].present != 0) != (dist == 5u))
+        return fail(ix, "the action distribution and the squashed-Gaussian section disagree");
+    if (s[CKPT_TAG_SQUASH].present) {
+        if (s[CKPT_TAG_SQUASH].len != CKPT_SQUASH_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_SQUASH);
+        const uint8_t* sq = img + s[CKPT_TAG_SQUASH].off;
+        const float lo = rd_f32(sq + 8), hi = rd_f32(sq + 12);
+        if (ckpt_rd32(sq) != 1 || ckpt_rd32(sq + 4) != 0) return fail_tag(ix, "a word out of range", CKPT_TAG_SQUASH);
+        if ((A & 1u) || A / 2 > CKPT_GAUSS_SD_MAX_AA)
+            return fail_tag(ix, "the action size is odd or wider than 64", CKPT_TAG_SQUASH);
+        if (!(lo < hi) || !(lo >= -20.f) || !(hi <= 20.f)) return fail_tag(ix, "bounds outside [-20, 20]", CKPT_TAG_SQUASH);
+        ix->sd_ls[0] = lo;
+        ix->sd_ls[1] = hi;
+    }
+
     /* layer normalisation: written only while it is on, so a finite positive eps, and a zero word */
     if (s[CKPT_TAG_LAYERNORM].present) {
         if (s[CKPT_TAG_LAYERNORM].len != CKPT_LAYERNORM_BYTES) return fail_tag(ix, "bad length", CKPT_TAG_LAYERNORM);
@@ -239,7 +257,8 @@ int ckpt_index(const void* buf, size_t len, CkptIndex* ix) {
     ix->flags = ckpt_rd32(img + 12);
     ix->count = ckpt_rd32(img + 16);
     if (ix->version != CKPT_VERSION) return fail(ix, "unsupported version (this reader knows version 1)");
-    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST | CKPT_F_GAUSS_SD | CKPT_F_BETA | CKPT_F_LAYERNORM))
+    if (ix->flags & ~(uint32_t)(CKPT_F_BUFFER | CKPT_F_ROLLOUT | CKPT_F_LRSCHED | CKPT_F_ADVNORM | CKPT_F_KLEST | CKPT_F_GAUSS_SD | CKPT_F_BETA | CKPT_F_LAYERNORM |
+                                CKPT_F_SQUASH))
         return fail(ix, "unknown header flags");
     if (ix->count > (len - CKPT_HEADER_BYTES) / CKPT_SECTION_BYTES)
         return fail(ix, "more sections than the file could hold");

@@ -233,8 +233,12 @@ static int md_on(const PPODev* d) { return d && d->action_dist == 2; }
 static int sd_on(const PPODev* d) { return d && d->action_dist == 3; }
 /* the Beta policy (4): μ's outputs are [raw α-logits | raw β-logits], the log σ vector is unread */
 static int beta_on(const PPODev* d) { return d && d->action_dist == 4; }
-/* either of the two: half of the action row's columns hold the action, the head is the distribution's own */
-static int half_on(const PPODev* d) { return sd_on(d) || beta_on(d); }
+/* the squashed Gaussian (5): μ's outputs as under 3, the action row holds [tanh(u) | u]; the bounds are sd_ls */
+static int sq_on(const PPODev* d) { return d && d->action_dist == 5; }
+/* any of the three: half of the action row's columns hold the action, the head is the distribution's own */
+static int half_on(const PPODev* d) { return sd_on(d) || beta_on(d) || sq_on(d); }
+/* what phip_env_step's `unit` takes: how a built-in environment maps a stored action column */
+static int env_unit(const PPODev* d) { return beta_on(d) ? 1 : sq_on(d) ? 2 : 0; }
 /* the multi-discrete offsets for the environment and KL launches: NULL unless it is on */
 static const int* md_off(const PPODev* d) { return md_on(d) ? d->md_off : NULL; }
 
@@ -717,6 +721,7 @@ static const float* clip_coef(PPODev* d, int ph, Adam* adam, const float* side, 
     return &d->clip[ph]->coef;
 }
 
+#define SQ_ENT_TAG 0x5351454E54ULL                    /* "SQENT": the entropy stream's key is splitmix64(… ^ tag), rng.h */
 typedef struct {
     PPO* ppo;
     PPODev* d;
@@ -730,6 +735,7 @@ typedef struct {
     long Kv, Kp;                  /* steps per graph as captured */
     int phg;                      /* the phases' inputs were gathered up front (PPODev ph_*) */
     const float* state;           /* layer 0's rows: buf->state_p, or its normalised shadow (obs_prepare) */
+    uint64_t sq_key;              /* the squashed Gaussian's entropy-stream key of this update (0 while it is off) */
 } StepCtx;
 
 /* value step iv (tab: the step-table form captured into a graph: gather and Adam read their
@@ -820,11 +826,12 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
     const int cat = !tab && cat_on(d);
     const int sd = !tab && sd_on(d);
     const int beta = !tab && beta_on(d);
+    const int sq = !tab && sq_on(d);
     /* the bounds the KL launch clamps under: the state-dependent-σ pair, or {−z_max, z_max} */
     const float kl_sd[2] = {beta ? -d->beta_zmax : d->sd_ls[0], beta ? d->beta_zmax : d->sd_ls[1]};
     /* the KL monitor under masking: the masked joint lp, the categorical policy as nvec = {A} */
     const int kl_mask = cat && mask_on(d);
-    const int kl_dist = kl_mask ? 2 : cat || sd || beta ? d->action_dist : 0;
+    const int kl_dist = kl_mask ? 2 : cat || sd || beta || sq ? d->action_dist : 0;
     const int* kl_off = kl_mask ? disc_off(d) : md_off(d);
     const int kl_D = kl_mask ? disc_D(d) : d->md_D;
     const uint32_t* kl_m = kl_mask ? d->mask : NULL;
@@ -873,7 +880,18 @@ static void policy_step(StepCtx* c, long ip, int* p_zero, int* ls_zero, int tab)
         phip_beta_head(mu->d_output, act, adv, olp, B, A, d->beta_zmax, ppo->epsilon, ppo->ent_coeff, d->gmu, NULL, NULL,
                        d->sd_rec, d->stats + 1);
         nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
-    } else if (c->fuse_p) {       /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
+    } else if (sq) {       /* the squashed Gaussian: the same branch with its head (squash.hip); log σ is unused likewise */
+        if (mu->dtype != 0) die("ppo_update: the squashed Gaussian policy needs fp32 compute mode (μ is in bf16 mode)");
+        if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
+        *ls_zero = 1;
+        phip_memset(d->sd_rec, 0, offsetof(PhipSdRec, ticket));
+        d->sd_rows = B;
+        nn_forward_dev_rows(mu, c->state, rows, d->states_p, B);
+        /* the entropy stream (rng.h): the update's key, the step's index under this rank in the offset's high word */
+        phip_sq_head(mu->d_output, act, adv, olp, B, A, d->sd_ls[0], d->sd_ls[1], ppo->epsilon, ppo->ent_coeff, c->sq_key,
+                     (uint64_t)phip_comm_rank() << 32 | (uint64_t)ip, d->gmu, NULL, NULL, d->sd_rec, d->stats + 1);
+        nn_backward_dev_z(mu, d->gmu, B, 0, *p_zero, c->comm ? align4(A) : -1);
+    } else if (c->fuse_p) {      /* output layer + clipped surrogate + output-layer backward (out_head.hip) */
         if (!*ls_zero) phip_memset(pol->d_log_std_grad, 0, sizeof(float) * (size_t)A);
         nn_out_head_step(mu, 1, c->state, rows, d->states_p, B, *p_zero, c->comm ? align4(A) : -1, NULL,
                          pol->d_log_std, act, adv, olp, ppo->epsilon, ppo->ent_coeff,
@@ -1276,7 +1294,11 @@ static void ppo_update_body(PPO* ppo, float gamma, int batch_size, int n_epochs_
     const int fuse_p = !own_head && nn_out_head_ok(mu, 1);
     StepCtx c = {ppo, d, B, S, A, limit, num_batches, comm, nn_out_head_ok(V, 0), fuse_p,
                  !fuse_p && !own_head && nn_policy_wide_ok(mu, B), nn_value_fold_ok(V, B), perms_v, perms_p, keys_v, keys_p, nv, np,
-                 NULL, NULL, NULL, NULL, 16, 1, 1, 0, state};
+                 NULL, NULL, NULL, NULL, 16, 1, 1, 0, state, 0};
+    /* the squashed Gaussian's entropy stream (rng.h): keyed by what this update was seeded with — the first policy
+     * epoch's shuffle key (the device shuffle's running key, which a checkpoint keeps; 0 under the host shuffle) and
+     * the caller's seed — under a tag of its own.  No state of its own: a resumed run draws what this one would */
+    if (sq_on(d)) c.sq_key = splitmix64(((n_epochs_policy > 0 ? keys_p[0] : 0) ^ (uint64_t)seed) ^ SQ_ENT_TAG);
     {
         const char* ge = getenv("PPO_GRAPH_STEPS");
         if (ge && atoi(ge) > 0) c.K = atoi(ge);
@@ -1499,7 +1521,8 @@ void ppo_read_stats(void* vppo, double* out, int n) {
     }
     if (half_on(d) && d->sd_rec) { /* the state-dependent-σ Gaussian: the last policy step's mean row entropy and its
                                     * clamped log-σ elements and elements (this rank's rows); zeros while it is off.
-                                    * The Beta policy: the same slots, its clamped logits and its logits m·A */
+                                    * The Beta policy: the same slots, its clamped logits and its logits m·A.  The
+                                    * squashed Gaussian: the state-dependent-σ slots, the entropy its estimate */
         PhipSdRec r;
         phip_d2h(&r, d->sd_rec, offsetof(PhipSdRec, ticket));
         v[4] = d->sd_rows > 0 ? r.ent_sum / d->sd_rows : 0.0;
@@ -1690,10 +1713,14 @@ int ppo_eval_device(void* vppo, int n_envs, int horizon, int env_kind, unsigned 
         else if (beta && deterministic) phip_beta_mean(pol->mu->d_output, d->ev_act, E, A, d->beta_zmax);
         else if (beta)
             phip_beta_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, d->beta_zmax, key, step);
+        else if (sq_on(d) && deterministic) phip_sq_mean(pol->mu->d_output, d->ev_act, E, A);
+        else if (sq_on(d))
+            phip_sq_sample_rows(pol->mu->d_output, d->ev_rows, d->ev_act, d->ev_lp, E, A, d->sd_ls[0], d->sd_ls[1], key,
+                                step);
         else if (deterministic) phip_mean_action(pol->mu->d_output, d->ev_act, (long)E * A);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->ev_rows, d->ev_act, d->ev_lp, E, A, key, step);
         phip_env_step_eval(env_kind, d->ev_env, d->ev_obs, d->ev_act, d->ev_reward, d->ev_term, d->ev_trunc,
-                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D, Au, beta);
+                           d->ev_cont, E, T, t, step, S, A, key, cat, md_off(d), d->md_D, Au, env_unit(d));
     }
     phip_episode_scan(d->ev_reward, d->ev_term, d->ev_trunc, d->ev_cont, E, T, gamma, NULL, NULL, NULL, NULL,
                       d->ev_agg, NULL);
@@ -2333,6 +2360,81 @@ int ppo_beta_kl_device(const float* d_new, const float* d_old, const int* d_rows
     return 0;
 }
 
+/* ppo_ext.h: the squashed (tanh) Gaussian — the state-dependent-σ Gaussian's shapes, bounds and record */
+int ppo_set_action_squashed_gaussian(void* vppo, float ls_min, float ls_max) {
+    PPO* ppo = (PPO*)vppo;
+    if (!ppo || !sd_bounds_ok(ls_min, ls_max) || !phip_sd_shape_ok(ppo->buffer->action_size)) return -1;
+    if (ppo->V->dtype == 1 || ppo->policy->mu->dtype == 1) return -1;           /* bf16 compute mode */
+    PPODev* d = dev_ws(ppo, 1);
+    if (!d->sd_rec) d->sd_rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    d->sd_ls[0] = ls_min;
+    d->sd_ls[1] = ls_max;
+    d->action_dist = 5;
+    if (d->mask_on) mask_store(ppo, d, 0);           /* masking belongs to a discrete policy: off with it */
+    return 0;
+}
+
+int ppo_get_action_squashed_gaussian(void* vppo, float* out2) {
+    PPO* ppo = (PPO*)vppo;
+    const PPODev* d = ppo ? (const PPODev*)ppo->dev : NULL;
+    if (!sq_on(d)) return 0;
+    if (out2) { out2[0] = d->sd_ls[0]; out2[1] = d->sd_ls[1]; }
+    return 1;
+}
+
+/* the head, the sampler and the KL launch on caller-supplied device arrays (test and serving entries: bad arguments
+ * return −1 ahead of any device call, so nothing is recorded for ppo_last_error) */
+int ppo_squash_head_device(const float* d_z, const float* d_action, const float* d_adv, const float* d_old_lp, int m,
+                           int A, float ls_min, float ls_max, float eps, float ent_coeff, unsigned long long key,
+                           unsigned long long offset, float* d_grad, float* d_lp, float* d_ent, double* loss,
+                           long long* clamped2) {
+    static PhipSdRec* rec = NULL;
+    if (!d_z || !d_action || !d_adv || !d_old_lp || !d_grad || !d_lp || !d_ent || !loss || !clamped2 || m <= 0 ||
+        !phip_sd_shape_ok(A) || !sd_bounds_ok(ls_min, ls_max) || isnan(eps))
+        return -1;
+    if (!rec) rec = (PhipSdRec*)phip_malloc(sizeof(PhipSdRec));
+    phip_memset(rec, 0, offsetof(PhipSdRec, ticket));
+    phip_sq_head(d_z, d_action, d_adv, d_old_lp, m, A, ls_min, ls_max, eps, ent_coeff, key, offset, d_grad, d_lp, d_ent,
+                 rec, NULL);
+    phip_sync();
+    PhipSdRec r;
+    phip_d2h(&r, rec, offsetof(PhipSdRec, ticket));
+    *loss = r.loss;
+    clamped2[0] = (long long)r.counts[0];
+    clamped2[1] = (long long)r.counts[1];
+    return 0;
+}
+
+int ppo_squash_sample_device(const float* d_z, int m, int A, float ls_min, float ls_max, unsigned long long key,
+                             unsigned long long offset, int deterministic, float* d_action, float* d_log_prob) {
+    if (!d_z || !d_action || (!deterministic && !d_log_prob) || m <= 0 || !phip_sd_shape_ok(A) ||
+        !sd_bounds_ok(ls_min, ls_max))
+        return -1;
+    if (deterministic) phip_sq_mean(d_z, d_action, m, A);
+    else phip_sq_sample(d_z, NULL, d_action, d_log_prob, m, A, ls_min, ls_max, key, offset);
+    phip_sync();
+    return 0;
+}
+
+int ppo_squash_kl_device(const float* d_new, const float* d_old, const int* d_rows, const float* d_action,
+                         const float* d_old_lp, int m, int A, float ls_min, float ls_max, float eps, double* d_row_kl,
+                         double* out3) {
+    static PhipKlRec* rec = NULL;
+    if (!d_new || !d_old || !d_action || !d_old_lp || !out3 || m <= 0 || !phip_sd_shape_ok(A) ||
+        !sd_bounds_ok(ls_min, ls_max) || isnan(eps))
+        return -1;
+    if (!rec) rec = (PhipKlRec*)phip_malloc(sizeof(PhipKlRec));
+    phip_memset(rec, 0, offsetof(PhipKlRec, ticket));
+    const PhipKlExact ex = {d_old, NULL, d_rows, NULL, 0, 0, d_row_kl};
+    const float sd[2] = {ls_min, ls_max};
+    phip_policy_kl(d_new, NULL, d_action, d_old_lp, m, A, 5, eps, INFINITY, m, 1, rec, NULL, 0, NULL, NULL, &ex, sd);
+    phip_sync();
+    float sums[4];
+    phip_d2h(sums, rec->sums, sizeof(sums));
+    for (int k = 0; k < 3; k++) out3[k] = (double)sums[k] / m;
+    return 0;
+}
+
 /* ---- orthogonal initialisation (ppo_ext.h; csrc/ortho.hip) ---- */
 #define ORTHO_TAG 0x4F5254484FULL                     /* "ORTHO": the stream's key is splitmix64(seed ^ tag), rng.h */
 static int ortho_gain_ok(float g) { return isfinite(g) && g > 0.f; }
@@ -2580,6 +2682,9 @@ double ppo_grad_norm_device(const float* d_a, long na, const float* d_b, long nb
 void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, int n_epochs_policy,
                      int n_epochs_value) {
     /* the host rollout samples from μ(raw state): it has no handle to the normaliser */
+    if (sq_on((PPODev*)ppo->dev))
+        die("train_ppo_epoch: the squashed Gaussian policy (ppo_set_action_squashed_gaussian) is not supported by the "
+            "host rollout; use ppo_rollout_device + ppo_update");
     if (beta_on((PPODev*)ppo->dev))
         die("train_ppo_epoch: the Beta policy (ppo_set_action_beta) is not supported by the host rollout; use "
             "ppo_rollout_device + ppo_update");
@@ -2608,6 +2713,9 @@ void train_ppo_epoch(PPO* ppo, Env* env, int steps_per_epoch, int batch_size, in
 
 /* ppo.cu:560-583: rollout `steps` and print the mean discounted return J and return R */
 void eval_ppo(PPO* ppo, Env* env, int steps) {
+    if (sq_on((PPODev*)ppo->dev))
+        die("eval_ppo: the squashed Gaussian policy (ppo_set_action_squashed_gaussian) is not supported by the host "
+            "rollout; use ppo_eval_device");
     if (beta_on((PPODev*)ppo->dev))
         die("eval_ppo: the Beta policy (ppo_set_action_beta) is not supported by the host rollout; use ppo_eval_device");
     if (sd_on((PPODev*)ppo->dev))
@@ -2720,10 +2828,11 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
     const int S = b->state_size, A = b->action_size;
     PPODev* d = dev_ws(ppo, 1);
     const int cat = cat_on(d), sd = sd_on(d), beta = beta_on(d);
-    const int Au = sd || beta ? A / 2 : A;           /* the action columns the environment reads */
+    const int sq = sq_on(d);
+    const int Au = half_on(d) ? A / 2 : A;           /* the action columns the environment reads */
     if (env_kind == 0 && (S != 3 || Au != 1))
-        die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1 (2 under the state-dependent-σ Gaussian "
-            "and the Beta policy)");
+        die("ppo_rollout_device: Pendulum-v1 needs state_size 3, action_size 1 (2 under the state-dependent-σ Gaussian, "
+            "the Beta policy and the squashed Gaussian)");
     if (env_kind == 2 && (S != 4 || A != 2 || !cat))
         die("ppo_rollout_device: CartPole-v1 needs state_size 4, action_size 2 and the categorical policy "
             "(ppo_set_action_dist, or ppo_set_action_multidiscrete with nvec = {2})");
@@ -2760,10 +2869,13 @@ void ppo_rollout_device(void* vppo, int n_envs, int horizon, int env_kind, unsig
                                 key, step);
         else if (beta)
             phip_beta_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->beta_zmax, key, step);
+        else if (sq)
+            phip_sq_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
+                                key, step);
         else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, key, step);
         phip_env_step(env_kind, d->env_state, b->d_state_p, b->d_action_p, b->d_next_state_p, b->d_reward_p,
                       (uint8_t*)b->d_terminated_p, (uint8_t*)b->d_truncated_p, d->ro_cont, E, T, t, step, S, A, key,
-                      cat, md_off(d), d->md_D, Au, beta);
+                      cat, md_off(d), d->md_D, Au, env_unit(d));
     }
     ro_finish(ppo, d, E, T);
 }
@@ -2804,6 +2916,11 @@ void ppo_fill_synthetic(void* vppo, int n_envs, int horizon, unsigned long long 
         nn_forward_dev(ppo->policy->mu, obs, (int)N);
         phip_beta_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, d->beta_zmax,
                          s0 ^ 0x5, 0);
+    } else if (sq_on((PPODev*)ppo->dev)) {           /* the "action noise" key, counter i·Aa + j */
+        PPODev* d = (PPODev*)ppo->dev;
+        nn_forward_dev(ppo->policy->mu, obs, (int)N);
+        phip_sq_sample(ppo->policy->mu->d_output, NULL, b->d_action_p, b->d_logprob_p, (int)N, A, d->sd_ls[0],
+                       d->sd_ls[1], s0 ^ 0x5, 0);
     } else {
         ppo_sample_action_device(ppo->policy, obs, b->d_action_p, b->d_logprob_p, (int)N, s0 ^ 0x5, 0);
     }
@@ -2872,6 +2989,9 @@ static long long rollout_act(PPO* ppo, const uint32_t* d_mask, float* d_action) 
                             d->ext_key, step);
     else if (beta_on(d))
         phip_beta_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->beta_zmax, d->ext_key, step);
+    else if (sq_on(d))
+        phip_sq_sample_rows(pol->mu->d_output, rows, b->d_action_p, b->d_logprob_p, E, A, d->sd_ls[0], d->sd_ls[1],
+                            d->ext_key, step);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, rows, b->d_action_p, b->d_logprob_p, E, A, d->ext_key, step);
     if (!d_mask && mask_on(d)) phip_mask_fill_rows(d->mask, rows, E, A);
     phip_action_rows_out(b->d_action_p, rows, d_action, E, A);
@@ -2950,6 +3070,9 @@ static int act_device(PPO* ppo, const float* d_obs, const uint32_t* d_mask, int 
     else if (beta_on(d) && deterministic) phip_beta_mean(pol->mu->d_output, d_action, m, A, d->beta_zmax);
     else if (beta_on(d))
         phip_beta_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, d->beta_zmax, key, step);
+    else if (sq_on(d) && deterministic) phip_sq_mean(pol->mu->d_output, d_action, m, A);
+    else if (sq_on(d))
+        phip_sq_sample_rows(pol->mu->d_output, d->act_rows, d_action, lp, m, A, d->sd_ls[0], d->sd_ls[1], key, step);
     else if (deterministic) phip_mean_action(pol->mu->d_output, d_action, (long)m * A);
     else phip_sample_rows(pol->mu->d_output, pol->d_log_std, d->act_rows, d_action, lp, m, A, key, step);
     return 0;

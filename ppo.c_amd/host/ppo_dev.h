@@ -189,6 +189,9 @@ typedef struct {
      * A / 2 raw β-logits, clamped to [−beta_zmax, beta_zmax] on read.  Its head leaves its record in sd_rec and its
      * rows in sd_rows, as the state-dependent-σ head does: counts = {clamped logits, logits m·A} */
     float beta_zmax;
+    /* the squashed Gaussian (ppo_set_action_squashed_gaussian; action_dist == 5; csrc/squash.hip) keeps nothing of its
+     * own: its bounds are sd_ls, its head's record sd_rec and its rows sd_rows; the entropy stream's key is derived
+     * in every update from that update's seed material */
 } PPODev;
 
 /* ppo.c: the PPO's PPODev, created on first use (as every setter does) */

@@ -209,6 +209,15 @@ _SIGS = {
                                      C.POINTER(C.c_double)]),
     "ppo_init_orthogonal": (C.c_int, [_P, C.c_ulonglong, C.c_float, C.c_float, C.c_float]),
     "ppo_orthogonal_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_float]),
+    "ppo_set_action_squashed_gaussian": (C.c_int, [_P, C.c_float, C.c_float]),
+    "ppo_get_action_squashed_gaussian": (C.c_int, [_P, C.POINTER(C.c_float)]),
+    "ppo_squash_head_device": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                         C.c_ulonglong, C.c_ulonglong, _P, _P, _P, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_longlong)]),
+    "ppo_squash_sample_device": (C.c_int, [_P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_ulonglong, C.c_ulonglong,
+                                           C.c_int, _P, _P]),
+    "ppo_squash_kl_device": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, _P,
+                                       C.POINTER(C.c_double)]),
     "ppo_set_action_mask": (C.c_int, [_P, C.c_int]),
     "ppo_get_action_mask": (C.c_int, [_P]),
     "ppo_action_mask_words": (C.c_int, [_P]),
